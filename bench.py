@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- corner residual + Jacobian evaluations per second on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N > 1: one rank per GPU.  Launched bare, bench.py re-executes itself through `python -m torch.distributed.run
    --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`; launched by torch.distributed.run it reads RANK / WORLD_SIZE.)
 
@@ -56,7 +56,42 @@ def parse():
                          "(emit_sweep, the chunked host route of pcie_inclusive) and the calib / pose-init sections, so that the "
                          "kernel's average in a rocprofv3 trace of this command is the headline launch's")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU-baseline budget per leg")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (residuals and Jacobian blocks, float64; "
+                         "a fixed sample of images when the whole output exceeds %d MB) as DIR/<name>.npy (rank 0's shard)"
+                    % (DUMP_BUDGET_BYTES // 10 ** 6))
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(directory, res, ji, jm):
+    """The arrays a caller of the timed step receives (vg_dataset_evaluate: residuals, intrinsic and member Jacobian
+    blocks, one row block per image), as <directory>/<name>.npy in float64.  When all of them together exceed
+    DUMP_BUDGET_BYTES, the same fixed, seeded sample of images is taken from each; image_index.npy names the rows."""
+    import numpy as np
+    import torch
+
+    arrays = [("residuals", res), ("jac_intrinsics", ji)] + [("jac_member%d" % l, t) for l, t in enumerate(jm)]
+    arrays = [(name, t) for name, t in arrays if t is not None]
+    n_img = res.shape[0]
+    per_image = sum(t[0].numel() * 8 for _, t in arrays) + 8
+    keep = min(n_img, (DUMP_BUDGET_BYTES - 64 * 1024) // per_image)
+    if keep < n_img:
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_img, keep, replace=False))
+    else:
+        pick = np.arange(n_img)
+    os.makedirs(directory, exist_ok=True)
+    idx = torch.from_numpy(pick).to(res.device)
+    for name, t in arrays:
+        np.save(os.path.join(directory, name + ".npy"), t.index_select(0, idx).to(torch.float64).cpu().numpy())
+    np.save(os.path.join(directory, "image_index.npy"), pick.astype(np.float64))
+    print("[bench] outputs of the last timed step: %d of %d images -> %s" % (keep, n_img, directory), file=sys.stderr)
 
 
 def _cgroup_cpu_max():
@@ -390,6 +425,8 @@ def main():
         all_reduce_(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert p.failed_count(ds) == 0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res, ji, jm)
     value = world * n_obs * a.steps / elapsed
     from visgeom_amd import capi
 

@@ -66,10 +66,11 @@ def one_rank():
     return line
 
 
-@pytest.mark.parametrize("n_ranks", [2, 8])
+@pytest.mark.parametrize("n_ranks", [2, 3])
 def test_ranks_over_gloo_on_one_gpu_run_every_section_and_reach_the_one_rank_optimum(one_rank, n_ranks):
-    """2 ranks, and the 8 of the driver's scaling run (the shard arithmetic, every collective and the deadline thread with the
-    world size the real run has)"""
+    """2 ranks, and 3 (an odd world size: the shard arithmetic, every collective and the deadline thread with more than two
+    ranks).  Every rank keeps the one device open, and rank 0 starts the `calib` program next to them: the world stays small
+    enough that, with the process running this suite, no more than 6 processes share a GPU at once."""
     line, err = run([sys.executable, "bench.py", "--gpus", str(n_ranks)] + SMALL, {"VG_BENCH_BACKEND": "gloo"})
     assert line["n_gpus"] == n_ranks and line["scaling"] == "weak"
     check_sections(line)
