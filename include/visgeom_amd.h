@@ -544,6 +544,27 @@ void vg_reproject_destroy(vg_reproject_set *s);
 int vg_camera_jacobian_evaluate(int device, void *hip_stream, int model, const double *intrinsics, const double *T12,
                                 const double *T23, int64_t n, const double *X2, const double *grad, double *dpdxi, double *dfdxi);
 
+/* =====================================================================================
+ * 7. Fisheye rectification: the reference's `rectify` program (test/calibration/rectify.cpp) on the GPU.  Stateless entries on
+ *    DEVICE pointers, asynchronous on hip_stream (no allocation, no synchronisation: a caller may capture them).  Every image
+ *    and map side is in [1, 16384]; arrays are dense (pitch = width).
+ * ===================================================================================== */
+/* initRemap (rectify.cpp:27-58) for EUCM / UCM / Mei: pinhole5 = [width, height, u0, v0, f] (HOST), xi6 = the pinhole -> camera
+ * transform [t, rotvec] (HOST).  Pixel (j, i) of the pinhole is the ray ((j - u0) / f, (i - v0) / f, 1) (pinhole.h:40-49), moved
+ * by R(xi) X + t(xi) (transformation.h:167-171) and projected in FP64 in the reference's order; map_x / map_y DEVICE float
+ * [height][width] receive the projection rounded to float.  A failed projection gives (-1, -1) (the reference leaves the
+ * pinhole pixel itself there: DESIGN.md section 9). */
+int vg_rectify_map(int device, void *hip_stream, int model, const double *intrinsics, const double *pinhole5, const double *xi6,
+                   float *map_x, float *map_y);
+enum vg_pixel_type { VG_PIXEL_U8 = 0, VG_PIXEL_F32 = 1 };
+/* cv::remap(INTER_LINEAR, BORDER_CONSTANT) of n_images same-size images through ONE map pair, in one launch: src DEVICE
+ * [n_images][src_h][src_w][channels], dst DEVICE [n_images][map_h][map_w][channels], pixel_type u8 or f32, channels 1, 3 or 4.
+ * A map entry outside (-1, src_w) x (-1, src_h), or NaN, gives `fill`; inside, the float32 bilinear blend of the four taps, a tap
+ * outside the image reading `fill`; u8 output is rounded half to even and saturated.  The fractional part is not quantised to
+ * 1/32 pixel as OpenCV's is. */
+int vg_remap(int device, void *hip_stream, int pixel_type, int channels, int64_t n_images, int src_w, int src_h, const void *src,
+             int map_w, int map_h, const float *map_x, const float *map_y, double fill, void *dst);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the A/B
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_force_mfma",
  * "gram_ch1", "gram_no_merge", "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop",

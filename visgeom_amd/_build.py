@@ -27,10 +27,12 @@ PRODUCTION_LIB = os.path.join(LIB_DIR, "production", "libvisgeom_amd.so")
 def sources():
     """the translation units of the library: every .hip file of csrc/ (vg_capi: problem assembly + emit; vg_gram_tu: normal
     equations; vg_solver_tu: LM / Schur + communicator; vg_refine_tu: per-image pose LM; vg_frontend_tu: calibration JSON;
-    vg_local_tu: localization costs)"""
+    vg_local_tu: localization costs; vg_rectify_tu: rectification maps and remap)"""
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
 
 
+# the host programs build_cli() makes: name -> source in csrc/
+CLI_SOURCES = {"calib": "calib_main.cpp", "rectify": "rectify_main.cpp"}
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 STAMP = os.path.join(LIB_DIR, "libvisgeom_amd.sources.sha256")
 _INCLUDE = None
@@ -80,13 +82,15 @@ def sources_digest():
     h = hashlib.sha256()
     for src in sources():
         h.update(unit_digest(src).encode())
-    with open(os.path.join(CSRC, "calib_main.cpp"), "rb") as fh:
-        h.update(fh.read())
+    for main in CLI_SOURCES.values():   # the host programs, with the project headers they include
+        for f in sorted(_closure(os.path.join(CSRC, main))):
+            with open(f, "rb") as fh:
+                h.update(fh.read())
     return h.hexdigest()
 
 
 def up_to_date():
-    if not os.path.exists(LIB) or not os.path.exists(os.path.join(PKG, "bin", "calib")) or not os.path.exists(STAMP):
+    if not os.path.exists(LIB) or not all(os.path.exists(os.path.join(PKG, "bin", c)) for c in CLI_SOURCES) or not os.path.exists(STAMP):
         return False
     with open(STAMP) as fh:
         return fh.read().strip() == sources_digest()
@@ -178,16 +182,22 @@ def build_variant(name, extra_flags, verbose=False, out=None, drop_flags=()):
 
 BIN_DIR = os.path.join(PKG, "bin")
 CLI = os.path.join(BIN_DIR, "calib")
+RECTIFY_CLI = os.path.join(BIN_DIR, "rectify")
+ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 
 def build_cli(verbose=False):
-    """the reference's `calib file1.json [file2.json ...]` entry point: a host-only C++ program on the C ABI"""
+    """the reference's programs, host-only C++ on the C ABI: `calib file1.json [file2.json ...]` and `rectify file.json` (which
+    also calls the HIP runtime for its device buffers)"""
     os.makedirs(BIN_DIR, exist_ok=True)
-    cmd = ["g++", "-O2", "-std=c++17", "-Wall", os.path.join(CSRC, "calib_main.cpp"), "-o", CLI,
-           "-L" + LIB_DIR, "-lvisgeom_amd", "-Wl,-rpath," + LIB_DIR, "-Wl,-rpath,/opt/rocm/lib"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
+    common = ["-L" + LIB_DIR, "-lvisgeom_amd", "-Wl,-rpath," + LIB_DIR, "-Wl,-rpath," + os.path.join(ROCM, "lib")]
+    cmds = [["g++", "-O2", "-std=c++17", "-Wall", os.path.join(CSRC, CLI_SOURCES["calib"]), "-o", CLI] + common,
+            ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROCM, "include"),
+             os.path.join(CSRC, CLI_SOURCES["rectify"]), "-o", RECTIFY_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"]]
+    for cmd in cmds:
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
     return CLI
 
 

@@ -23,6 +23,7 @@ MAX_CHAIN = 5
 DOUBLE_BIG = 1e15
 OK = 0
 ERR_INVALID_ARGUMENT, ERR_HIP, ERR_NO_DEVICE, ERR_STATE, ERR_ALLOC, ERR_NUMERIC = 1, 2, 3, 4, 5, 6
+PIXEL_U8, PIXEL_F32 = 0, 1
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, _dp, ctypes.c_int64, ctypes.c_void_p)
 
@@ -177,6 +178,9 @@ SIGNATURES = {
     "vg_reproject_synchronize": (ctypes.c_int, [_vp]),
     "vg_reproject_destroy": (None, [_vp]),
     "vg_camera_jacobian_evaluate": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _dp, _dp, _dp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "vg_rectify_map": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _dp, _dp, _dp, _vp, _vp]),
+    "vg_remap": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp,
+                                ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_double, _vp]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),
