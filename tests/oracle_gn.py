@@ -10,6 +10,8 @@ Nothing here touches the product: rows from oracle/vgo.py, algebra from numpy.  
 A case is the dict of tests/golden_cases.py (cameras / transforms / datasets, image b of a dataset uses element b of its
 sequence transform).
 """
+import os
+
 import numpy as np
 
 from tests import golden_cases as G
@@ -55,86 +57,16 @@ def shard_case(c, lo, hi):
 def gauss_newton_step(c, x, threads=None):
     """-> dict(cost, dg [G], gcols [G] parameter index of every global column, dp [P, 6], pose_param [P] first parameter
     of every pose block, grad_g, grad_p).  Undamped: (J^T J) delta = -J^T r, solved through the Schur complement of the
-    pose blocks; global parameters sitting on a bound of their camera's box with the step pointing outwards are held."""
-    import os
-
-    from oracle import vgo
+    pose blocks; global parameters sitting on a bound of their camera's box with the step pointing outwards are held.
+    The mu = 0, no-loss case of the damped step of tests/oracle_lm.py."""
+    from tests import oracle_lm
 
     if threads is None:
         threads = max(1, min(32, os.cpu_count() or 1))
-    x = np.asarray(x, float)
-    cam_off, tf_off, _, lb, ub = G.layout(c)
-    gcols, cam_g, tf_g = [], [], {}
-    for (model, _), o in zip(c["cameras"], cam_off):
-        K = vgo.NUM_INTRINSICS[vgo.MODELS[model]]
-        cam_g.append(np.arange(len(gcols), len(gcols) + K))
-        gcols += list(range(o, o + K))
-    pose_base, pose_param = {}, []
-    for t, (is_global, vals) in enumerate(c["transforms"]):
-        if is_global:
-            tf_g[t] = np.arange(len(gcols), len(gcols) + 6)
-            gcols += list(range(tf_off[t], tf_off[t] + 6))
-        else:
-            pose_base[t] = len(pose_param)
-            pose_param += [tf_off[t] + 6 * i for i in range(np.asarray(vals).reshape(-1, 6).shape[0])]
-    gcols, pose_param = np.array(gcols, dtype=np.int64), np.array(pose_param, dtype=np.int64)
-    Gn, P = gcols.size, pose_param.size
-    U, gg = np.zeros((Gn, Gn)), np.zeros(Gn)
-    V, W, gp = np.zeros((P, 6, 6)), np.zeros((P, Gn, 6)), np.zeros((P, 6))
-    cost2 = 0.0
-    for cam, chain, board, corners in c["datasets"]:
-        model = vgo.MODELS[c["cameras"][cam][0]]
-        n, N = np.asarray(corners).shape[0], np.asarray(board).shape[0]
-        if n == 0:
-            continue
-        status = [s for _, s in chain]
-        bases = [tf_off[t] for t, _ in chain]
-        strides = [0 if c["transforms"][t][0] else 6 for t, _ in chain]
-        r, ji, jm = vgo.eval_dataset(model, status, board, corners, x, cam_off[cam], bases, strides, np.arange(n), threads=threads)
-        cost2 += float(np.sum(r * r))
-        cols = [cam_g[cam]]
-        blocks = [ji]
-        B, pb = None, None
-        for l, (t, _) in enumerate(chain):
-            if c["transforms"][t][0]:
-                cols.append(tf_g[t])
-                blocks.append(jm[l])
-            else:
-                assert B is None, "one sequence member per chain"
-                B, pb = jm[l], pose_base[t]
-        cols = np.concatenate(cols)
-        A = np.concatenate(blocks, axis=2)                       # [n, 2N, G_local]
-        A2 = A.reshape(-1, A.shape[2])
-        U[np.ix_(cols, cols)] += A2.T @ A2
-        gg[cols] += A2.T @ r.ravel()
-        if B is not None:
-            V[pb:pb + n] += np.einsum("bri,brj->bij", B, B)
-            W[pb:pb + n][:, cols, :] += np.einsum("bri,brj->bij", A, B)
-            gp[pb:pb + n] += np.einsum("bri,br->bi", B, r)
-    seen = np.einsum("pii->p", V) > 0                            # poses without observations do not move
-    Vs = V.copy()
-    Vs[~seen] = np.eye(6)
-    rhs_p = np.concatenate([np.swapaxes(W, 1, 2), gp[:, :, None]], axis=2)   # [P, 6, G + 1]
-    rhs_p[~seen] = 0.0
-    X = np.linalg.solve(Vs, rhs_p)                               # V^-1 [W^T | g_p]
-    S = U - np.einsum("pgi,pih->gh", W, X[:, :, :Gn])
-    rhs = -gg + np.einsum("pgi,pi->g", W, X[:, :, Gn])
-    held = np.zeros(Gn, dtype=bool)
-    dg = np.zeros(Gn)
-    for _ in range(Gn + 1):
-        f = ~held
-        dg = np.zeros(Gn)
-        if f.any():
-            dg[f] = np.linalg.solve(S[np.ix_(f, f)], rhs[f])
-        xg = x[gcols]
-        out = f & (((xg <= lb[gcols]) & (dg < 0)) | ((xg >= ub[gcols]) & (dg > 0)))
-        if not out.any():
-            break
-        held |= out
-    dp = -(X[:, :, Gn] + np.einsum("pig,g->pi", X[:, :, :Gn], dg))
-    dp[~seen] = 0.0
-    return {"cost": 0.5 * cost2, "dg": dg, "gcols": gcols, "dp": dp, "pose_param": pose_param, "grad_g": gg, "grad_p": gp,
-            "held": held}
+    sy = oracle_lm.arrow_system(c, x, threads=threads)
+    st = oracle_lm.damped_step(sy, 0.0)
+    return {"cost": sy["cost"], "dg": st["dg"], "gcols": sy["gcols"], "dp": st["dp"], "pose_param": sy["pose_param"],
+            "grad_g": sy["gg"], "grad_p": sy["gp"], "held": st["held"]}
 
 
 def assert_converged(c, x, final_cost, tol=1e-6, cost_rtol=1e-9, cost_scale=1.0, what=""):
