@@ -46,7 +46,8 @@ NAMES = ["mono_eucm", "mono_ucm", "mono_mei", "stereo", "rig"]
 
 
 def layout(c):
-    """offsets of every camera / transform in the parameter vector, the initial vector, the box bounds"""
+    """offsets of every camera / transform in the parameter vector, the initial vector, the box bounds (free-standing
+    parameter blocks, the optional case key "parameter_blocks" of tests/oracle_lm.py, follow the transforms, unbounded)"""
     from oracle import vgo
 
     off, cam_off, tf_off = 0, [], []
@@ -56,13 +57,26 @@ def layout(c):
     for _, vals in c["transforms"]:
         tf_off.append(off)
         off += np.asarray(vals).size
+    blocks = [np.asarray(v, float).ravel() for v, _ in c.get("parameter_blocks", ())]
+    off += sum(b.size for b in blocks)
     x0 = np.concatenate([np.asarray(i, float).ravel() for _, i in c["cameras"]] +
-                        [np.asarray(v, float).ravel() for _, v in c["transforms"]])
+                        [np.asarray(v, float).ravel() for _, v in c["transforms"]] + blocks)
     lb, ub = np.full(off, -np.inf), np.full(off, np.inf)
     for (model, _), o in zip(c["cameras"], cam_off):
         lo, hi = BOUNDS[model]
         lb[o:o + len(lo)], ub[o:o + len(hi)] = lo, hi
     return cam_off, tf_off, x0, lb, ub
+
+
+def block_offsets(c):
+    """offset of every free-standing parameter block (case key "parameter_blocks") in the parameter vector"""
+    cam_off, tf_off, x0, _, _ = layout(c)
+    off = x0.size - sum(np.asarray(v).size for v, _ in c.get("parameter_blocks", ()))
+    out = []
+    for v, _ in c.get("parameter_blocks", ()):
+        out.append(off)
+        off += np.asarray(v).size
+    return out
 
 
 def oracle_rows(c, x, want_jac=True):

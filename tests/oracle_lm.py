@@ -21,6 +21,17 @@ A case is the dict of tests/golden_cases.py, with optional extensions:
   const_cameras   camera indices whose intrinsics are constant
   const_transforms  transform indices that are constant (global or sequence)
   const_poses     {transform index: [element indices]} constant pose elements (set_pose_constant)
+  priors          [(transform, stiffness[6], xi_prior[6])] TransformationPrior blocks (vg_problem_add_transformation_prior:
+                  xi_prior is the transform's initial value); on a sequence the block acts on element 0
+  odometry_priors [(transform, i, errV, errW, lam, xi1[6], xi2[6])] OdometryPrior blocks between elements i and i + 1
+  parameter_blocks  [(values, constant)] free-standing global parameter blocks, placed after the transforms, unbounded
+  odometry_costs  [(transform, i, errV, errW, lam, delta_q [n, 2], block)] OdometryCost blocks between elements i and i + 1
+                  and parameter block `block` (its initial values are the cost's intrinsics prior)
+A case with any of the last four keys is held to the FULL system (full_system, dense over all G + 6P columns): the grid rows
+as in arrow_system, the prior and odometry rows uncorrected (the library adds them without a loss), with the oracle's own
+Jacobians (vgo.transformation_prior, vgo.OdometryPrior, vgo.OdometryCost; not exact derivatives, so finite differences are
+the wrong reference).  A pose is free when it is not constant and some residual block touches it.  Cases without them keep
+the arrow path.
 """
 import os
 
@@ -78,7 +89,8 @@ def cost_floor(r, corners, soft_l1_scale=0.0):
 
 
 def cost(c, x, soft_l1_scale=0.0, threads=None, floor=False):
-    """sum over images of 1/2 rho(|r_b|^2) at x (plain 1/2 |r|^2 without a loss); floor: also its rounding floor"""
+    """sum over images of 1/2 rho(|r_b|^2) at x (plain 1/2 |r|^2 without a loss), plus 1/2 |r|^2 of the prior and odometry
+    blocks; floor: also its rounding floor"""
     cam_off, tf_off, _, _, _ = G.layout(c)
     x = np.asarray(x, float)
     total, fl = 0.0, 0.0
@@ -89,6 +101,9 @@ def cost(c, x, soft_l1_scale=0.0, threads=None, floor=False):
         total += float(np.sum(soft_l1(np.sum(r * r, axis=1), soft_l1_scale)[0])) if soft_l1_scale else float(np.sum(r * r))
         if floor:
             fl += cost_floor(r, np.asarray(c["datasets"][d][3], float).reshape(r.shape), soft_l1_scale)
+    if has_extras(c):      # prior and odometry blocks, without a loss
+        e, efl = extra_cost(c, x, floor=True)
+        return (0.5 * total + e, fl + efl) if floor else 0.5 * total + e
     return (0.5 * total, fl) if floor else 0.5 * total
 
 
@@ -104,7 +119,7 @@ def arrow_system(c, x, soft_l1_scale=0.0, threads=None):
     cam_off, tf_off, _, lb, ub = G.layout(c)
     const_cams = set(c.get("const_cameras", ()))
     const_tfs = set(c.get("const_transforms", ()))
-    gcols, frozen, cam_g, tf_g = [], [], [], {}
+    gcols, frozen, cam_g, tf_g, pb_g = [], [], [], {}, []
     for k, ((model, _), o) in enumerate(zip(c["cameras"], cam_off)):
         K = vgo.NUM_INTRINSICS[vgo.MODELS[model]]
         cam_g.append(np.arange(len(gcols), len(gcols) + K))
@@ -122,6 +137,11 @@ def arrow_system(c, x, soft_l1_scale=0.0, threads=None):
             pose_param += [tf_off[t] + 6 * i for i in range(m)]
             cp = set(c.get("const_poses", {}).get(t, ()))
             pose_const += [t in const_tfs or i in cp for i in range(m)]
+    for (vals, const), o in zip(c.get("parameter_blocks", ()), G.block_offsets(c)):
+        k = np.asarray(vals).size
+        pb_g.append(np.arange(len(gcols), len(gcols) + k))
+        gcols += list(range(o, o + k))
+        frozen += [bool(const)] * k
     gcols, pose_param = np.array(gcols, dtype=np.int64), np.array(pose_param, dtype=np.int64)
     Gn, P = gcols.size, pose_param.size
     U, gg = np.zeros((Gn, Gn)), np.zeros(Gn)
@@ -162,7 +182,224 @@ def arrow_system(c, x, soft_l1_scale=0.0, threads=None):
     seen = np.einsum("pii->p", V) > 0                            # poses without observations do not move
     return {"U": U, "gg": gg, "V": V, "W": W, "gp": gp, "cost": 0.5 * cost2, "gcols": gcols, "pose_param": pose_param,
             "frozen": np.array(frozen, dtype=bool), "pose_free": seen & ~np.array(pose_const, dtype=bool),
-            "lb": lb[gcols], "ub": ub[gcols], "x": x}
+            "lb": lb[gcols], "ub": ub[gcols], "x": x, "tf_g": tf_g, "pb_g": pb_g, "pose_base": pose_base,
+            "pose_const": np.array(pose_const, dtype=bool), "seen": seen}
+
+
+EXTRA_KEYS = ("priors", "odometry_priors", "parameter_blocks", "odometry_costs")
+
+
+def has_extras(c):
+    """does the case carry prior / odometry / parameter-block keys (-> the full system)"""
+    return any(c.get(k) for k in EXTRA_KEYS)
+
+
+def _pose_cols(sy, t, i):
+    Gn = sy["gcols"].size
+    p = sy["pose_base"][t] + i
+    return np.arange(Gn + 6 * p, Gn + 6 * p + 6), p
+
+
+def extra_blocks(c, x, sy):
+    """the prior and odometry residual blocks at x, from the oracle: [dict(kind, r [6], cols [system columns], J [6, cols],
+    poses [pose blocks touched])]; system columns: global column g -> g, element k of pose block p -> G + 6 p + k"""
+    from oracle import vgo
+
+    x = np.asarray(x, float)
+    _, tf_off, _, _, _ = G.layout(c)
+    out = []
+    for t, stiff, xi_prior in c.get("priors", ()):
+        if c["transforms"][t][0]:
+            cols, poses = sy["tf_g"][t], []
+        else:
+            cols, p = _pose_cols(sy, t, 0)
+            poses = [p]
+        r, J = vgo.transformation_prior(stiff, xi_prior, x[sy["x_cols"][cols]])
+        out.append({"kind": "prior", "r": r, "cols": cols, "J": J, "poses": poses})
+    for t, i, eV, eW, lam, xi1, xi2 in c.get("odometry_priors", ()):
+        c1, p1 = _pose_cols(sy, t, i)
+        c2, p2 = _pose_cols(sy, t, i + 1)
+        r, J1, J2 = vgo.OdometryPrior(eV, eW, lam, xi1, xi2).evaluate(x[sy["x_cols"][c1]], x[sy["x_cols"][c2]])
+        out.append({"kind": "odometry_prior", "r": r, "cols": np.concatenate([c1, c2]), "J": np.hstack([J1, J2]),
+                    "poses": [p1, p2]})
+    for t, i, eV, eW, lam, dq, b in c.get("odometry_costs", ()):
+        c1, p1 = _pose_cols(sy, t, i)
+        c2, p2 = _pose_cols(sy, t, i + 1)
+        c3 = sy["pb_g"][b]
+        blk = vgo.OdometryCost(eV, eW, lam, dq, np.asarray(c["parameter_blocks"][b][0], float))
+        r, J1, J2, J3 = blk.evaluate(x[sy["x_cols"][c1]], x[sy["x_cols"][c2]], x[sy["x_cols"][c3]])
+        out.append({"kind": "odometry_cost", "r": r, "cols": np.concatenate([c1, c2, c3]), "J": np.hstack([J1, J2, J3]),
+                    "poses": [p1, p2], "n_pose_cols": 12})
+    return out
+
+
+def _x_cols(sy):
+    """parameter index of every system column"""
+    return np.concatenate([sy["gcols"], (sy["pose_param"][:, None] + np.arange(6)[None, :]).ravel()])
+
+
+def extra_cost(c, x, floor=False):
+    """sum of 1/2 |r|^2 over the prior and odometry blocks (no loss); floor: also its rounding floor, 4 eps sum_k |r_k|
+    sum_j |J_kj| |x_j| (what rounding x, relative eps, moves the cost by)"""
+    if not has_extras(c):
+        return (0.0, 0.0) if floor else 0.0
+    x = np.asarray(x, float)
+    sy = _skeleton(c, x)
+    tot, fl = 0.0, 0.0
+    for b in extra_blocks(c, x, sy):
+        tot += float(b["r"] @ b["r"])
+        fl += 4.0 * np.finfo(float).eps * float(np.abs(b["r"]) @ (np.abs(b["J"]) @ np.abs(x[sy["x_cols"][b["cols"]]])))
+    return (0.5 * tot, fl) if floor else 0.5 * tot
+
+
+def _skeleton(c, x):
+    """the column bookkeeping of arrow_system without its rows"""
+    sy = arrow_system(dict(c, datasets=[]), x)
+    sy["x_cols"] = _x_cols(sy)
+    return sy
+
+
+def full_system(c, x, soft_l1_scale=0.0, threads=None):
+    """the damped step's system of a case with prior / odometry blocks, dense over all G + 6P columns (globals first, then
+    the pose blocks): H [n, n], g [n], the cost, the arrow system's bookkeeping (gcols, pose_param, frozen, pose_free, lb,
+    ub, gg, gp) and the pieces the planted errors of tests/test_oracle_lm.py take apart (diag_grid: diag H of the grid
+    rows alone; blocks: the extra residual blocks)"""
+    sy = arrow_system(c, x, soft_l1_scale, threads)
+    Gn, P = sy["gcols"].size, sy["pose_param"].size
+    n = Gn + 6 * P
+    H, g = np.zeros((n, n)), np.zeros(n)
+    H[:Gn, :Gn] = sy["U"]
+    g[:Gn] = sy["gg"]
+    Wf = np.transpose(sy["W"], (1, 0, 2)).reshape(Gn, 6 * P)
+    H[:Gn, Gn:], H[Gn:, :Gn] = Wf, Wf.T
+    for p in range(P):
+        H[Gn + 6 * p:Gn + 6 * p + 6, Gn + 6 * p:Gn + 6 * p + 6] = sy["V"][p]
+    g[Gn:] = sy["gp"].ravel()
+    diag_grid = np.diag(H).copy()
+    sy["x_cols"] = _x_cols(sy)
+    blocks = extra_blocks(c, x, sy)
+    touched = sy["seen"].copy()
+    cost2 = 2.0 * sy["cost"]
+    for b in blocks:
+        cols, J, r = b["cols"], b["J"], b["r"]
+        H[np.ix_(cols, cols)] += J.T @ J
+        g[cols] += J.T @ r
+        cost2 += float(r @ r)
+        touched[b["poses"]] = True
+    sy.update({"dense": True, "H": H, "g": g, "cost": 0.5 * cost2, "diag_grid": diag_grid, "blocks": blocks,
+               "pose_free": touched & ~sy["pose_const"], "gg": g[:Gn], "gp": g[Gn:].reshape(P, 6)})
+    return sy
+
+
+def system(c, x, soft_l1_scale=0.0, threads=None):
+    """the step's system: the full (dense) one for a case with prior / odometry blocks, else the arrow one"""
+    return full_system(c, x, soft_l1_scale, threads) if has_extras(c) else arrow_system(c, x, soft_l1_scale, threads)
+
+
+def _dense_free(sy, held):
+    return np.concatenate([~held, np.repeat(sy["pose_free"], 6)])
+
+
+def dense_step(sy, mu, opt=None, plant=None):
+    """(H + mu D) delta = -g on the full system, D = clamp(diag H) over the free columns, the active set of damped_step.
+    plant: deliberate errors for the tests of the step metric ("image_only_diag": pose damping clamped from the grid rows'
+    diagonal; {"drop_e": k}: the pose-pose coupling of odometry block k dropped; "drop_wodo": the pose-global coupling of
+    every OdometryCost block dropped; "prior_twice": every TransformationPrior block counted twice; {"keep_frozen": p}:
+    constant pose p eliminated as a unit block with its couplings kept).  -> the dict of damped_step"""
+    plant = plant or {}
+    o = dict(DEFAULTS, **(opt or {}))
+    H, g = sy["H"], sy["g"]
+    Gn, P = sy["gcols"].size, sy["pose_param"].size
+    if plant:
+        H, g = H.copy(), g.copy()
+    for k, b in enumerate(sy["blocks"]):
+        cols, J, r = b["cols"], b["J"], b["r"]
+        if b["kind"] == "prior" and "prior_twice" in plant:
+            H[np.ix_(cols, cols)] += J.T @ J
+            g[cols] += J.T @ r
+        if b["kind"] != "prior" and plant.get("drop_e") == k:
+            a, c2 = cols[:6], cols[6:12]
+            E = J[:, :6].T @ J[:, 6:12]
+            H[np.ix_(a, c2)] -= E
+            H[np.ix_(c2, a)] -= E.T
+        if b["kind"] == "odometry_cost" and "drop_wodo" in plant:
+            pc, gc = cols[:12], cols[12:]
+            Wo = J[:, :12].T @ J[:, 12:]
+            H[np.ix_(pc, gc)] -= Wo
+            H[np.ix_(gc, pc)] -= Wo.T
+    D = clamp_diag(np.diag(H), o)
+    if "image_only_diag" in plant:
+        D[Gn:] = clamp_diag(sy["diag_grid"][Gn:], o)
+    pose_free = sy["pose_free"].copy()
+    if "keep_frozen" in plant:
+        q = plant["keep_frozen"]
+        pose_free[q] = True
+        qc = np.arange(Gn + 6 * q, Gn + 6 * q + 6)
+        H[np.ix_(qc, qc)] = np.eye(6)
+        D[qc] = 0.0
+        g[qc] = 0.0
+    held = sy["frozen"].copy()
+    xg = sy["x"][sy["gcols"]]
+    for _ in range(Gn + 1):
+        f = np.concatenate([~held, np.repeat(pose_free, 6)])
+        A = H[np.ix_(f, f)]
+        if mu:
+            A = A + np.diag(mu * D[f])
+        d = np.zeros(H.shape[0])
+        if f.any():
+            d[f] = np.linalg.solve(A, -g[f])
+        dg = d[:Gn]
+        if not o["use_bounds"]:
+            break
+        out = ~held & (((xg <= sy["lb"]) & (dg < 0)) | ((xg >= sy["ub"]) & (dg > 0)))
+        if not out.any():
+            break
+        held |= out
+    dp = d[Gn:].reshape(P, 6).copy()
+    dp[~sy["pose_free"]] = 0.0
+    return {"dg": dg.copy(), "dp": dp, "held": held, "Dg": D[:Gn], "Dp": D[Gn:].reshape(P, 6)}
+
+
+def dense_backward_error(sy, mu, dg, dp, opt=None, x_next=None):
+    """backward_error on the full system: the same Jacobi-scaled, blockwise normwise value, where the rows of a pose block
+    touch every global column, its own columns and those of the poses it is coupled to (odometry neighbours)"""
+    o = dict(DEFAULTS, **(opt or {}))
+    held = damped_step(sy, mu, o)["held"]
+    Gn, P = sy["gcols"].size, sy["pose_param"].size
+    pf = sy["pose_free"]
+    f = _dense_free(sy, held)
+    H = sy["H"]
+    A = H + np.diag(mu * clamp_diag(np.diag(H), o))
+    d = np.concatenate([np.asarray(dg, float), np.asarray(dp, float).ravel()])
+    s = np.zeros(H.shape[0])
+    s[f] = 1.0 / np.sqrt(np.diag(A)[f])
+    As = A * s[:, None] * s[None, :]
+    gs, ds = sy["g"] * s, np.where(f, d / np.where(s > 0, s, 1.0), 0.0)
+    res = As @ ds + gs
+    eps = np.finfo(float).eps
+    e = None
+    if x_next is not None:
+        e = np.where(f, eps * np.abs(np.asarray(x_next, float)[sy["x_cols"]]) / np.where(s > 0, s, 1.0), 0.0)
+    gsel = np.zeros_like(f)
+    gsel[:Gn] = f[:Gn]
+
+    def block(rows, touch):
+        nd = np.linalg.norm(ds[touch])
+        v = np.linalg.norm(res[rows]) / (np.linalg.norm(As[np.ix_(rows, touch)]) * nd + np.linalg.norm(gs[rows]))
+        return v, (np.linalg.norm(e[touch]) / nd if e is not None else 0.0)
+
+    be_g, fl_g = block(gsel, f) if gsel.any() else (0.0, 0.0)
+    be_p, fl_p = np.zeros(P), np.zeros(P)
+    Hp = np.abs(H[Gn:, Gn:]).reshape(P, 6, P, 6).sum(axis=(1, 3)) > 0     # pose-pose coupling pattern
+    for p in np.nonzero(pf)[0]:
+        rows = np.arange(Gn + 6 * p, Gn + 6 * p + 6)
+        touch = gsel.copy()
+        for q in np.nonzero(Hp[p] & pf)[0]:
+            touch[Gn + 6 * q:Gn + 6 * q + 6] = True
+        be_p[p], fl_p[p] = block(rows, touch)
+    if x_next is None:
+        return float(be_g), be_p
+    return float(be_g), be_p, float(fl_g), fl_p
 
 
 def clamp_diag(d, opt=None):
@@ -175,7 +412,10 @@ def damped_step(sy, mu, opt=None, plant=None):
     mu = 0 without an option dict: D never enters (the Gauss-Newton step).  plant: deliberate errors for the tests of
     the step metric ({"mu_scale": s} the damping times s, "no_pose_damping", {"drop_w": i} pose i's coupling dropped,
     {"drop_rhs": i} pose i's term of the reduced right-hand side dropped).
-    -> dict(dg [G], dp [P, 6], held [G], Dg [G], Dp [P, 6])"""
+    -> dict(dg [G], dp [P, 6], held [G], Dg [G], Dp [P, 6])  (the full system of a case with prior / odometry blocks:
+    dense_step)"""
+    if sy.get("dense"):
+        return dense_step(sy, mu, opt, plant)
     plant = plant or {}
     o = dict(DEFAULTS, **(opt or {}))
     U, gg, V, W, gp = sy["U"], sy["gg"], sy["V"], sy["W"].copy(), sy["gp"]
@@ -243,7 +483,7 @@ def lm_step(c, x, radius, decrease_factor=2.0, opt=None, threads=None, sy=None):
     o = dict(DEFAULTS, **(opt or {}))
     a = o["soft_l1_scale"]
     if sy is None:
-        sy = arrow_system(c, x, a, threads)
+        sy = system(c, x, a, threads)
     mu = 1.0 / radius
     st = damped_step(sy, mu, o)
     mc = model_change(sy, st, mu)
@@ -292,7 +532,10 @@ def backward_error(sy, mu, dg, dp, opt=None, x_next=None):
     zero by construction; a caller checks that separately).
     x_next: the point the step was recovered from (delta = x_next - x): then also the rounding floor of every block,
     ||e_B|| / ||delta_B|| with e = eps |x_next| in the same scaling -- what the rounding of x alone can add to the value.
-    -> (global value, [P] per pose (0 for fixed poses)), and with x_next also (global floor, [P] floors)"""
+    -> (global value, [P] per pose (0 for fixed poses)), and with x_next also (global floor, [P] floors)
+    (the full system of a case with prior / odometry blocks: dense_backward_error)"""
+    if sy.get("dense"):
+        return dense_backward_error(sy, mu, dg, dp, opt, x_next)
     o = dict(DEFAULTS, **(opt or {}))
     held = damped_step(sy, mu, o)["held"]
     f, pf = ~held, sy["pose_free"]

@@ -18,15 +18,15 @@ The per-image pose refinement (refine_poses, vg_pose_lm.hpp) is held the same wa
 import numpy as np
 import pytest
 
-from tests import golden_cases as G
 from tests import lm_cases as C
+from tests import lm_check as K
 from tests import oracle_lm as L
 
 pytestmark = pytest.mark.gpu
 
-BAR, RHO_MARGIN = L.BAR, L.RHO_MARGIN   # backward error of a step above its rounding floor; margin of every decision
-COST_RTOL = 1e-12
-RADIUS_RTOL = 1e-8
+BAR, RHO_MARGIN = K.BAR, K.RHO_MARGIN   # backward error of a step above its rounding floor; margin of every decision
+COST_RTOL = K.COST_RTOL
+RADIUS_RTOL = K.RADIUS_RTOL
 
 # (route, case, initial radii, SoftLOne scale, hooks, kernel the sizes select); a route named *_rejected must meet a rejected
 # step, *_held a held column.  (The UCM case with radius 1e4 is left out: its second step is clipped by the bound, so
@@ -90,51 +90,15 @@ def report():
 
 
 def _check_chain(vg, route, c, R, a, hooks, kernel):
-    x0 = G.layout(c)[2]
-    opt = {"initial_trust_region_radius": R, "soft_l1_scale": a}
-    ref = L.lm_chain(c, x0, 3, opt)
-    for it in ref:   # every compared decision is far from the acceptance threshold
-        assert abs(it["rho"] - L.DEFAULTS["min_relative_decrease"]) > RHO_MARGIN, (route, R, it["rho"])
+    def route_ok(what, s):
+        assert expected_route(s["num_global_columns"], s["num_pose_blocks"], len(c["datasets"]), hooks) == kernel, \
+            (what, s["num_global_columns"], s["num_pose_blocks"])
+
     p = C.build_product_problem(vg, c)
-    worst = _WORST.setdefault(route, [0.0, 0.0, 0.0, 0.0])
     try:
-        x_prev, radius_prev = x0, R
-        for k in (1, 2, 3):
-            p.set_parameters(x0)
-            s = p.solve(max_num_iterations=k, initial_trust_region_radius=R, soft_l1_scale=a)
-            x = p.get_parameters()
-            r = ref[k - 1]
-            what = (route, R, k)
-            assert s["termination"] == "NO_CONVERGENCE", (what, s["message"])
-            assert expected_route(s["num_global_columns"], s["num_pose_blocks"], len(c["datasets"]), hooks) == kernel, \
-                (what, s["num_global_columns"], s["num_pose_blocks"])
-            assert s["num_successful_steps"] == r["n_success"], (what, s["num_successful_steps"], r["n_success"])
-            oc, fl = L.cost(c, x, a, floor=True)
-            dc = max(abs(s["final_cost"] - oc) - fl, 0.0) / oc    # beyond the cost's rounding floor (oracle_lm.cost_floor)
-            dr = abs(s["final_radius"] - r["radius"]) / r["radius"]
-            assert dc <= COST_RTOL, (what, s["final_cost"], oc)
-            assert dr <= RADIUS_RTOL, (what, s["final_radius"], r["radius"])
-            worst[2], worst[3] = max(worst[2], dc), max(worst[3], dr)
-            if not r["success"]:
-                assert np.array_equal(x, x_prev), what   # a rejected step (a discarded speculation) leaves no trace
-            else:
-                sy = L.arrow_system(c, x_prev, a)
-                mu = 1.0 / radius_prev
-                own = L.damped_step(sy, mu, opt)
-                dg, dp = L.split_step(sy, x)
-                # the reference's own step is not clipped by a bound: x_k - x_{k-1} is the step itself
-                xg = x_prev[sy["gcols"]] + own["dg"]
-                assert np.all((xg >= sy["lb"]) & (xg <= sy["ub"])), what
-                assert np.all(dg[own["held"]] == 0.0), (what, "held / frozen columns moved")
-                assert np.all(dp[~sy["pose_free"]] == 0.0), (what, "constant / unobserved poses moved")
-                # x_k - x_{k-1} carries the rounding of x_k: each block may exceed BAR by its rounding floor (oracle_lm.backward_error)
-                excess, be, floor = L.recovered_step_error(sy, mu, x, opt)
-                worst[0], worst[1] = max(worst[0], be), max(worst[1], floor)
-                assert excess <= BAR, (what, be, floor)
-            x_prev, radius_prev = x, s["final_radius"]
+        return K.check_chain(p, route, c, R, a, _WORST.setdefault(route, [0.0, 0.0, 0.0, 0.0]), route_ok)
     finally:
         p.close()
-    return ref
 
 
 @pytest.mark.parametrize("route,name,radii,a,hooks,kernel", ROUTES, ids=[r[0] for r in ROUTES])
