@@ -565,6 +565,46 @@ enum vg_pixel_type { VG_PIXEL_U8 = 0, VG_PIXEL_F32 = 1 };
 int vg_remap(int device, void *hip_stream, int pixel_type, int channels, int64_t n_images, int src_w, int src_h, const void *src,
              int map_w, int map_h, const float *map_x, const float *map_y, double fill, void *dst);
 
+/* =====================================================================================
+ * 8. Checkerboard corner detection: the reference's CornerDetector (include/calibration/corner_detector.h,
+ *    src/calibration/corner_detector.cpp) for batches of same-size 8-bit images.  The pixel and per-candidate stages run on the
+ *    GPU, the graph stages on at most 16 host threads (one image per task).  Images are DEVICE u8 [n][height][width], dense;
+ *    every side is in [16, 16384].  The calls are synchronous on the detector's stream.  Deviations: DESIGN.md section 9.
+ * ===================================================================================== */
+typedef struct vg_corner_detector vg_corner_detector;
+/* A detector for a board of cols x rows inner corners (object.cols / object.rows; cols, rows >= 2, cols x rows <= 400);
+ * improve = 1 adds the subpixel refinement (improveCorners).  hip_stream: a hipStream_t or NULL.  Allocates nothing on the
+ * device until the first call; then it keeps the scratch of one image size (a call with another size replaces it).
+ * Memory bound, whatever n_images is: the device scratch is at most max(1 GiB, the scratch of one image), about 21 bytes per
+ * pixel per image of a chunk of up to 64 images; the pinned host staging is 9 bytes per pixel of the same chunk.  Larger
+ * calls are worked through chunk by chunk. */
+int vg_corner_detector_create(vg_corner_detector **out, int device, void *hip_stream, int cols, int rows, int improve);
+void vg_corner_detector_destroy(vg_corner_detector *d);
+/* detectPattern (.cpp:223-260) of every image: the sigma retries {1.4, 2, 1} run batched over the images not found yet.
+ * HOST outputs: corners [n_images][cols x rows][2] FP64 (u, v) in the reference's order (row by row from the corner with the
+ * smallest u + v; zeros for an image not found), found [n_images] (1 / 0), sigma [n_images] (the sigma
+ * that found the board, 0 if none) or NULL. */
+int vg_corner_detect(vg_corner_detector *d, int64_t n_images, int width, int height, const uint8_t *images, double *corners,
+                     uint8_t *found, double *sigma);
+/* Stage entry: computeResponse(0.7, sigma) (.cpp:262-330) of n_images images at sigma 1.4, 2 or 1.  DEVICE outputs
+ * [n_images][height][width]: src1 / src2 (the two blurred u8 images), gradx / grady / imgrad (float, 0 on the one-pixel
+ * border) and resp (float, 0 where not kept); HOST avg [n_images] (_avgVal, NaN when no response is kept). */
+int vg_corner_response(vg_corner_detector *d, int64_t n_images, int width, int height, const uint8_t *images, double sigma,
+                       uint8_t *src1, uint8_t *src2, float *gradx, float *grady, float *imgrad, float *resp, double *avg);
+/* Stage entry: selectCandidates (.cpp:494-610) at sigma 1.4, 2 or 1.  HOST outputs: uv [n_images][max_out][2] the accepted
+ * candidates in descending response (ties: smaller v width + u first), count [n_images] how many were accepted (at most
+ * 10 cols rows), val_thresh [n_images] VAL_THRESH, n_maxima [n_images] the local maxima not below _avgVal. */
+int vg_corner_candidates(vg_corner_detector *d, int64_t n_images, int width, int height, const uint8_t *images, double sigma,
+                         int max_out, int32_t *uv, int32_t *count, double *val_thresh, int64_t *n_maxima);
+/* getCircle (.cpp:1079-1108) around (0, 0), radius in [1, 64]: the first max_points offsets to du / dv, their number to
+ * *n_points.  Host only (the tables the kernels use). */
+int vg_corner_circle(int radius, int max_points, int32_t *du, int32_t *dv, int *n_points);
+/* measurement: accumulated over the detector's detect calls: [0] GPU stages s, [1] device -> host copy s, [2] its bytes,
+ * [3] graph stage wall s, [4] images through it, [5] refinement s (upload, kernel, download), [6] refined corners, [7] calls */
+int vg_corner_detector_stats(const vg_corner_detector *d, double *stats8);
+/* the number of images one chunk of a detect call holds for this image size */
+int vg_corner_detector_chunk(const vg_corner_detector *d, int width, int height, int *chunk);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the A/B
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_force_mfma",
  * "gram_ch1", "gram_no_merge", "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop",

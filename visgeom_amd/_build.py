@@ -27,7 +27,8 @@ PRODUCTION_LIB = os.path.join(LIB_DIR, "production", "libvisgeom_amd.so")
 def sources():
     """the translation units of the library: every .hip file of csrc/ (vg_capi: problem assembly + emit; vg_gram_tu: normal
     equations; vg_solver_tu: LM / Schur + communicator; vg_refine_tu: per-image pose LM; vg_frontend_tu: calibration JSON;
-    vg_local_tu: localization costs; vg_rectify_tu: rectification maps and remap)"""
+    vg_local_tu: localization costs; vg_rectify_tu: rectification maps and remap;
+    vg_corners_tu: checkerboard corner detection)"""
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
 
 

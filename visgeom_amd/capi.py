@@ -181,6 +181,16 @@ SIGNATURES = {
     "vg_rectify_map": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _dp, _dp, _dp, _vp, _vp]),
     "vg_remap": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp,
                                 ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_double, _vp]),
+    "vg_corner_detector_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vg_corner_detector_destroy": (None, [_vp]),
+    "vg_corner_detect": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _dp, _vp, _dp]),
+    "vg_corner_response": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _dp]),
+    "vg_corner_candidates": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_double, ctypes.c_int,
+                                            _i32p, _i32p, _dp, _i64p]),
+    "vg_corner_circle": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i32p, _i32p, _ip]),
+    "vg_corner_detector_stats": (ctypes.c_int, [_vp, _dp]),
+    "vg_corner_detector_chunk": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _ip]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),

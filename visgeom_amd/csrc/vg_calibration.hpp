@@ -5,8 +5,9 @@
 // the solve) goes through the C ABI of this library to the GPU.  Included at the end of vg_capi.hip.
 //
 // Differences from the reference, all stated in DESIGN.md section 8:
-//   * "images" datasets need pre-extracted corners ("corners_file", same layout as ir_data's "data_file"): the
-//     corner detector (OpenCV) is out of scope.  "ir_data" is read exactly as the reference reads it.
+//   * "images" datasets read 8-bit PGM files (images.prefix / images.names) and find the board with this library's corner
+//     detector (section 8 of the C ABI), or take pre-extracted corners ("corners_file", same layout as
+//     ir_data's "data_file").  "ir_data" is read exactly as the reference reads it.
 //   * odometry_intrinsic (:660-742) is accepted with the parameter blocks the reference ADDS the cost with (xi_i, xi_i+1,
 //     [radius_left, radius_right, track_gauge]); the reference declares OdometryCost with a single block of 6 and its
 //     report indexes cameraMap with the transform's name (broken as shipped).  Here the wheel geometry lives in
@@ -25,6 +26,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <iterator>
 #include <map>
 #include <memory>
 #include <sstream>
@@ -104,7 +106,7 @@ struct ImageData {  // unified_calibration.h:46-87 (the fields the grid residual
     std::string cameraName;
     std::vector<std::string> transNameVec;
     std::vector<int> transStatusVec;
-    bool doNotSolve = false, doNotSolveGlobal = false;
+    bool doNotSolve = false, doNotSolveGlobal = false, improveDetection = false;
     std::vector<std::string> unknownFlags;
     std::vector<std::array<double, 3>> board;
     int Nx = 0, Ny = 0, idxUL = 0, idxUR = 0, idxBL = 0, idxBR = 0;
@@ -559,9 +561,10 @@ inline void init_chain_info(vg_calibration *c, ImageData &data, const vgjson::Va
         const std::string f = flag.as_string();
         if (f == "do_not_solve") data.doNotSolve = true;
         else if (f == "do_not_solve_global") data.doNotSolveGlobal = true;
-        else if (f == "check_extraction" || f == "improve_detection" || f == "show_outliers" || f == "user_guided" ||
-                 f == "save_outlire_images" || f == "draw_improved") {
-            // detector / GUI flags: nothing to do without images
+        else if (f == "improve_detection") data.improveDetection = true;   // :189, the detector's subpixel refinement
+        else if (f == "check_extraction" || f == "show_outliers" || f == "user_guided" || f == "save_outlire_images" ||
+                 f == "draw_improved") {
+            // GUI flags: ignored
         } else {
             c->log += "WARNING : UNKNOWN FLAG -- " + f + "\n";  // :200-203, tolerated
             data.unknownFlags.push_back(f);
@@ -692,6 +695,129 @@ inline void read_corners(vg_calibration *c, ImageData &data, const std::string &
     });
 }
 
+// binary 8-bit PGM ("P5", maxval <= 255, '#' comments in the header); false when the file is missing or not such a file (the
+// reference's imread(fileName, 0) returns an empty image for both)
+inline bool read_pgm(const std::string &path, int &w, int &h, std::vector<uint8_t> &px)
+{
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return false;
+    std::string data((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    size_t pos = 2;
+    auto number = [&](long long &v) {
+        while (pos < data.size()) {
+            if (data[pos] == '#') while (pos < data.size() && data[pos] != '\n') pos++;
+            else if (std::isspace((unsigned char)data[pos])) pos++;
+            else break;
+        }
+        v = 0;
+        int digits = 0;
+        while (pos < data.size() && std::isdigit((unsigned char)data[pos]) && digits < 9) v = v * 10 + (data[pos++] - '0'), digits++;
+        return digits > 0;
+    };
+    if (data.size() < 2 || data[0] != 'P' || data[1] != '5') return false;
+    long long W = 0, H = 0, maxval = 0;
+    if (!number(W) || !number(H) || !number(maxval)) return false;
+    if (W < 1 || H < 1 || W > 16384 || H > 16384 || maxval < 1 || maxval > 255) return false;
+    if (pos >= data.size() || !std::isspace((unsigned char)data[pos])) return false;
+    pos++;
+    if (data.size() - pos < (size_t)(W * H)) return false;
+    w = (int)W;
+    h = (int)H;
+    px.assign(data.begin() + (std::ptrdiff_t)pos, data.begin() + (std::ptrdiff_t)(pos + (size_t)(W * H)));
+    return true;
+}
+
+// initGrid :296-307 + extractGridProjections :993-1064: the board of every image file, found by this library's detector.
+// Images of one size are detected together, up to kDetectBatch at a time; the log lines are the reference's, in image order.
+inline void extract_grid_projections(vg_calibration *c, ImageData &data, const vgjson::Value &di, const std::string &base_dir)
+{
+    constexpr size_t kDetectBatch = 64;
+    std::string prefix = di.at("images.prefix").as_string();
+    if (!prefix.empty() && prefix[0] != '/') prefix = base_dir + prefix;
+    std::vector<std::string> names;
+    for (auto &x : di.at("images.names").arr) names.push_back(prefix + x.as_string());
+    std::string sequenceName;
+    for (auto &name : data.transNameVec)
+        if (!c->transformInfoMap[name].global) {
+            sequenceName = name;
+            break;
+        }
+    const bool initialized = c->transformInfoMap[sequenceName].initialized;
+    const std::vector<bool> initVec = c->sequenceInitMap[sequenceName];
+    const size_t n = names.size(), nb = data.board.size();
+    enum { kSkipped, kMissing, kNotFound, kFound };
+    std::vector<int> status(n, kNotFound);
+    data.detectedCornersVec.assign(n, std::vector<double>());
+    vg_corner_detector *det = nullptr;
+    if (int rc = vg_corner_detector_create(&det, c->device, nullptr, data.Nx, data.Ny, data.improveDetection ? 1 : 0))
+        throw Error{rc, vg_last_error()};
+    std::unique_ptr<vg_corner_detector, void (*)(vg_corner_detector *)> guard(det, vg_corner_detector_destroy);
+    uint8_t *dev = nullptr;
+    size_t dev_bytes = 0;
+    struct DevFree {
+        uint8_t **p;
+        ~DevFree() { if (*p) (void)hipFree(*p); }
+    } dev_free{&dev};
+    std::map<std::pair<int, int>, std::vector<std::pair<size_t, std::vector<uint8_t>>>> buckets;   // (w, h) -> (image, pixels)
+    auto flush = [&](const std::pair<int, int> &size) {
+        auto &b = buckets[size];
+        if (b.empty()) return;
+        const size_t plane = (size_t)size.first * size.second, k = b.size();
+        if (dev_bytes < k * plane) {
+            if (dev) (void)hipFree(dev);
+            dev = nullptr;
+            dev_bytes = 0;
+            if (hipMalloc(&dev, k * plane) != hipSuccess) {
+                (void)hipGetLastError();
+                throw Error{VG_ERR_ALLOC, "corner detection: device image buffer allocation failed"};
+            }
+            dev_bytes = k * plane;
+        }
+        for (size_t j = 0; j < k; j++)
+            if (hipMemcpy(dev + j * plane, b[j].second.data(), plane, hipMemcpyHostToDevice) != hipSuccess)
+                throw Error{VG_ERR_HIP, "corner detection: image upload failed"};
+        std::vector<double> corners(k * nb * 2);
+        std::vector<uint8_t> found(k);
+        if (int rc = vg_corner_detect(det, (int64_t)k, size.first, size.second, dev, corners.data(), found.data(), nullptr))
+            throw Error{rc, vg_last_error()};
+        for (size_t j = 0; j < k; j++) {
+            if (!found[j]) continue;
+            status[b[j].first] = kFound;
+            data.detectedCornersVec[b[j].first].assign(corners.begin() + j * nb * 2, corners.begin() + (j + 1) * nb * 2);
+        }
+        b.clear();
+    };
+    for (size_t i = 0; i < n; i++) {
+        if (initialized && (i >= initVec.size() || !initVec[i])) {
+            status[i] = kSkipped;
+            continue;
+        }
+        int w = 0, h = 0;
+        std::vector<uint8_t> px;
+        {
+            PhaseClock clk(c->timings.read_files_s);
+            if (!read_pgm(names[i], w, h, px)) {
+                status[i] = kMissing;
+                continue;
+            }
+        }
+        if (w < 16 || h < 16) continue;   // too small for the detector: not found
+        auto &b = buckets[{w, h}];
+        b.emplace_back(i, std::move(px));
+        if (b.size() == kDetectBatch) flush({w, h});
+    }
+    for (auto &kv : buckets) flush(kv.first);
+    size_t countSuccess = 0;
+    for (size_t i = 0; i < n; i++) {
+        c->log += names[i] + "\n";
+        if (status[i] == kSkipped) c->log += names[i] + " : ERROR, the pattern has not been found on the corresponding image\n";
+        else if (status[i] == kMissing) c->log += names[i] + " : ERROR, file not found\n";
+        else if (status[i] == kNotFound) c->log += names[i] + " : ERROR, pattern not found\n";
+        else countSuccess++;
+    }
+    c->log += "\nDETECTION RATE : " + std::to_string(countSuccess) + " of " + std::to_string(n) + " detected\n";
+}
+
 inline std::string dirname_of(const std::string &path)
 {
     const size_t s = path.find_last_of('/');
@@ -730,17 +856,22 @@ inline void parse_data(vg_calibration *c, const vgjson::Value &root, const std::
                 data.idxUR = data.Nx - 1;
                 data.idxBL = data.Nx * (data.Ny - 1);
                 data.idxBR = data.Nx * data.Ny - 1;
-                if (!di.has("corners_file"))
+                if (di.has("corners_file")) {
+                    file = di.at("corners_file").as_string();
+                } else if (di.has("images")) {
+                    extract_grid_projections(c, data, di, base_dir);
+                } else {
                     throw Error{VG_ERR_INVALID_ARGUMENT,
-                                "\"images\" datasets need pre-extracted corners (\"corners_file\"): the corner detector is out of scope"};
-                file = di.at("corners_file").as_string();
+                                "\"images\" datasets need image files (\"images.prefix\" / \"images.names\") or pre-extracted "
+                                "corners (\"corners_file\"); without either the corner detector is out of scope"};
+                }
             }
             const int nb = (int)data.board.size();
             for (int idx : {data.idxUL, data.idxUR, data.idxBL, data.idxBR})
                 if (idx < 0 || idx >= nb) throw Error{VG_ERR_INVALID_ARGUMENT, "board corner index out of range"};
             if (!file.empty() && file[0] != '/') file = base_dir + file;
-            read_corners(c, data, file, data.cameraName);
-            if (type == "images") {
+            if (!file.empty()) read_corners(c, data, file, data.cameraName);
+            if (type == "images" && di.has("corners_file")) {
                 // extractGridProjections :996-1023: when the chain's sequence has already been initialised through another
                 // dataset, an image whose counterpart there had no pattern is skipped here as well
                 std::string sequenceName;
