@@ -605,6 +605,63 @@ int vg_corner_detector_stats(const vg_corner_detector *d, double *stats8);
 /* the number of images one chunk of a detect call holds for this image size */
 int vg_corner_detector_chunk(const vg_corner_detector *d, int width, int height, int *chunk);
 
+/* =====================================================================================
+ * 9. Dense fisheye stereo: the reference's EnhancedSgm (src/reconstruction/eucm_sgm.cpp), semi-global matching along the
+ *    epipolar curves of two unrectified EUCM images, hypotheses = 1.  Images are DEVICE u8 [n][v_max][u_max], dense; depth
+ *    maps are [n][y_max][x_max].  The calls are synchronous on the handle's stream.  Deviations: DESIGN.md section 9.
+ * ===================================================================================== */
+typedef struct vg_stereo vg_stereo;
+/* ScaleParameters + StereoParameters + SgmParameters (scale_parameters.h, eucm_stereo.h:34-60, eucm_sgm.h:41-70).  equal_margins
+ * != 0 replaces x_max / y_max by (u_max - 2 u0) / scale + 1 and (v_max - 2 v0) / scale + 1.  epipole_margin is the SQUARED
+ * pixel distance (the JSON key holds the distance).  verbosity is ignored; hypotheses must be 1. */
+typedef struct vg_stereo_params {
+    int scale, u0, v0, u_max, v_max, x_max, y_max, equal_margins;
+    int num_epipolar_planes, epipole_margin;
+    int disp_max, error_max, verbosity, hypotheses, hypo_difference, flaw_cost, desc_length, desc_resp_thresh;
+    int n_scales, scales[8];
+    int step_cost, jump_cost, image_based_cost, salient_points_only, use_uv_cache;
+} vg_stereo_params;
+/* the reference's defaults (scale 1, no margins, 1 x 1 image, disparity_max 48, error_max 25, epipole margin 50 px, flaw_cost 7,
+ * descriptor_size 5, scales {1, 2, 3, 5}, descriptor_response_thresh 5, 2000 planes, step_cost 5, jump_cost 32, image based cost,
+ * salient points only, uv cache) */
+void vg_stereo_params_default(vg_stereo_params *p);
+/* A handle for one calibrated EUCM pair: eucm1 / eucm2 the 6 intrinsics, xi12 the pose of camera 2 in camera 1 ([t, rotvec],
+ * the reference's stereo_transformation), all HOST.  Checks every argument before touching HIP: disp_max even in [4, 256],
+ * desc_length odd in [3, 31], 1 to 8 scales each in [1, 16], u_max / v_max in [1, 16384], x_max, y_max in [1, 16384],
+ * num_epipolar_planes even in [2, 2^20], |t| > 1e-5, hypotheses 1; a camera neither of whose epipoles projects is refused.
+ * Builds the curve tables on the host in FP64 and the per-pixel geometry on the GPU (32 bytes per depth pixel).  hip_stream
+ * (a hipStream_t or NULL) is fixed for the handle's life: every later call runs on it, and the caller orders the work that
+ * produces the images before the call. */
+int vg_stereo_create(vg_stereo **out, int device, void *hip_stream, const double *eucm1, const double *eucm2, const double *xi12,
+                     const vg_stereo_params *params);
+void vg_stereo_destroy(vg_stereo *s);
+/* the depth map size of the handle */
+int vg_stereo_size(const vg_stereo *s, int *x_max, int *y_max);
+/* EnhancedSgm::computeStereo (eucm_sgm.cpp:140-152) + DepthMap::at / sigma / cost of n_pairs pairs sharing the geometry.
+ * DEVICE outputs [n][y_max][x_max], each may be NULL: depth (FP64 range along camera 1's ray, 0 = none), sigma, cost (the
+ * matching error at disparity 0, as the reference reports it) and disparity (int32, -1 = none).  Device scratch: at most
+ * max(2 GiB, one pair's) of 5 disp_max + 7 bytes per depth pixel per pair; larger batches are worked through in chunks. */
+int vg_stereo_compute(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const uint8_t *img2, double *depth, double *sigma,
+                      double *cost, int32_t *disparity);
+/* the number of pairs one chunk of vg_stereo_compute holds */
+int vg_stereo_chunk(const vg_stereo *s, int64_t *pairs);
+/* Stage entry: the per-pixel geometry, DEVICE int32 [y_max][x_max][8]: status (1 camera 1 reconstructs the pixel, 2 its
+ * point at infinity projects into camera 2), round(pinf) u, v, the curve index, chooseEpipole flags of camera 1 and 2
+ * (1 inverted, 2 too close), 0, 0. */
+int vg_stereo_geometry(vg_stereo *s, int32_t *geometry);
+/* Stage entry: computeCurveCost of n pairs, DEVICE outputs: err u8 [n][y][x][disp_max], step u8 [n][y][x] (the descriptor
+ * step, 0 where none was set), salient u8, skip u8.  The stage entries are for tests and measurement: unlike vg_stereo_compute
+ * they run all n pairs in one launch per kernel, without chunking.  This one needs no scratch. */
+int vg_stereo_curve_cost(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const uint8_t *img2, uint8_t *err, uint8_t *step,
+                         uint8_t *salient, uint8_t *skip);
+/* Stage entry: the sum of the four directional tableaux (computeDynamicProgramming), DEVICE int32 [n][y][x][disp_max], and
+ * the winner, DEVICE int32 [n][y][x] (NULL allowed).  Not chunked; its device scratch is disp_max + 3 bytes per depth pixel
+ * per pair (the error volume, step / salient / skip), 4 more when disparity is NULL. */
+int vg_stereo_aggregate(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const uint8_t *img2, int32_t *total, int32_t *disparity);
+/* Host only: CurveRasterizer<int, Polynomial2>(u, v, eu, ev, poly6) after setStep(step_mult), then `steps` steps (negative:
+ * unsteps), one at a time, |steps| <= 1000: uv [|steps| + 1][2] receives the start and every position. */
+int vg_stereo_curve_walk(const double *poly6, int u, int v, int eu, int ev, int step_mult, int steps, int32_t *uv);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the A/B
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_force_mfma",
  * "gram_ch1", "gram_no_merge", "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop",

@@ -191,12 +191,33 @@ SIGNATURES = {
     "vg_corner_circle": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i32p, _i32p, _ip]),
     "vg_corner_detector_stats": (ctypes.c_int, [_vp, _dp]),
     "vg_corner_detector_chunk": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _ip]),
+    "vg_stereo_params_default": (None, [_vp]),
+    "vg_stereo_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, _dp, _dp, _dp, _vp]),
+    "vg_stereo_destroy": (None, [_vp]),
+    "vg_stereo_size": (ctypes.c_int, [_vp, _ip, _ip]),
+    "vg_stereo_chunk": (ctypes.c_int, [_vp, _i64p]),
+    "vg_stereo_compute": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vg_stereo_geometry": (ctypes.c_int, [_vp, _vp]),
+    "vg_stereo_curve_cost": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vg_stereo_aggregate": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "vg_stereo_curve_walk": (ctypes.c_int, [_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            _i32p]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),
     "vg_calib_d2h_copies": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, _dp]),
     "vg_calib_fp64_fma": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
 }
+
+
+class StereoParams(ctypes.Structure):
+    """struct vg_stereo_params"""
+    _fields_ = [(n, ctypes.c_int) for n in ("scale", "u0", "v0", "u_max", "v_max", "x_max", "y_max", "equal_margins",
+                                            "num_epipolar_planes", "epipole_margin", "disp_max", "error_max", "verbosity",
+                                            "hypotheses", "hypo_difference", "flaw_cost", "desc_length", "desc_resp_thresh",
+                                            "n_scales")] + \
+               [("scales", ctypes.c_int * 8)] + \
+               [(n, ctypes.c_int) for n in ("step_cost", "jump_cost", "image_based_cost", "salient_points_only", "use_uv_cache")]
 
 
 class VisgeomError(RuntimeError):

@@ -1,0 +1,721 @@
+// vg_stereo.hpp -- dense fisheye stereo: the reference's EnhancedSgm (src/reconstruction/eucm_sgm.cpp), semi-global
+// matching along the epipolar curves of two unrectified EUCM images.  The FP64 pieces the host and the kernels share
+// (EUCM reconstruct / project, the epipolar-curve rasteriser, the curve index, the triangulation) and the four kernels:
+// per-pixel geometry, curve cost, directional aggregation (left+right, top+bottom with the winner) and depth.  The entries
+// are in vg_stereo_tu.hip.  Everything is evaluated in the order written (the library is built with -ffp-contract=off), so
+// the host walk, the kernels and tests/stereo_ref.py agree bit for bit.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+namespace vgs {
+
+#define VGS_HD __host__ __device__ __forceinline__
+
+enum : int { kEpipoleInverted = 1, kEpipoleTooClose = 2 };      // EpipoleResult (epipoles.h:33)
+enum : int { kGeomMask = 1, kGeomPinf = 2 };                    // status bits of a geometry entry
+constexpr int kDisparityMargin = 20;                            // DISPARITY_MARGIN (eucm_sgm.h:162)
+constexpr int kMaxDesc = 31, kMaxHalf = 15, kMaxScales = 8;
+constexpr int kMoveLimit = 1 << 20;                             // largest single rasteriser move (see rnd_move)
+constexpr int kInf = 1 << 28;                                   // "no path" in the descriptor DP; kInf + cost stays < 2^31
+constexpr double kTriangulateDistMax = 100.;                    // TRIANGULATE_DIST_MAX (eucm_stereo.cpp:250)
+constexpr double kTriEps = 1e-3;                                // Triangulator(1e-3)
+
+// one depth pixel's geometry, written once per handle
+struct GeomEntry {
+    int status;        // kGeomMask: camera 1 reconstructs the pixel; kGeomPinf: its point at infinity projects into camera 2
+    int pinf_u, pinf_v;  // round(pinf)
+    int index;         // EnhancedEpipolar::index of the reconstructed ray
+    int flags1, flags2;  // chooseEpipole for camera 1 at the pixel, for camera 2 at pinf
+    int pad0, pad1;
+};
+
+struct Poly2 {
+    double kuu, kuv, kvv, ku, kv, k1;
+};
+
+VGS_HD double poly_val(const Poly2 &s, int u, int v)
+{
+    return (s.kuu * u + s.kuv * v + s.ku) * u + (s.kvv * v + s.kv) * v + s.k1;
+}
+VGS_HD double poly_gu(const Poly2 &s, int u, int v) { return 2 * s.kuu * u + s.kuv * v + s.ku; }
+VGS_HD double poly_gv(const Poly2 &s, int u, int v) { return s.kuv * u + 2 * s.kvv * v + s.kv; }
+
+VGS_HD int sgn(double x) { return 2 * int(x > 0) - 1; }   // sign (std.h:74): sign(0) = -1
+
+// -round(x) as the int a move takes.  The reference converts without a bound (undefined past INT_MAX, e.g. 0/0 where both
+// gradients vanish); here NaN moves 0 and the move is clamped to +-2^20, so every walk stays far inside int range.
+VGS_HD int rnd_move(double x)
+{
+    double r = round(x);
+    if (!(r == r)) return 0;
+    r = r < -kMoveLimit ? -kMoveLimit : (r > kMoveLimit ? kMoveLimit : r);
+    return -(int)r;
+}
+
+// CurveRasterizer<int, Polynomial2> (curve_rasterizer.h, the second definition)
+struct Raster {
+    double delta, fu, fv;
+    int eps, u, v;
+    Poly2 surf;
+
+    VGS_HD void init(int u_, int v_, int eu, int ev, const Poly2 &s)
+    {
+        u = u_;
+        v = v_;
+        surf = s;
+        fu = poly_gu(surf, u, v);
+        fv = poly_gv(surf, u, v);
+        delta = poly_val(surf, u, v);
+        eps = (fu * (ev - v) - fv * (eu - u) > 0) ? 1 : -1;
+    }
+    VGS_HD void move_u(int du)
+    {
+        if (du == 0) return;
+        u += du;
+        const double fu2 = poly_gu(surf, u, v);
+        delta += 0.5 * du * (fu + fu2);
+        fu = fu2;
+        fv = poly_gv(surf, u, v);
+    }
+    VGS_HD void move_v(int dv)
+    {
+        if (dv == 0) return;
+        v += dv;
+        const double fv2 = poly_gv(surf, u, v);
+        delta += 0.5 * dv * (fv + fv2);
+        fv = fv2;
+        fu = poly_gu(surf, u, v);
+    }
+    VGS_HD void step()
+    {
+        if (fabs(fu) > fabs(fv)) {
+            move_v(eps * sgn(fu));
+            move_u(rnd_move(delta / fu));
+        } else {
+            move_u(-eps * sgn(fv));
+            move_v(rnd_move(delta / fv));
+        }
+    }
+    VGS_HD void unstep()
+    {
+        if (fabs(fu) > fabs(fv)) {
+            move_v(-eps * sgn(fu));
+            move_u(rnd_move(delta / fu));
+        } else {
+            move_u(eps * sgn(fv));
+            move_v(rnd_move(delta / fv));
+        }
+    }
+    VGS_HD void steps(int n)
+    {
+        if (n > 0)
+            for (int i = 0; i < n; i++) step();
+        else
+            for (int i = 0; i > n; i--) unstep();
+    }
+};
+
+// EnhancedCamera::reconstructPoint (eucm.h:85-104)
+VGS_HD bool eucm_reconstruct(const double *p, double u, double v, double *X)
+{
+    const double alpha = p[0], beta = p[1], fu = p[2], fv = p[3], u0 = p[4], v0 = p[5];
+    const double xn = (u - u0) / fu;
+    const double yn = (v - v0) / fv;
+    const double u2 = xn * xn + yn * yn;
+    const double gamma = 1. - alpha;
+    const double num = 1. - u2 * alpha * alpha * beta;
+    const double det = 1 - (alpha - gamma) * beta * u2;
+    if (det < 0) return false;
+    const double denom = gamma + alpha * sqrt(det);
+    X[0] = xn;
+    X[1] = yn;
+    X[2] = num / denom;
+    return true;
+}
+
+// EnhancedProjector (eucm.h:30-63)
+VGS_HD bool eucm_project(const double *p, const double *X, double *uv)
+{
+    const double alpha = p[0], beta = p[1], fu = p[2], fv = p[3], u0 = p[4], v0 = p[5];
+    const double x = X[0], y = X[1], z = X[2];
+    const double denom = alpha * sqrt(z * z + beta * (x * x + y * y)) + (1. - alpha) * z;
+    if (denom < 1e-3) return false;
+    if (alpha > 0.5) {
+        const double zn = z / denom;
+        const double C = (alpha - 1.) / (alpha + alpha - 1.);
+        if (zn < C) return false;
+    }
+    uv[0] = fu * (x / denom) + u0;
+    uv[1] = fv * (y / denom) + v0;
+    return true;
+}
+
+VGS_HD double dot3(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+VGS_HD void mat_vec(const double *M, const double *x, double *y)   // y = M x, M row-major
+{
+    for (int i = 0; i < 3; i++) y[i] = M[3 * i] * x[0] + M[3 * i + 1] * x[1] + M[3 * i + 2] * x[2];
+}
+VGS_HD int round_int(double x) { return (int)round(x); }
+
+// Triangulator::regDiv (triangulator.cpp:114-129)
+VGS_HD double reg_div(double num, double denom)
+{
+    if (denom > kTriEps * num) return num / denom;
+    if (num == 0) return 2. / kTriEps;
+    return 2. / kTriEps - denom / (num * kTriEps * kTriEps);
+}
+
+// Triangulator::computeRegular, the first root only (triangulator.cpp:145-175); R, t: Transf T12 (rotMat, trans)
+VGS_HD double triangulate_lambda(const double *R, const double *t, const double *p, const double *q0)
+{
+    double q[3], r[3];
+    mat_vec(R, q0, q);
+    for (int i = 0; i < 3; i++) r[i] = p[i] + q[i];
+    const double tp = dot3(t, p), tq = dot3(t, q), tr = dot3(t, r), tt = dot3(t, t);
+    const double rp = dot3(r, p), rq = dot3(r, q);
+    const double delta = tp * rq - tq * rp;
+    const double delta1 = tt * rq - tr * tq;
+    return reg_div(delta1, delta);
+}
+
+// everything the kernels read about one handle (host-built, passed by value)
+struct StereoGeom {
+    double c1[6], c2[6];
+    double R[9], Rinv[9], t[3];       // Transf T12: rotMat, rotMatInv, trans
+    double xBase[3], yBase[3];
+    double plane_step;                // 4 / num_epipolar_planes
+    int n_planes;
+    int epi_px[2][2][2];              // [camera][0 epipole, 1 anti-epipole][u, v]
+    int epi_ok[2][2];                 // projected?
+    const Poly2 *table;               // DEVICE [2][n_planes + 1]
+    int scale, u0, v0, u_max, v_max, x_max, y_max;
+    int epipole_margin;               // squared
+    int disp_max, error_max, flaw_cost, desc_length, n_scales, scales[kMaxScales], desc_resp_thresh;
+    int step_cost, jump_cost, image_based_cost, salient_points_only, use_uv_cache;
+};
+
+// EnhancedEpipolar::index (eucm_epipolar.cpp:110-127)
+VGS_HD int curve_index(const StereoGeom &g, const double *X)
+{
+    const double c = dot3(X, g.xBase), ac = fabs(c);
+    const double s = dot3(X, g.yBase), as = fabs(s);
+    if (ac + as < 1e-4) return 0;
+    const int i = ac > as ? round_int((s / c + 1) / g.plane_step) : round_int((1 - c / s) / g.plane_step) + g.n_planes / 2;
+    return i < 0 ? 0 : (i > g.n_planes ? g.n_planes : i);   // in range already; the clamp only guards the table read
+}
+
+// StereoEpipoles::chooseEpipole (epipoles.cpp:59-93); squared distances in double (the reference's int squaredNorm can
+// overflow for an epipole near the +-1e6 limit).  Neither epipole projected is refused by vg_stereo_create.
+VGS_HD int choose_epipole(const StereoGeom &g, int cam, int u, int v)
+{
+    int res = 0;
+    const double du = (double)u - g.epi_px[cam][0][0], dv = (double)v - g.epi_px[cam][0][1];
+    const double au = (double)u - g.epi_px[cam][1][0], av = (double)v - g.epi_px[cam][1][1];
+    const double dist = du * du + dv * dv, anti = au * au + av * av;
+    const double th = g.epipole_margin;
+    if (g.epi_ok[cam][0] && g.epi_ok[cam][1]) {
+        if (anti < dist) {
+            res |= kEpipoleInverted;
+            if (anti < th) res |= kEpipoleTooClose;
+        } else if (dist < th) res |= kEpipoleTooClose;
+    } else if (g.epi_ok[cam][0]) {
+        if (dist < th) res |= kEpipoleTooClose;
+    } else {
+        res |= kEpipoleInverted;
+        if (anti < th) res |= kEpipoleTooClose;
+    }
+    return res;
+}
+
+// EnhancedSgm::getCurveRasteriser (eucm_sgm.cpp:33-46)
+VGS_HD void make_raster(const StereoGeom &g, int cam, int u, int v, int index, int flags, Raster &r)
+{
+    const int inv = (flags & kEpipoleInverted) ? 1 : 0;
+    r.init(u, v, g.epi_px[cam][inv][0], g.epi_px[cam][inv][1], g.table[cam * (g.n_planes + 1) + index]);
+    if (inv) r.eps *= -1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// kernels
+
+// computeReconstructed / computeRotated / computePinf and the curve index + epipole choice: one lane per depth pixel
+__global__ __launch_bounds__(256) void stereo_geometry_kernel(StereoGeom g, GeomEntry *out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t P = (int64_t)g.x_max * g.y_max;
+    if (i >= P) return;
+    const int x = (int)(i % g.x_max), y = (int)(i / g.x_max);
+    const int u = x * g.scale + g.u0, v = y * g.scale + g.v0;
+    GeomEntry e = {0, 0, 0, 0, 0, 0, 0, 0};
+    double X[3], Xr[3], pinf[2];
+    if (eucm_reconstruct(g.c1, (double)u, (double)v, X)) {
+        e.status = kGeomMask;
+        e.index = curve_index(g, X);
+        e.flags1 = choose_epipole(g, 0, u, v);
+        mat_vec(g.Rinv, X, Xr);
+        if (eucm_project(g.c2, Xr, pinf)) {
+            e.status |= kGeomPinf;
+            e.pinf_u = round_int(pinf[0]);
+            e.pinf_v = round_int(pinf[1]);
+            e.flags2 = choose_epipole(g, 1, e.pinf_u, e.pinf_v);
+        }
+    }
+    out[i] = e;
+}
+
+// the unit-step walk of camera 2 for the uv cache: state k is kDisparityMargin unsteps back from pinf, then k steps
+// (k < 0: further unsteps -- DESIGN.md section 9, deviation 3).  Positions outside the image read as (-1, -1).
+struct CacheWalk {
+    Raster r;
+    int k;
+    VGS_HD void start(const StereoGeom &g, const GeomEntry &e)
+    {
+        make_raster(g, 1, e.pinf_u, e.pinf_v, e.index, e.flags2, r);
+        r.steps(-kDisparityMargin);
+        k = 0;
+    }
+    VGS_HD void go(int k_to)
+    {
+        r.steps(k_to - k);   // only ever forward after the first call with k_to < 0
+        k = k_to;
+    }
+};
+
+VGS_HD bool inside(const StereoGeom &g, int u, int v) { return !(v < 0 || v >= g.v_max || u < 0 || u >= g.u_max); }
+
+VGS_HD int compute_error(int v, int th)   // computeError (eucm_stereo.cpp:73-76); th = thMin | thMax << 8
+{
+    const int lo = th & 255, hi = th >> 8;
+    const int a = lo - v, b = v - hi;
+    return 0 > (a > b ? a : b) ? 0 : (a > b ? a : b);
+}
+
+VGS_HD int imin(int a, int b) { return a < b ? a : b; }
+
+struct CurveCostArgs {
+    const uint8_t *img1, *img2;    // [n][v_max][u_max]
+    const GeomEntry *geom;         // [P]
+    uint8_t *err;                  // [n][P][disp_max]
+    uint8_t *step, *salient, *skip;   // [n][P]
+    int64_t n_pairs;
+};
+
+constexpr int kCostLanes = 256;
+constexpr int kRing = 32;   // > 2 HALF_LENGTH: the lag of the second half of compareDescriptor
+
+// writes the skipPixel pattern (eucm_sgm.cpp:220-226)
+__device__ __forceinline__ void skip_pixel(uint8_t *e, int D, uint8_t *skip)
+{
+    e[0] = 0;
+    for (int d = 1; d < D; d++) e[d] = 255;
+    *skip = 1;
+}
+
+// computeCurveCost (eucm_sgm.cpp:228-393) with EpipolarDescriptor::compute, compareDescriptor and fillGaps: one lane per
+// (pair, depth pixel).  compareDescriptor's two row DPs run as one stream over the samples: the first half (descriptor rows 0
+// .. H, columns left to right) keeps two columns of history per row; the second half (rows L-1 .. H+1, whose recurrence looks
+// two columns to the right) runs row k lagged by 2k columns, so after 2H columns the final cost of column j is known.  The
+// samples and the first-half results of the last 32 columns live in an LDS ring; the thresholds of the descriptor in LDS.
+__global__ __launch_bounds__(kCostLanes) void stereo_curve_cost_kernel(StereoGeom g, CurveCostArgs a)
+{
+    __shared__ int ring[kRing][kCostLanes];         // (V_H[j] << 8) | sample[j] at slot j % 32
+    __shared__ uint16_t thr[kMaxDesc][kCostLanes];   // thMin | thMax << 8
+    __shared__ uint8_t desc[kMaxDesc][kCostLanes];
+    const int lane = threadIdx.x;
+    const int64_t P = (int64_t)g.x_max * g.y_max;
+    const int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gi >= P * a.n_pairs) return;
+    const int64_t pair = gi / P, pix = gi % P;
+    const int D = g.disp_max, L = g.desc_length, H = L / 2, f = g.flaw_cost;
+    uint8_t *e = a.err + gi * D;
+    uint8_t *skipp = a.skip + gi;
+    a.step[gi] = 0;
+    a.salient[gi] = 0;
+    *skipp = 0;
+    const GeomEntry ge = a.geom[pix];
+    if (!(ge.status & kGeomMask) || !(ge.status & kGeomPinf) || (ge.flags1 & kEpipoleTooClose)) {
+        skip_pixel(e, D, skipp);
+        return;
+    }
+    const int x = (int)(pix % g.x_max), y = (int)(pix / g.x_max);
+    const uint8_t *im1 = a.img1 + pair * (int64_t)g.u_max * g.v_max;
+    const uint8_t *im2 = a.img2 + pair * (int64_t)g.u_max * g.v_max;
+
+    // EpipolarDescriptor::compute
+    Raster ref;
+    make_raster(g, 0, x * g.scale + g.u0, y * g.scale + g.v0, ge.index, ge.flags1, ref);
+    int step = -1, resp = 0;
+    const int wave_thresh = g.desc_resp_thresh * L;
+    for (int si = 0; si < g.n_scales; si++) {
+        const int sc = g.scales[si];
+        Raster r = ref;
+        r.eps *= -sc;
+        r.steps(-H);
+        bool border = false;
+        for (int i = 0; i < L; i++, r.step()) {
+            if (!inside(g, r.u, r.v)) {
+                border = true;
+                break;
+            }
+            desc[i][lane] = im1[(int64_t)r.v * g.u_max + r.u];
+        }
+        if (border) {
+            step = -1;
+            break;
+        }
+        int tv = 0;
+        for (int i = 1; i < L; i++) tv += abs((int)desc[i - 1][lane] - (int)desc[i][lane]);
+        resp = (tv * 100) / ((int)desc[H][lane] + 30);
+        step = sc;
+        if (abs(resp) > wave_thresh) break;
+    }
+    if (step < 1) {
+        skip_pixel(e, D, skipp);
+        return;
+    }
+    a.step[gi] = (uint8_t)step;
+    if (g.salient_points_only && step < 2 && abs(resp) > wave_thresh) a.salient[gi] = 1;
+
+    // thresholds (compareDescriptor, eucm_stereo.cpp:81-113)
+    for (int i = 0; i < L; i++) {
+        const int di = desc[i][lane];
+        int lo, hi;
+        if (i == 0 || i == L - 1) {
+            const int dn = desc[i == 0 ? 1 : L - 2][lane];
+            const int m = (di + dn) / 2;
+            if (di > dn) {
+                lo = m;
+                hi = di;
+            } else {
+                hi = m;
+                lo = di;
+            }
+        } else {
+            const int d1 = (di + desc[i - 1][lane]) / 2, d2 = (di + desc[i + 1][lane]) / 2;
+            lo = imin(di, imin(d1, d2));
+            hi = di > d1 ? (di > d2 ? di : d2) : (d1 > d2 ? d1 : d2);
+        }
+        thr[i][lane] = (uint16_t)(lo | hi << 8);
+    }
+
+    // the sample walk of camera 2
+    const int nSteps = (D + step - 1) / step;
+    const int N = nSteps + L - 1;
+    CacheWalk cw;
+    Raster r2;
+    if (g.use_uv_cache) {
+        cw.start(g, ge);
+        cw.go(kDisparityMargin - H * step);
+    } else {
+        make_raster(g, 1, ge.pinf_u, ge.pinf_v, ge.index, ge.flags2, r2);
+        r2.eps *= step;
+        r2.steps(-H);
+    }
+
+    int v1[kMaxHalf], v2[kMaxHalf];           // first half: rows 0 .. H-1, columns t-1 and t-2
+    int w0[kMaxHalf], w1[kMaxHalf], w2[kMaxHalf];   // second half, level k = row L-1-k: its last three columns
+#pragma unroll
+    for (int i = 0; i < kMaxHalf; i++) {
+        v1[i] = v2[i] = kInf;
+        w0[i] = w1[i] = w2[i] = kInf;
+    }
+    int prev = 0;
+    const int t_end = nSteps + 3 * H;   // column j = t - 2H is final at time t; j runs to H + nSteps - 1
+    for (int t = 0; t < t_end; t++) {
+        int s = 0;
+        if (t < N) {
+            int su, sv;
+            if (g.use_uv_cache) {
+                if (t > 0) cw.go(cw.k + step);
+                su = cw.r.u;
+                sv = cw.r.v;
+            } else {
+                if (t > 0) r2.step();
+                su = r2.u;
+                sv = r2.v;
+            }
+            if (!inside(g, su, sv)) {
+                skip_pixel(e, D, skipp);
+                return;
+            }
+            s = im2[(int64_t)sv * g.u_max + su];
+            // first half, column t
+            int cur = compute_error(s, thr[0][lane]);
+#pragma unroll
+            for (int i = 1; i <= kMaxHalf; i++) {
+                if (i <= H) {
+                    const int nv = imin(cur + f, imin(v1[i - 1], v2[i - 1] + f)) + compute_error(s, thr[i][lane]);
+                    v2[i - 1] = v1[i - 1];
+                    v1[i - 1] = cur;
+                    cur = nv;
+                }
+            }
+            ring[t % kRing][lane] = cur << 8 | s;
+        }
+        // second half: level k at column t - 2k
+#pragma unroll
+        for (int k = 0; k < kMaxHalf; k++) {
+            if (k < H) {
+                const int c = t - 2 * k;
+                int val = kInf;
+                if (c >= 0 && c < N) {
+                    const int sc = ring[c % kRing][lane] & 255;
+                    const int ev = compute_error(sc, thr[L - 1 - k][lane]);
+                    if (k == 0) val = ev;
+                    else val = imin(w2[k - 1] + f, imin(w1[k - 1], w0[k - 1] + f)) + ev;
+                }
+                w2[k] = w1[k];
+                w1[k] = w0[k];
+                w0[k] = val;
+            }
+        }
+        const int j = t - 2 * H;
+        if (j >= H) {
+            int fw2 = kInf, fw1 = kInf, fw0 = kInf;
+#pragma unroll
+            for (int k = 0; k < kMaxHalf; k++)
+                if (k == H - 1) {
+                    fw2 = w2[k];
+                    fw1 = w1[k];
+                    fw0 = w0[k];
+                }
+            const int total = (ring[j % kRing][lane] >> 8) + imin(fw2 + f, imin(fw1, fw0 + f));
+            const int d = j - H;
+            const int val = imin(total, 255);
+            if (step == 1) {
+                e[d] = (uint8_t)val;
+            } else {
+                const int base = d * step;
+                e[base] = (uint8_t)val;
+                if (d > 0)   // fillGaps (eucm_sgm.cpp:407-448), case 3 as (2 a + b) / 3, (a + 2 b) / 3
+                    for (int i = step - 1; i > 0; i--) e[base - i] = (uint8_t)((prev * i + val * (step - i)) / step);
+                if (d == nSteps - 1)
+                    for (int q = base + 1; q < D; q++) e[q] = (uint8_t)val;
+            }
+            prev = val;
+        }
+    }
+}
+
+// the per-pixel jump cost of the dynamic programming (_costBuffer; a pixel whose descriptor step was never set: jump_cost)
+__device__ __forceinline__ int jump_of(const StereoGeom &g, int step)
+{
+    if (!g.image_based_cost || step == 0) return g.jump_cost;
+    const int k = step == 1 ? 1 : (step == 2 ? 3 : 6);
+    return (uint8_t)(g.jump_cost * k);   // _costBuffer is 8-bit
+}
+
+constexpr int kAggLanes = 64;        // one wave per scanline
+constexpr int kAggPer = 4;           // disparities per lane (disp_max <= 256)
+
+__device__ __forceinline__ int wave_min(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = imin(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long w = __shfl_xor(v, o, 64);
+        v = w < v ? w : v;
+    }
+    return v;
+}
+
+struct AggArgs {
+    const uint8_t *err;          // [n][P][D]
+    const uint8_t *step, *salient, *skip;   // [n][P]
+    int *sum;                    // [n][P][D]  L + R (+ T + B when write_total)
+    int32_t *disparity;          // [n][P]
+    int64_t n_pairs;
+    int write_total;             // the aggregation stage entry: store L + R + T + B
+};
+
+// computeDynamicStep (eucm_sgm.cpp:450-476) for one wave: c[] holds inCost of this lane's disparities and becomes outCost
+__device__ __forceinline__ void dyn_step(int *c, const uint8_t *err, int D, int lambda, int jump, int *lds)
+{
+    const int lane = threadIdx.x;
+    int m = kInf;
+#pragma unroll
+    for (int q = 0; q < kAggPer; q++) {
+        const int d = lane + q * kAggLanes;
+        if (d < D) {
+            m = imin(m, c[q]);
+            lds[d] = c[q];
+        }
+    }
+    const int best = wave_min(m);
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kAggPer; q++) {
+        const int d = lane + q * kAggLanes;
+        if (d < D) {
+            int val = c[q];
+            if (d + 1 < D) val = imin(val, lds[d + 1] + lambda);
+            if (d > 0) val = imin(val, lds[d - 1] + lambda);
+            val = imin(val, best + jump);
+            c[q] = val + err[d];
+        }
+    }
+    __syncthreads();
+}
+
+// left then right tableaux of one row (computeDynamicProgramming, eucm_sgm.cpp:513-543): sum = L + R
+__global__ __launch_bounds__(kAggLanes) void stereo_agg_rows_kernel(StereoGeom g, AggArgs a)
+{
+    __shared__ int lds[256];
+    const int64_t row = blockIdx.x;   // pair * y_max + y
+    const int X = g.x_max, D = g.disp_max, lane = threadIdx.x;
+    const int64_t p0 = row * X;
+    for (int pass = 0; pass < 2; pass++) {
+        int c[kAggPer];
+        const int x0 = pass == 0 ? 0 : X - 1, dx = pass == 0 ? 1 : -1;
+        const uint8_t *er = a.err + (p0 + x0) * D;
+        int *sr = a.sum + (p0 + x0) * D;
+#pragma unroll
+        for (int q = 0; q < kAggPer; q++) {
+            const int d = lane + q * kAggLanes;
+            if (d < D) {
+                c[q] = er[d];
+                sr[d] = pass == 0 ? c[q] : sr[d] + c[q];
+            }
+        }
+        for (int i = 1; i < X; i++) {
+            const int64_t p = p0 + x0 + (int64_t)dx * i;
+            const int jump = jump_of(g, a.step[p]);
+            dyn_step(c, a.err + p * D, D, g.step_cost, jump, lds);
+            int *s = a.sum + p * D;
+#pragma unroll
+            for (int q = 0; q < kAggPer; q++) {
+                const int d = lane + q * kAggLanes;
+                if (d < D) s[d] = pass == 0 ? c[q] : s[d] + c[q];
+            }
+        }
+    }
+}
+
+// top then bottom tableaux of one column (eucm_sgm.cpp:544-576) added to sum; the bottom pass has the whole sum of every
+// pixel it reaches and picks the winner there (reconstructDisparity, eucm_sgm.cpp:580-626)
+__global__ __launch_bounds__(kAggLanes) void stereo_agg_cols_kernel(StereoGeom g, AggArgs a)
+{
+    __shared__ int lds[256];
+    const int64_t colid = blockIdx.x;   // pair * x_max + x
+    const int X = g.x_max, Y = g.y_max, D = g.disp_max, lane = threadIdx.x;
+    const int64_t pair = colid / X;
+    const int x = (int)(colid % X);
+    const int64_t P = (int64_t)X * Y;
+    for (int pass = 0; pass < 2; pass++) {
+        int c[kAggPer];
+        for (int i = 0; i < Y; i++) {
+            const int y = pass == 0 ? i : Y - 1 - i;
+            const int64_t p = pair * P + (int64_t)y * X + x;
+            const uint8_t *er = a.err + p * D;
+            if (i == 0) {
+#pragma unroll
+                for (int q = 0; q < kAggPer; q++) {
+                    const int d = lane + q * kAggLanes;
+                    if (d < D) c[q] = er[d];
+                }
+            } else {
+                dyn_step(c, er, D, g.step_cost, jump_of(g, a.step[p]), lds);
+            }
+            int *s = a.sum + p * D;
+            if (pass == 0) {
+#pragma unroll
+                for (int q = 0; q < kAggPer; q++) {
+                    const int d = lane + q * kAggLanes;
+                    if (d < D) s[d] += c[q];
+                }
+                continue;
+            }
+            unsigned long long key = ~0ull;
+#pragma unroll
+            for (int q = 0; q < kAggPer; q++) {
+                const int d = lane + q * kAggLanes;
+                if (d < D) {
+                    const int tot = s[d] + c[q];
+                    if (a.write_total) s[d] = tot;
+                    const int ev = er[d];
+                    if (d >= 1 && ev <= g.error_max) {
+                        const unsigned long long k = (unsigned long long)(unsigned)(tot - 2 * ev) << 32 | (unsigned)d;
+                        key = k < key ? k : key;
+                    }
+                }
+            }
+            key = wave_min_u64(key);
+            if (lane == 0) {
+                const bool off = (g.salient_points_only && a.salient[p] == 0) || a.skip[p];
+                a.disparity[p] = (off || key == ~0ull) ? -1 : (int)(key & 0xffffffffu);
+            }
+        }
+    }
+}
+
+struct DepthArgs {
+    const GeomEntry *geom;
+    const uint8_t *err, *step, *salient, *skip;
+    const int32_t *disparity;
+    double *depth, *sigma, *cost;    // [n][P]
+    int64_t n_pairs;
+};
+
+// reconstructDepth (eucm_sgm.cpp:154-218) with the six-argument triangulate (eucm_stereo.cpp:250-296): one lane per pixel
+__global__ __launch_bounds__(256) void stereo_depth_kernel(StereoGeom g, DepthArgs a)
+{
+    const int64_t P = (int64_t)g.x_max * g.y_max;
+    const int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gi >= P * a.n_pairs) return;
+    const int64_t pix = gi % P;
+    double dep = 0., sig = 0., cst = 0.;
+    const GeomEntry ge = a.geom[pix];
+    if (!((g.salient_points_only && !a.salient[gi]) || a.skip[gi]) && (ge.status & kGeomMask)) {
+        cst = (double)a.err[gi * g.disp_max];
+        const int x = (int)(pix % g.x_max), y = (int)(pix / g.x_max);
+        const int disp = a.disparity[gi], step = a.step[gi];
+        int u21, v21, u22, v22;
+        if (g.use_uv_cache) {
+            CacheWalk cw;
+            cw.start(g, ge);
+            cw.go(kDisparityMargin + disp);
+            const bool in1 = inside(g, cw.r.u, cw.r.v);
+            u21 = in1 ? cw.r.u : -1;
+            v21 = in1 ? cw.r.v : -1;
+            cw.go(cw.k + step);
+            const bool in2 = inside(g, cw.r.u, cw.r.v);
+            u22 = in2 ? cw.r.u : -1;
+            v22 = in2 ? cw.r.v : -1;
+        } else {
+            Raster r;
+            make_raster(g, 1, ge.pinf_u, ge.pinf_v, ge.index, ge.flags2, r);
+            r.steps(disp);
+            u21 = r.u;
+            v21 = r.v;
+            r.steps(step);
+            u22 = r.u;
+            v22 = r.v;
+        }
+        double p[3], q1[3], q2[3];
+        if (eucm_reconstruct(g.c1, (double)(x * g.scale + g.u0), (double)(y * g.scale + g.v0), p) &&
+            eucm_reconstruct(g.c2, (double)u21, (double)v21, q1) && eucm_reconstruct(g.c2, (double)u22, (double)v22, q2)) {
+            const double pn = sqrt(dot3(p, p));
+            const double l1 = triangulate_lambda(g.R, g.t, p, q1) * pn;
+            const double l2 = triangulate_lambda(g.R, g.t, p, q2) * pn;
+            if (l1 < kTriangulateDistMax) {
+                sig = fabs(l2 - l1);
+                dep = l1;
+            }
+        }
+    }
+    if (a.depth) a.depth[gi] = dep;
+    if (a.sigma) a.sigma[gi] = sig;
+    if (a.cost) a.cost[gi] = cst;
+}
+
+}  // namespace vgs
