@@ -662,11 +662,11 @@ int vg_stereo_aggregate(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, cons
  * unsteps), one at a time, |steps| <= 1000: uv [|steps| + 1][2] receives the start and every position. */
 int vg_stereo_curve_walk(const double *poly6, int u, int v, int eu, int ev, int step_mult, int steps, int32_t *uv);
 
-/* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the A/B
- * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_force_mfma",
- * "gram_ch1", "gram_no_merge", "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop",
- * "solver_no_speculation", "emit_equal_tiles", ... (the list: enum DebugHook, visgeom_amd/csrc/vg_internal.hpp); value 0 restores
- * the default.  The PRODUCTION library (python -m visgeom_amd._build --production, built without VG_DEBUG_HOOKS) has none of them:
+/* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
+ * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",
+ * "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop", "solver_no_fold_frames",
+ * "solver_fold_max_groups", "emit_nt_min_bytes", "host_chunk_bytes", "gram_persistent", "emit_map_window" (what each does:
+ * enum DebugHook, visgeom_amd/csrc/vg_internal.hpp); value 0 restores the default.  The PRODUCTION library (python -m visgeom_amd._build --production, built without VG_DEBUG_HOOKS) has none of them:
  * every switch is its default at compile time and this entry is not exported.  (VG_RCCL_LIBRARY, the path of the RCCL library to
  * bind, is deployment configuration, not a hook.) */
 int vg_debug_set(const char *name, long long value);

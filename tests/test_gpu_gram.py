@@ -66,9 +66,8 @@ def build(vg, model, n_images, chain_kind, n_points=None):
     return p, ds, status, board, corners, K, bases, strides
 
 
-# single-member chains (W <= 17) run on the vector-pipe kernel (vg_gram_valu.hpp: one chunk of 3 corners per lane for W <= 13,
-# chunks of 2 + 1 for Mei's 17), longer chains on the matrix-core kernel; test_matrix_core_kernels_for_narrow_blocks
-# repeats the narrow cases with the matrix-core kernel forced
+# single-member chains (W <= 17) run on the direct vector-pipe kernel (vg_gram_valu.hpp: one chunk of 3 corners per lane for
+# W <= 13, chunks of 2 + 1 for Mei's 17), longer chains on its factored form (vg_gram_valu_z_kernel)
 CASES = [("eucm", 40, "D", None),      # W = 13                          (config 2 / headline shape)
          ("ucm", 17, "D", None),       # W = 12
          ("mei", 23, "D", None),       # W = 17                          (config 4 shape)
@@ -189,23 +188,6 @@ def test_full_size_10k_gram_properties(vg):
     p.close()
 
 
-def test_matrix_core_kernels_for_narrow_blocks(vg):
-    """vg_debug_set("gram_force_mfma", 1) sends the single-member chains to vg_gram_fused_kernel as well -- one 16 x 16 tile
-    for W <= 16, the RCOL variant (16 Jacobian columns in the tile, residual column on the lanes) for Mei's W = 17: the same
-    cases, the same bars"""
-    from visgeom_amd import capi
-
-    capi.debug_set("gram_force_mfma", 1)
-    try:
-        for c in CASES:
-            test_gram_fused_two_pass_and_sum(vg, *c)
-        test_gram_with_failed_projections_matches_ceres_semantics(vg)
-    finally:
-        capi.debug_set("gram_force_mfma", 0)
-    with pytest.raises(capi.VisgeomError):
-        capi.debug_set("no_such_hook", 1)
-
-
 # The persistent form of the direct kernel (vg_gram_valu_pers_kernel: resident workgroups, the chain walk once per workgroup
 # and chunk, pairs taken from a counter, per-pair totals added in pair order) against the one-shot kernel, through the hook
 # `gram_persistent` (1 = never, 2 / 3 = its four-wave / eight-wave shape whenever it applies): the per-image blocks are the SAME
@@ -286,6 +268,8 @@ def test_persistent_kernel_with_an_image_to_sequence_map(vg):
         assert np.allclose(out[name][1], out["one-shot"][1], rtol=1e-12, atol=0.)
     Gref = oracle_grams("eucm", [0], d["board"], d["corners"][pick], p.get_parameters(), 0, [p.transform_offset(seq, 0)], [6], pick)
     assert_gram_parity(out["eight waves"][0].reshape(n_img, W, W), Gref, "persistent, mapped images")
+    with pytest.raises(capi.VisgeomError):
+        capi.debug_set("no_such_hook", 1)
 
 
 def test_persistent_kernel_on_failed_projections_and_missing_corners(vg):

@@ -38,7 +38,6 @@ ROUTES = [
     ("fold_kJ2_g16", "rig_g16", (1e4, 1.0), 0.0, {}, "fold kJ=2"),
     ("fold_kJ2_stereo", "stereo_missing", (1e4, 1.0, 1e-2), 0.0, {}, "fold kJ=2"),
     ("fold_kJ2_g24", "rig_g24", (1e4, 1.0), 0.0, {}, "fold kJ=2"),
-    ("fold_kJ2_one_wave", "stereo_missing", (1e4, 1e-2), 0.0, {"solver_one_wave_fold": 1}, "fold kJ=2"),
     ("no_fold_hook", "stereo_missing", (1e4, 1e-2), 0.0, {"solver_fold_max_groups": 1}, "entries"),
     ("no_fold_mono_16k", "mono_eucm_16k", (1e4,), 0.0, {}, "entries"),
     ("entries_mei_stereo_rejected", "stereo_mei", (1e4, 1.0, 1e16), 0.0, {}, "entries"),

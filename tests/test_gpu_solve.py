@@ -978,58 +978,38 @@ def test_wide_system_on_the_device_resident_loop(vg):
     assert np.max(np.abs(x_host - x_dev) / np.maximum(np.abs(x_dev), 1.0)) < 1e-6
 
 
-def test_tail_of_a_solve_does_not_depend_on_the_reduced_solve_variant(vg):
+def test_tail_of_a_solve_ends_on_the_function_tolerance_within_ten_iterations(vg):
     """With the reference's tolerances of 1e-15 (unified_calibration.cpp:47-49) the last steps of a solve are rounding noise.
     Ceres tests |cost change| <= function_tolerance * cost on every evaluated candidate BEFORE the acceptance test; with that
     order a rejected noise-level step ends the solve within a radius reduction or two, and the iteration count no longer flips
-    between 6 and 16 with the summation order of a kernel (round 4: the two variants of the reduced solve inside the
-    back-substitution launch).  Same count, same termination, same optimum for both."""
-    from visgeom_amd import capi, synthetic as S
+    between 6 and 16 with the summation order of a kernel (round 4: two variants of the reduced solve inside the
+    back-substitution launch)."""
+    from visgeom_amd import synthetic as S
 
     d = S.make_mono("eucm", 1000, 1)
-    out = []
-    for one_wave in (0, 1):
-        capi.debug_set("solver_one_wave_fold", one_wave)
-        try:
-            p = mono_problem(vg, d, "eucm")[0]
-            s = p.solve(max_num_iterations=100)
-            out.append((s, p.get_parameters()))
-            p.close()
-        finally:
-            capi.debug_set("solver_one_wave_fold", 0)
-    (s_new, x_new), (s_old, x_old) = out
-    assert s_new["termination"] == "CONVERGENCE_FUNCTION" and s_old["termination"] == "CONVERGENCE_FUNCTION"
-    assert s_new["num_iterations"] == s_old["num_iterations"] <= 10
-    assert abs(s_new["final_cost"] - s_old["final_cost"]) <= 1e-12 * s_old["final_cost"]
-    assert np.max(np.abs(x_new - x_old) / np.maximum(np.abs(x_old), 1.0)) < 1e-8
+    p = mono_problem(vg, d, "eucm")[0]
+    s = p.solve(max_num_iterations=100)
+    p.close()
+    assert s["termination"] == "CONVERGENCE_FUNCTION"
+    assert s["num_iterations"] <= 10
 
 
-def test_host_loop_waits_on_sequence_words_or_through_the_runtime_with_the_same_result(vg):
+def test_host_loop_waits_on_sequence_words_and_converges(vg):
     """The host-driven loop (here: a transformation prior forces it) learns of its two read-backs per iteration from pinned
-    sequence words (a counter in the strided sum's last workgroup, a one-thread kernel behind the evaluation); the hook restores
-    hipStreamSynchronize.  Nothing but the wait differs: bit-identical solves."""
-    from visgeom_amd import capi, synthetic as S
+    sequence words (a counter in the strided sum's last workgroup, a one-thread kernel behind the evaluation) instead of
+    hipStreamSynchronize."""
+    from visgeom_amd import synthetic as S
 
     st = S.make_stereo(60)
-    out = []
-    for event_wait in (0, 1):
-        capi.debug_set("solver_event_wait", event_wait)
-        try:
-            p = vg.CalibrationProblem(0)
-            c1 = p.add_camera("eucm", st["init_intrinsics1"])
-            c2 = p.add_camera("eucm", st["init_intrinsics2"])
-            x12 = p.add_transform(True, st["init_xi12"])
-            seq = p.add_transform(False, st["init_poses"])
-            p.add_dataset(c1, [(seq, 0)], st["board"], st["corners1"])
-            p.add_dataset(c2, [(x12, 1), (seq, 0)], st["board"], st["corners2"])
-            p.add_transformation_prior(x12, np.full(6, 0.5))
-            p.finalize()
-            s = p.solve(max_num_iterations=60)
-            out.append((s, p.get_parameters()))
-            p.close()
-        finally:
-            capi.debug_set("solver_event_wait", 0)
-    (s_a, x_a), (s_b, x_b) = out
-    assert s_a["termination"].startswith("CONVERGENCE")
-    assert s_a["num_iterations"] == s_b["num_iterations"] and s_a["final_cost"] == s_b["final_cost"]
-    assert np.array_equal(x_a, x_b)
+    p = vg.CalibrationProblem(0)
+    c1 = p.add_camera("eucm", st["init_intrinsics1"])
+    c2 = p.add_camera("eucm", st["init_intrinsics2"])
+    x12 = p.add_transform(True, st["init_xi12"])
+    seq = p.add_transform(False, st["init_poses"])
+    p.add_dataset(c1, [(seq, 0)], st["board"], st["corners1"])
+    p.add_dataset(c2, [(x12, 1), (seq, 0)], st["board"], st["corners2"])
+    p.add_transformation_prior(x12, np.full(6, 0.5))
+    p.finalize()
+    s = p.solve(max_num_iterations=60)
+    p.close()
+    assert s["termination"].startswith("CONVERGENCE")

@@ -7,9 +7,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", ".."))
 import numpy as np
 
 from visgeom_amd import synthetic as S
-from visgeom_amd import capi as _capi  # noqa: E402
 
-_capi.hooks_from_env()  # legacy VG_* switches -> vg_debug_set
 if os.environ.get("AB_LIB"):   # an A/B library (python -m visgeom_amd._build --variant NAME -DFLAG)
     from visgeom_amd import _build
     _build.LIB = os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), os.environ["AB_LIB"])

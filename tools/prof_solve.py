@@ -13,9 +13,7 @@ from visgeom_amd import _build as _b  # noqa: E402
 if os.environ.get("AB_LIB"):   # same-box A/B against a variant library
     _b.LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.environ["AB_LIB"])
 from visgeom_amd import CalibrationProblem, synthetic  # noqa: E402
-from visgeom_amd import capi as _capi  # noqa: E402
 
-_capi.hooks_from_env()  # legacy VG_* switches -> vg_debug_set
 
 which = sys.argv[1] if len(sys.argv) > 1 else "rig"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 5000

@@ -215,8 +215,9 @@ void fill_emit_args(const vg_problem *p, const Dataset &d, vg::EmitArgs &a, int6
 #ifdef VG_DEBUG_HOOKS
 namespace {
 long long g_debug_hooks[vgi::kHookCount] = {0};
-const char *const kDebugHookNames[vgi::kHookCount] = {"inline_chain_max_bytes", "gram_force_mfma", "gram_ch1", "gram_no_merge", "max_obs_per_launch",
-                                                      "solver_timing", "solver_host_loop", "solver_device_loop", "solver_no_speculation", "emit_equal_tiles", "schur_private_gather", "solver_event_wait", "solver_no_fold_frames", "solver_one_wave_fold", "solver_fold_max_groups", "emit_nt_min_bytes", "host_chunk_bytes", "gram_stamps", "gram_persistent", "emit_map_window"};
+const char *const kDebugHookNames[vgi::kHookCount] = {"inline_chain_max_bytes", "gram_no_merge", "max_obs_per_launch", "solver_timing",
+                                                      "solver_host_loop", "solver_device_loop", "solver_no_fold_frames", "solver_fold_max_groups",
+                                                      "emit_nt_min_bytes", "host_chunk_bytes", "gram_persistent", "emit_map_window"};
 }  // namespace
 long long vgi::debug_hook(vgi::DebugHook h) { return g_debug_hooks[h]; }
 #endif
@@ -781,11 +782,11 @@ int vg_problem_evaluate(vg_problem *p, const vg_dataset_outputs *outs)
         alone.insert(alone.end(), shared.begin(), shared.end());
         shared.clear();
     }
-    if (vgi::debug_hook(vgi::kHookEmitEqualTiles) != 4)   // widest rows first: every die ends on its lightest tiles (hook 4: problem order)
-        std::stable_sort(shared.begin(), shared.end(), [&](int a2, int b2) {
-            const Dataset &da = p->dss[a2], &db = p->dss[b2];
-            return p->cams[da.camera].K + 6 * da.L > p->cams[db.camera].K + 6 * db.L;
-        });
+    // widest rows first: every die ends on its lightest tiles
+    std::stable_sort(shared.begin(), shared.end(), [&](int a2, int b2) {
+        const Dataset &da = p->dss[a2], &db = p->dss[b2];
+        return p->cams[da.camera].K + 6 * da.L > p->cams[db.camera].K + 6 * db.L;
+    });
     for (int i : shared) need_frames = need_frames || !single_launch_dataset(p, p->dss[i]);
     if (need_frames && (rc = vgi::ensure_frames(p)) != VG_OK) return rc;
     for (size_t g0 = 0; g0 < shared.size(); g0 += vg::kEmitMultiMax) {
@@ -815,51 +816,11 @@ int vg_problem_evaluate(vg_problem *p, const vg_dataset_outputs *outs)
                 m.ds[k].map_window = emit_map_window(launch_bytes);
             }
         }
-        // pieces of equal bytes per XCD: a tile of dataset k weighs its bytes per observation -- once the pass is large
-        // enough to be bound by the write stream (past the 256 MiB Infinity Cache); a small pass (a stereo pair: 104 MB in
-        // 21 us) is bound by the latency of a tile, the same for every dataset, and keeps equal counts (measured: 20.9 us
-        // against 22.5 us with byte weights)
-        double w[vg::kEmitMultiMax], total = 0., bytes = 0.;
-        for (int k = 0; k < m.n; k++) {
-            const Dataset &d = p->dss[shared[g0 + k]];
-            w[k] = 32. + 16. * (p->cams[d.camera].K + 6 * d.L);
-            bytes += w[k] * m.ds[k].n_obs;
-        }
-        for (int k = 0; k < m.n; k++) {
-            const long long hook = vgi::debug_hook(vgi::kHookEmitEqualTiles);
-            if (hook == 1 || (hook != 2 && bytes < 256. * 1024 * 1024)) w[k] = 1.;
-            total += w[k] * (m.first_tile[k + 1] - m.first_tile[k]);
-        }
-        unsigned int cut[9], longest = 0;
-        cut[0] = 0;
-        cut[8] = tiles;
-        for (int x = 1; x < 8; x++) {
-            const double target = total * x / 8.;
-            double cum = 0.;
-            unsigned int t = tiles;
-            for (int k = 0; k < m.n; k++) {
-                const unsigned int nk = m.first_tile[k + 1] - m.first_tile[k];
-                if (cum + w[k] * nk >= target) {
-                    t = m.first_tile[k] + (unsigned int)((target - cum) / w[k] + 0.5);
-                    break;
-                }
-                cum += w[k] * nk;
-            }
-            cut[x] = t < cut[x - 1] ? cut[x - 1] : (t > tiles ? tiles : t);
-        }
-        for (int x = 0; x < 8; x++) {
-            m.xcd_first[x] = cut[x];
-            m.xcd_count[x] = cut[x + 1] - cut[x];
-            longest = m.xcd_count[x] > longest ? m.xcd_count[x] : longest;
-        }
-        // default: XCD x takes the x-th eighth of EVERY dataset, dataset after dataset -- equal bytes and equal arithmetic per die
+        // XCD x takes the x-th eighth of EVERY dataset, dataset after dataset -- equal bytes and equal arithmetic per die
         // whatever the mix of models, and the datasets that need no prepared frames come first on every die (same box:
-        // stereo 21.1 -> 19.6 us, rig 116 (equal tile counts) / 108.5 (equal bytes) / 109.4 us; hooks 1 / 2 keep the cut pieces)
-        m.per_dataset = (vgi::debug_hook(vgi::kHookEmitEqualTiles) == 1 || vgi::debug_hook(vgi::kHookEmitEqualTiles) == 2) ? 0 : 1;
-        if (m.per_dataset) {
-            longest = 0;
-            for (int k = 0; k < m.n; k++) longest += (m.first_tile[k + 1] - m.first_tile[k] + 7) / 8;
-        }
+        // stereo 21.1 -> 19.6 us, rig 116 (one contiguous piece of equal tile counts per die) / 108.5 (equal bytes) / 109.4 us)
+        unsigned int longest = 0;
+        for (int k = 0; k < m.n; k++) longest += (m.first_tile[k + 1] - m.first_tile[k] + 7) / 8;
         hipLaunchKernelGGL(vg::vg_emit_multi_kernel, dim3(8 * longest), dim3(vg::kEmitThreads), lds, p->stream, m);
         VG_HIP(hipGetLastError());
     }

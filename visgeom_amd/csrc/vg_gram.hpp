@@ -5,14 +5,12 @@
 // assembled from them (vg_solver).  This code has no counterpart in the reference tree: Ceres forms
 // J^T J internally (call sites src/calibration/unified_calibration.cpp:53,426,1152).
 //
-// Kernels
-//   vg_gram_fused_kernel      one WAVE per image: lanes evaluate corners (same device functions as the emit
-//                             kernel, J never leaves the CU), rows go to a wave-private LDS tile, and
-//                             v_mfma_f64_16x16x4_f64 contracts 4 rows per instruction -- the matrix core is
-//                             used as the cross-lane reduction of the Gram sum.
-//   vg_gram_rows_kernel       same contraction, rows read back from the materialised Ceres-layout J
-//                             (the "second pass" of BASELINE.json's north_star); HBM-read bound.
-//   vg_gram_reduce_kernel     fixed-order two-stage sum over images (no atomics -> run-to-run and
+// Kernels (the fused evaluate + Gram build itself runs on the vector pipe: vg_gram_valu.hpp)
+//   vg_gram_rows_kernel       Gram of the materialised Ceres-layout J (the "second pass" of BASELINE.json's
+//                             north_star): v_mfma_f64_16x16x4_f64 contracts 4 rows per instruction, the
+//                             matrix core used as the cross-lane reduction of the Gram sum; HBM-read bound.
+//   vg_gram_slab_sum_kernel / vg_gram_final_sum_kernel
+//                             fixed-order two-stage sum over images (no atomics -> run-to-run and
 //                             1/2/4/8-GPU reproducible).
 #pragma once
 
@@ -22,8 +20,7 @@ namespace vg {
 
 using f64x4 = __attribute__((ext_vector_type(4))) double;
 
-constexpr int kGramMaxWavesPerBlock = 4;  // the host lowers it when 4 LDS tiles would not fit (wide W)
-constexpr int kGramRowsPerTile = 2 * kWave;  // 64 observations x 2 rows
+constexpr int kGramMaxWavesPerBlock = 4;
 
 struct GramArgs {
     const double *frames;
@@ -59,7 +56,7 @@ __device__ __forceinline__ f64x4 mfma_f64_16x16x4(double a, double b, f64x4 c)
 
 // Store the T x T tiles of accumulators as the full symmetric W x W matrix.
 // f64 C/D layout: lane l, register r holds D[row = (l>>4) + 4r][col = l&15].
-template <int T, bool SKIP_LAST_DIAGONAL = false>
+template <int T>
 __device__ __forceinline__ void store_gram(const f64x4 (&acc)[T][T], double *__restrict__ g, int W, int lane)
 {
     const int col = lane & 15, row0 = lane >> 4;
@@ -67,7 +64,6 @@ __device__ __forceinline__ void store_gram(const f64x4 (&acc)[T][T], double *__r
     for (int ti = 0; ti < T; ti++)
 #pragma unroll
         for (int tj = ti; tj < T; tj++) {
-            if (SKIP_LAST_DIAGONAL && ti == T - 1 && tj == T - 1) continue;  // written by the caller
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int i = 16 * ti + row0 + 4 * r, j = 16 * tj + col;
@@ -95,208 +91,14 @@ __device__ __forceinline__ void wave_lds_fence()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-
 // ------------------------------------------------------------------------------------------
-// fused evaluate + Gram.  One wave owns TWO consecutive images, one per 32-lane half, and walks their
-// corners 32 at a time (an 8 x 12 board is 3 full steps, no idle lanes; a 64-wide step would idle a
-// quarter of them).  Per step every lane evaluates one corner and writes its two rows to the wave's LDS
-// tile (rows 0..63: image A, 64..127: image B); then v_mfma_f64_16x16x4_f64 contracts 4 rows per
-// instruction, alternating between the A and B accumulators (two independent chains).
-// dynamic LDS per wave: [128 rows][W] row tile + the two images' frames.
-// T = ceil(W / 16) column tiles.
-// ------------------------------------------------------------------------------------------
-constexpr int kGramHalf = 32;
-
-__host__ __device__ constexpr int gram_wave_lds_doubles(int W, int frame_stride_d)
-{
-    return kGramRowsPerTile * (W | 1) + 2 * frame_stride_d;  // odd LDS row stride, see the kernel
-}
-
-// CORNER (only with T == 2, W <= 20): the small (W-16) x (W-16) corner of the Gram matrix -- the 1 x 1 r^T r of Mei
-// mono (W = 17), the 3 x 3 of the stereo chain (W = 19) -- would cost a whole third MFMA per 4 rows; it is
-// accumulated by the lanes instead (<= 10 products per row) and reduced once per image with shuffles.
-constexpr int kCornerMax = 4;
-
-//
-// RCOL (only with T == 1, W == 17 -- Mei mono: K + 6 = 16 Jacobian columns + the residual column): the Jacobian
-// columns fill the 16 x 16 MFMA tile exactly, so the whole 17th row/column (J^T r and r^T r) is accumulated by the
-// lanes -- 17 products per row -- instead of costing a second MFMA per 4 rows that would be 15/16 padding.
-template <int MODEL, int T, bool CORNER = false, bool RCOL = false>
-__global__ __launch_bounds__(kGramMaxWavesPerBlock *kWave) void vg_gram_fused_kernel(GramArgs a)
-{
-    static_assert(!CORNER || T == 2, "the VALU corner only exists for two column tiles");
-    static_assert(!RCOL || (T == 1 && !CORNER), "the VALU residual column goes with one full column tile");
-    constexpr int K = CameraTraits<MODEL>::K;
-    using d2 = HIP_vector_type<double, 2>;
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    if (gate_closed(a.gate, a.gate_expect)) return;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const unsigned int bA = 2 * (blockIdx.x * (blockDim.x >> 6) + wave);  // wave-uniform
-    if (bA >= a.n_blocks) return;  // whole wave leaves; no workgroup barrier below
-    const int W = a.W, FS = a.frame_stride_d;
-    double *tile = smem + (size_t)wave * gram_wave_lds_doubles(W, FS);
-    // LDS row stride: odd number of doubles.  An even W (UCM: 12, 18, 24) puts the rows of lanes l and l + 16 in the
-    // same banks -- UCM mono ran at 41 us where the wider EUCM block (W = 13) took 35 us.
-    const int WS = W | 1;
-    double *fr_lds = tile + kGramRowsPerTile * WS;
-    const int h = lane >> 5, sl = lane & (kGramHalf - 1);
-    const unsigned int b = bA + h;
-    const bool bvalid = b < a.n_blocks;
-
-    // both frames are adjacent in memory: one coalesced copy into LDS
-    {
-        const int n_fr = (a.n_blocks - bA >= 2 ? 2 : 1) * FS;
-        const double *src = a.frames + (size_t)bA * FS;
-        for (int i = lane; i < n_fr; i += kWave) fr_lds[i] = src[i];
-        wave_lds_fence();
-    }
-    const double *fr = fr_lds + (bvalid ? h : 0) * FS;
-
-    f64x4 accA[T][T], accB[T][T];
-    zero_acc<T>(accA);
-    zero_acc<T>(accB);
-    double cacc[kCornerMax * (kCornerMax + 1) / 2];
-#pragma unroll
-    for (int q = 0; q < kCornerMax * (kCornerMax + 1) / 2; q++) cacc[q] = 0.;
-    const int Wc = CORNER ? W - 16 : 0;  // 1 .. kCornerMax
-    double racc[RCOL ? 17 : 1];
-#pragma unroll
-    for (int q = 0; q < (RCOL ? 17 : 1); q++) racc[q] = 0.;
-    const int c16 = lane & 15, k4 = lane >> 4;
-
-    for (unsigned int c0 = 0; c0 < a.N; c0 += kGramHalf) {
-        const unsigned int c = c0 + sl;
-        const bool valid = bvalid && c < a.N;
-        const unsigned int cc = c < a.N ? c : a.N - 1;
-        const unsigned int bb = bvalid ? b : bA;
-        const double g0 = a.board[3 * cc], g1 = a.board[3 * cc + 1], g2 = a.board[3 * cc + 2];
-        const double X0 = (fr[0] * g0 + fr[1] * g1 + fr[2] * g2) + fr[9];
-        const double X1 = (fr[3] * g0 + fr[4] * g1 + fr[5] * g2) + fr[10];
-        const double X2 = (fr[6] * g0 + fr[7] * g1 + fr[8] * g2) + fr[11];
-        const d2 ob = reinterpret_cast<const d2 *>(a.obs)[(size_t)bb * a.N + cc];
-        CornerEval<K> e;
-        eval_corner_fast<MODEL>(a.intr, X0, X1, X2, e);
-
-        // rows are written unconditionally; lanes without a corner then overwrite theirs with zeros (a branch
-        // no lane takes on full boards) -- cheaper than a select per element
-        double *ru = tile + (size_t)(kWave * h + 2 * sl) * WS, *rv = ru + WS;
-#pragma unroll
-        for (int i = 0; i < K; i++) {
-            ru[i] = e.Ju[i];
-            rv[i] = e.Jv[i];
-        }
-        for (int l = 0; l < a.L; l++) {
-            double rows[12];
-            pose_rows_fast(e.P, X0, X1, X2, fr + 12 + 21 * l, rows);
-#pragma unroll
-            for (int j = 0; j < 6; j++) {
-                ru[K + 6 * l + j] = rows[j];
-                rv[K + 6 * l + j] = rows[6 + j];
-            }
-        }
-        // residual column; a failed projection contributes the in-band 1e15 exactly as it would
-        // inside Ceres (calib_cost_functions.cpp:66-70)
-        ru[W - 1] = e.ok ? e.u - ob.x : kDoubleBig;
-        rv[W - 1] = e.ok ? e.v - ob.y : kDoubleBig;
-        if (!valid) {
-            for (int i = 0; i < W; i++) {
-                ru[i] = 0.;
-                rv[i] = 0.;
-            }
-        }
-        if (CORNER) {
-            // this lane's own two rows, columns 16 .. W-1 (just written; DS ops of a wave execute in order)
-            double cu[kCornerMax], cv[kCornerMax];
-#pragma unroll
-            for (int q = 0; q < kCornerMax; q++) {
-                cu[q] = q < Wc ? ru[16 + q] : 0.;
-                cv[q] = q < Wc ? rv[16 + q] : 0.;
-            }
-#pragma unroll
-            for (int r = 0, q = 0; r < kCornerMax; r++)
-#pragma unroll
-                for (int c = r; c < kCornerMax; c++, q++) cacc[q] += cu[r] * cu[c] + cv[r] * cv[c];
-        }
-        if constexpr (RCOL) {
-            // this lane's own two rows (just written, zeroed when the lane has no corner): column 16 against all 17
-            const double su = ru[16], sv = rv[16];
-#pragma unroll
-            for (int q = 0; q < 16; q++) racc[q] += ru[q] * su + rv[q] * sv;
-            racc[16] += su * su + sv * sv;
-        }
-        wave_lds_fence();
-
-        // always 16 groups of 4 rows per image: rows of lanes without a corner are zero, so a ragged last
-        // step only wastes matrix-pipe time, and the fixed trip count lets the LDS reads be pipelined
-        constexpr int n_steps = kGramHalf / 2;
-        const double *rowA = tile + (size_t)k4 * WS, *rowB = rowA + (size_t)kWave * WS;
-#pragma unroll 4
-        for (int t = 0; t < n_steps; t++) {
-            double vA[T], vB[T];
-#pragma unroll
-            for (int j = 0; j < T; j++) {
-                const int col = 16 * j + c16;
-                vA[j] = col < W ? rowA[(size_t)(4 * t) * WS + col] : 0.;
-                vB[j] = col < W ? rowB[(size_t)(4 * t) * WS + col] : 0.;
-            }
-#pragma unroll
-            for (int ti = 0; ti < T; ti++)
-#pragma unroll
-                for (int tj = ti; tj < T; tj++) {
-                    if (CORNER && ti == 1) continue;  // the corner tile is accumulated by the lanes
-                    accA[ti][tj] = mfma_f64_16x16x4(vA[ti], vA[tj], accA[ti][tj]);
-                    accB[ti][tj] = mfma_f64_16x16x4(vB[ti], vB[tj], accB[ti][tj]);
-                }
-        }
-        wave_lds_fence();
-    }
-    store_gram<T, CORNER>(accA, a.gram + (size_t)bA * W * W, W, lane);
-    if (bA + 1 < a.n_blocks) store_gram<T, CORNER>(accB, a.gram + (size_t)(bA + 1) * W * W, W, lane);
-    if constexpr (RCOL) {
-        // sum over the 32 lanes of each image (fixed butterfly inside the half-wave), lane 0 of the half stores
-#pragma unroll
-        for (int q = 0; q < 17; q++)
-#pragma unroll
-            for (int off = 16; off >= 1; off >>= 1) racc[q] += __shfl_xor(racc[q], off, kWave);
-        if (sl == 0 && bvalid) {
-            double *g = a.gram + (size_t)b * W * W;
-#pragma unroll
-            for (int q = 0; q < 16; q++) {
-                g[q * W + 16] = racc[q];
-                g[16 * W + q] = racc[q];
-            }
-            g[16 * W + 16] = racc[16];
-        }
-    }
-    if (CORNER) {
-        // sum over the 32 lanes of each image (fixed butterfly inside the half-wave), lane 0 of the half stores
-#pragma unroll
-        for (int q = 0; q < kCornerMax * (kCornerMax + 1) / 2; q++)
-#pragma unroll
-            for (int off = 16; off >= 1; off >>= 1) cacc[q] += __shfl_xor(cacc[q], off, kWave);
-        if (sl == 0 && bvalid) {
-            double *g = a.gram + (size_t)b * W * W;
-#pragma unroll
-            for (int r = 0, q = 0; r < kCornerMax; r++)
-#pragma unroll
-                for (int c = r; c < kCornerMax; c++, q++)
-                    if (c < Wc) {
-                        g[(16 + r) * W + 16 + c] = cacc[q];
-                        g[(16 + c) * W + 16 + r] = cacc[q];
-                    }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// two-pass: Gram of the materialised rows (the "second pass" over J).  Same work split and the same
-// contraction order as the fused kernel -- one wave per pair of images, A / B accumulators alternating,
-// 4 rows per MFMA in increasing row order -- so both paths give bit-identical matrices.  Every MFMA
+// two-pass: Gram of the materialised rows (the "second pass" over J).  One wave per pair of images, A / B
+// accumulators alternating, 4 rows per MFMA in increasing row order.  Every MFMA
 // operand is gathered straight from the Ceres-layout arrays (per 4 rows: 4K, 24 and 4 consecutive
 // doubles); kRowsUnroll groups are loaded ahead of their MFMAs to keep loads in flight.
 // ------------------------------------------------------------------------------------------
 constexpr int kRowsUnroll = 8;
+constexpr int kGramHalf = 32;   // corners per contraction step of an image
 
 template <int T>
 __global__ __launch_bounds__(kGramMaxWavesPerBlock *kWave) void vg_gram_rows_kernel(GramArgs a, int K)
@@ -336,8 +138,8 @@ __global__ __launch_bounds__(kGramMaxWavesPerBlock *kWave) void vg_gram_rows_ker
     f64x4 accA[T][T], accB[T][T];
     zero_acc<T>(accA);
     zero_acc<T>(accB);
-    // the fused kernel contracts each image in steps of 32 corners = 16 groups of 4 rows, zero-padded at the
-    // end of the image; reproduce exactly that sequence of (row group -> MFMA) so the sums round identically
+    // each image is contracted in steps of 32 corners = 16 groups of 4 rows, zero-padded at the end of the image:
+    // a fixed sequence of (row group -> MFMA), so the sums round the same way whatever the launch
     const unsigned int n_chunks = (a.N + kGramHalf - 1) / kGramHalf;
     for (unsigned int ch = 0; ch < n_chunks; ch++) {
         const unsigned int row0 = ch * 2 * kGramHalf;

@@ -29,9 +29,6 @@ void fill_gram_args(const vg_problem *p, const Dataset &d, vg::GramArgs &a, doub
     a.obs = d.d_obs;
     a.intr = d_params + cam.offset;
     a.res = nullptr;
-#ifdef VG_GRAM_STAMPS
-    a.res = reinterpret_cast<double *>(vgi::debug_hook(vgi::kHookGramStamps));   // measurement build: the clock stamps' buffer
-#endif
     a.jac_intr = nullptr;
     for (int l = 0; l < vg::kMaxChain; l++) a.jac_member[l] = nullptr;
     a.gram = gram;
@@ -44,43 +41,11 @@ void fill_gram_args(const vg_problem *p, const Dataset &d, vg::GramArgs &a, doub
     a.gate_expect = p->gram_gate_expect;
 }
 
-template <int MODEL>
-int launch_gram_fused(hipStream_t stream, const vg::GramArgs &a)
-{
-    const bool rcol = a.W == 17;  // 16 Jacobian columns + residual (Mei mono): residual row / column on the lanes
-    const int T = rcol ? 1 : (a.W + 15) / 16;
-    // one LDS tile per wave (= per pair of images); as many waves per workgroup (<= 4) as fit in 80 KiB, so
-    // that two workgroups share a CU (160 KiB LDS) and one can contract while the other evaluates
-    const size_t tile = (size_t)vg::gram_wave_lds_doubles(a.W, a.frame_stride_d) * sizeof(double);
-    int waves = (int)((80 * 1024) / tile);
-    waves = waves < 1 ? 1 : (waves > vg::kGramMaxWavesPerBlock ? vg::kGramMaxWavesPerBlock : waves);
-    const unsigned int n_pairs = (a.n_blocks + 1) / 2;
-    const unsigned int grid = (n_pairs + waves - 1) / waves;
-    const size_t lds = (size_t)waves * tile;
-    const dim3 blk(waves * vg::kWave);
-    if (rcol) hipLaunchKernelGGL((vg::vg_gram_fused_kernel<MODEL, 1, false, true>), dim3(grid), blk, lds, stream, a);
-    else if (T == 1) hipLaunchKernelGGL((vg::vg_gram_fused_kernel<MODEL, 1>), dim3(grid), blk, lds, stream, a);
-    else if (T == 2 && a.W - 16 <= vg::kCornerMax)
-        hipLaunchKernelGGL((vg::vg_gram_fused_kernel<MODEL, 2, true>), dim3(grid), blk, lds, stream, a);
-    else if (T == 2) hipLaunchKernelGGL((vg::vg_gram_fused_kernel<MODEL, 2>), dim3(grid), blk, lds, stream, a);
-    else hipLaunchKernelGGL((vg::vg_gram_fused_kernel<MODEL, 3>), dim3(grid), blk, lds, stream, a);
-    VG_HIP(hipGetLastError());
-    return VG_OK;
-}
-
-
-// Narrow row blocks (W <= 13, chain of at most one member) take the vector-pipe kernel of vg_gram_valu.hpp; a single
-// DIRECT member is walked in-kernel.  Both are pure functions of the problem (never of call history).
-bool gram_uses_valu(const vg_problem *p, const Dataset &d)
-{
-    const bool force_mfma = vgi::debug_hook(vgi::kHookGramForceMfma) != 0;  // measurement hook (A/B of the two kernels)
-    (void)p;
-    return !force_mfma && d.L <= vg::kMaxChain;  // one member: the direct form; two or more: the factored form (vg_gram_valu_z_kernel)
-}
-
+// Every row block takes the vector-pipe kernels of vg_gram_valu.hpp (one member: the direct form; two or more: the factored
+// form, vg_gram_valu_z_kernel); a single DIRECT member is walked in-kernel.  A pure function of the problem (never of call history).
 bool gram_inline_chain(const vg_problem *p, const Dataset &d)
 {
-    return !p->force_prepared_frames && gram_uses_valu(p, d) && d.L == 1 && d.status[0] == VG_TRANSFORM_DIRECT;
+    return !p->force_prepared_frames && d.L == 1 && d.status[0] == VG_TRANSFORM_DIRECT;
 }
 
 // The persistent form (vg_gram_valu_pers_kernel): a single DIRECT member walked in the kernel, blocks up to 13 wide, a board of
@@ -174,15 +139,10 @@ int launch_gram_valu_lch(hipStream_t stream, const vg::GramValuArgs &a, bool inl
 template <int MODEL, int L>
 int launch_gram_valu_l(hipStream_t stream, const vg::GramValuArgs &a, bool inline_chain)
 {
-    const bool force_ch1 = vgi::debug_hook(vgi::kHookGramCh1) != 0;  // measurement hook
     constexpr int W = vg::CameraTraits<MODEL>::K + 6 * L + 1;
-#ifdef VG_GRAM_CH2
-    constexpr int kMain = W <= 19 ? 2 : 1;   // tools/exp A/B build: two corners per lane, three waves per SIMD on the 13-wide blocks
-#else
     constexpr int kMain = W <= 13 ? 3 : (W <= 19 ? 2 : 1);
-#endif
     if constexpr (kMain > 1)
-        if (!force_ch1 && a.g.N > (unsigned)vg::kValuLanesPerImage) return launch_gram_valu_lch<MODEL, L, kMain>(stream, a, inline_chain);
+        if (a.g.N > (unsigned)vg::kValuLanesPerImage) return launch_gram_valu_lch<MODEL, L, kMain>(stream, a, inline_chain);
     return launch_gram_valu_lch<MODEL, L, 1>(stream, a, inline_chain);
 }
 
@@ -195,7 +155,7 @@ int launch_gram_valu(hipStream_t stream, const vg::GramValuArgs &a, int L, bool 
     constexpr int K = vg::CameraTraits<MODEL>::K;
     constexpr int CH = K + 7 <= 13 ? 3 : 2;
     const size_t lds = vg::gram_valu_z_lds_bytes(K, L);
-    const bool small_board = a.g.N <= (unsigned)vg::kValuLanesPerImage || vgi::debug_hook(vgi::kHookGramCh1) != 0;
+    const bool small_board = a.g.N <= (unsigned)vg::kValuLanesPerImage;
     if (lds > 48 * 1024) {  // chains of four or five members: more than the default dynamic LDS limit
         const void *fn = small_board ? reinterpret_cast<const void *>(vg::vg_gram_valu_z_kernel<MODEL, 1>)
                                      : reinterpret_cast<const void *>(vg::vg_gram_valu_z_kernel<MODEL, CH>);
@@ -234,63 +194,52 @@ int vgi::gram_fused_at(vg_problem *p, int dataset_id, const double *d_params, do
     if (!gram) return fail(VG_ERR_INVALID_ARGUMENT, "gram is NULL");
     if (d.n_blocks > 0x7fffffff) return fail(VG_ERR_INVALID_ARGUMENT, "too many blocks for one launch");
     int rc;
-    if (gram_uses_valu(p, d)) {
-        vg::GramValuArgs a;
-        fill_gram_args(p, d, a.g, gram, d_params);
-        const bool inl = gram_inline_chain(p, d);
-        a.chain_params = d.L ? d_params + d.chain.base[0] : nullptr;
-        a.chain_stride = d.L ? d.chain.stride[0] : 0;
-        a.seq_index = d.seq_identity ? nullptr : d.d_seq;
-        a.n_wg = (unsigned int)((d.n_blocks + vg::kValuImagesPerBlock - 1) / vg::kValuImagesPerBlock);
-        a.partials = nullptr;
-        const int E = W * (W + 1) / 2;
-        if (sum) {
-            // room for either kernel's partials: one per octet (one-shot), one per resident workgroup (persistent: at most one per
-            // image pair and never more than 1 024)
-            const size_t n_part = gram_partial_count(d.n_blocks);
-            if (!d.d_wg_partials) VG_HIP(hipMalloc(&d.d_wg_partials, sizeof(double) * (size_t)E * n_part));
-            a.partials = d.d_wg_partials;
-        }
-        const int pers = (inl && d.L == 1) ? gram_pers_shape(a, sum != nullptr) : 0;
-        if (pers) {
-            unsigned int n_wg = 0;
-            switch (cam.model) {
-            case VG_MODEL_EUCM: rc = launch_gram_valu_pers_shape<vg::kEUCM, 3>(p->stream, a, pers, &n_wg); break;
-            case VG_MODEL_UCM: rc = launch_gram_valu_pers_shape<vg::kUCM, 3>(p->stream, a, pers, &n_wg); break;
-            default: rc = launch_gram_valu_pers_shape<vg::kMEI, 2>(p->stream, a, pers, &n_wg); break;   // 17-wide rows: two corners, then the third
-            }
-            a.n_wg = n_wg;
-        } else {
-            switch (cam.model) {
-            case VG_MODEL_EUCM: rc = launch_gram_valu<vg::kEUCM>(p->stream, a, d.L, inl); break;
-            case VG_MODEL_UCM: rc = launch_gram_valu<vg::kUCM>(p->stream, a, d.L, inl); break;
-            default: rc = launch_gram_valu<vg::kMEI>(p->stream, a, d.L, inl); break;
-            }
-        }
-        if (rc != VG_OK || !sum) return rc;
-        hipLaunchKernelGGL(vg::vg_gram_partials_sum_kernel, dim3(E), dim3(256), 0, p->stream,
-                           (const double *)d.d_wg_partials, a.n_wg, W, sum);
-        VG_HIP(hipGetLastError());
-        return VG_OK;
+    vg::GramValuArgs a;
+    fill_gram_args(p, d, a.g, gram, d_params);
+    const bool inl = gram_inline_chain(p, d);
+    a.chain_params = d.L ? d_params + d.chain.base[0] : nullptr;
+    a.chain_stride = d.L ? d.chain.stride[0] : 0;
+    a.seq_index = d.seq_identity ? nullptr : d.d_seq;
+    a.n_wg = (unsigned int)((d.n_blocks + vg::kValuImagesPerBlock - 1) / vg::kValuImagesPerBlock);
+    a.partials = nullptr;
+    const int E = W * (W + 1) / 2;
+    if (sum) {
+        // room for either kernel's partials: one per octet (one-shot), one per resident workgroup (persistent: at most one per
+        // image pair and never more than 1 024)
+        const size_t n_part = gram_partial_count(d.n_blocks);
+        if (!d.d_wg_partials) VG_HIP(hipMalloc(&d.d_wg_partials, sizeof(double) * (size_t)E * n_part));
+        a.partials = d.d_wg_partials;
     }
-    vg::GramArgs a;
-    fill_gram_args(p, d, a, gram, d_params);
-    switch (cam.model) {
-    case VG_MODEL_EUCM: rc = launch_gram_fused<vg::kEUCM>(p->stream, a); break;
-    case VG_MODEL_UCM: rc = launch_gram_fused<vg::kUCM>(p->stream, a); break;
-    default: rc = launch_gram_fused<vg::kMEI>(p->stream, a); break;
+    const int pers = (inl && d.L == 1) ? gram_pers_shape(a, sum != nullptr) : 0;
+    if (pers) {
+        unsigned int n_wg = 0;
+        switch (cam.model) {
+        case VG_MODEL_EUCM: rc = launch_gram_valu_pers_shape<vg::kEUCM, 3>(p->stream, a, pers, &n_wg); break;
+        case VG_MODEL_UCM: rc = launch_gram_valu_pers_shape<vg::kUCM, 3>(p->stream, a, pers, &n_wg); break;
+        default: rc = launch_gram_valu_pers_shape<vg::kMEI, 2>(p->stream, a, pers, &n_wg); break;   // 17-wide rows: two corners, then the third
+        }
+        a.n_wg = n_wg;
+    } else {
+        switch (cam.model) {
+        case VG_MODEL_EUCM: rc = launch_gram_valu<vg::kEUCM>(p->stream, a, d.L, inl); break;
+        case VG_MODEL_UCM: rc = launch_gram_valu<vg::kUCM>(p->stream, a, d.L, inl); break;
+        default: rc = launch_gram_valu<vg::kMEI>(p->stream, a, d.L, inl); break;
+        }
     }
     if (rc != VG_OK || !sum) return rc;
-    return vgi::gram_sum_into(p, dataset_id, gram, sum);
+    hipLaunchKernelGGL(vg::vg_gram_partials_sum_kernel, dim3(E), dim3(256), 0, p->stream,
+                       (const double *)d.d_wg_partials, a.n_wg, W, sum);
+    VG_HIP(hipGetLastError());
+    return VG_OK;
 }
 
 bool vgi::gram_merge_covers_all(const vg_problem *p)
 {
-    if (vgi::debug_hook(vgi::kHookGramNoMerge) || vgi::debug_hook(vgi::kHookGramCh1)) return false;
+    if (vgi::debug_hook(vgi::kHookGramNoMerge)) return false;
     int n = 0;
     for (const Dataset &d : p->dss) {
         if (!d.n_blocks) continue;
-        if (!(d.n_blocks <= 0x7fffffff && gram_uses_valu(p, d) && d.L >= 1 && d.N > vg::kValuLanesPerImage)) return false;
+        if (!(d.n_blocks <= 0x7fffffff && d.L >= 1 && d.N > vg::kValuLanesPerImage)) return false;
         n++;
     }
     return n >= 2 && n % vg::kGramMultiMax != 1;  // a lone leftover group would go the ordinary way
@@ -299,23 +248,22 @@ bool vgi::gram_merge_covers_all(const vg_problem *p)
 int vgi::gram_fused_merged_at(vg_problem *p, const double *d_params, double *const *grams, std::vector<char> &taken,
                               double *const *partials)
 {
-    const bool off = vgi::debug_hook(vgi::kHookGramNoMerge) == 1 || vgi::debug_hook(vgi::kHookGramCh1) != 0;  // measurement hooks
+    const bool off = vgi::debug_hook(vgi::kHookGramNoMerge) != 0;  // test hook: one launch per dataset
     const int n_ds = (int)p->dss.size();
     taken.assign((size_t)n_ds, 0);
     std::vector<int> ids;
     for (int i = 0; i < n_ds && !off; i++) {
         const Dataset &d = p->dss[i];
-        if (d.n_blocks > 0 && d.n_blocks <= 0x7fffffff && grams[i] && gram_uses_valu(p, d) && d.L >= 1 && d.N > vg::kValuLanesPerImage)
+        if (d.n_blocks > 0 && d.n_blocks <= 0x7fffffff && grams[i] && d.L >= 1 && d.N > vg::kValuLanesPerImage)
             ids.push_back(i);
     }
     if (ids.size() < 2) return VG_OK;
     // heaviest workgroups first: the launch ends on the light datasets' workgroups instead of a tail of the widest blocks
     // (same box, merged launch in dataset order -> heaviest first: stereo 14.4 -> 12.7 us, rig 66-71 -> 61-64 us)
-    if (vgi::debug_hook(vgi::kHookGramNoMerge) != 2)
-        std::stable_sort(ids.begin(), ids.end(), [&](int a2, int b2) {
-            const Dataset &da = p->dss[a2], &db = p->dss[b2];
-            return p->cams[da.camera].K + 6 * da.L > p->cams[db.camera].K + 6 * db.L;
-        });
+    std::stable_sort(ids.begin(), ids.end(), [&](int a2, int b2) {
+        const Dataset &da = p->dss[a2], &db = p->dss[b2];
+        return p->cams[da.camera].K + 6 * da.L > p->cams[db.camera].K + 6 * db.L;
+    });
     for (size_t g0 = 0; g0 < ids.size(); g0 += vg::kGramMultiMax) {
         vg::GramValuMultiArgs m;
         m.n = (int)(ids.size() - g0 < (size_t)vg::kGramMultiMax ? ids.size() - g0 : (size_t)vg::kGramMultiMax);

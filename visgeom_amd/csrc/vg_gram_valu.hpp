@@ -23,23 +23,6 @@
 
 #include "vg_gram.hpp"
 
-// Measurement build only (-DVG_GRAM_STAMPS, tools/exp/gram_stamps_probe.py): lane 0 of every wave stores the shader clock at
-// eight points of its life into the buffer the "gram_stamps" debug hook names (it travels in GramArgs::res, which the Gram
-// kernels do not use otherwise).  The product build compiles none of this.
-#ifdef VG_GRAM_STAMPS
-#define VG_STAMP(slot, i)                                                                    \
-    do {                                                                                     \
-        if (slot) {                                                                          \
-            const unsigned long long t_ = __builtin_readcyclecounter();                      \
-            if ((threadIdx.x & 63) == 0) (slot)[i] = t_;                                     \
-        }                                                                                    \
-    } while (0)
-#else
-#define VG_STAMP(slot, i) \
-    do {                  \
-    } while (0)
-#endif
-
 namespace vg {
 
 #ifndef VG_VALU_THREADS
@@ -262,7 +245,7 @@ struct ValuChunkIn {
 // lanes in one depth-first pass; the lane's share of the image's Gram sum is added to out[].
 template <int MODEL, int L, int CC, int kOut>
 __device__ __forceinline__ void valu_chunk(const double *__restrict__ intr, const double *fr, const ValuChunkIn<CC> &in,
-                                           int sl, double (&out)[kOut], unsigned long long *stamps = nullptr)
+                                           int sl, double (&out)[kOut])
 {
     using Rows = ValuRows<MODEL, L, CC>;
     constexpr int K = Rows::K, W = Rows::W;
@@ -315,12 +298,10 @@ __device__ __forceinline__ void valu_chunk(const double *__restrict__ intr, cons
             }
     }
     // ---- phase 2: products and the sum over the 32 lanes of the image in one depth-first pass
-    VG_STAMP(stamps, 3);
     double t[kOut];
     valu_tree_all(R, t, std::make_integer_sequence<int, kOut>{});
 #pragma unroll
     for (int k = 0; k < kOut; k++) out[k] += t[k];
-    VG_STAMP(stamps, 4);
 }
 
 // CH = corners per lane in a full chunk (32 CH corners of the image): 3 covers an 8 x 12 board in one chunk for the 13-wide
@@ -349,15 +330,6 @@ __device__ __forceinline__ void gram_valu_body(const GramValuArgs &a, const unsi
     const unsigned int b0 = block * kValuImagesPerBlock;
     const unsigned int b = b0 + (unsigned)(tid / kValuLanesPerImage);
     const bool bvalid = b < a.g.n_blocks;
-#ifdef VG_GRAM_STAMPS
-    unsigned long long *stamps = a.g.res ? reinterpret_cast<unsigned long long *>(const_cast<double *>(a.g.res)) + ((size_t)block * (kValuThreads / kWave) + wave) * 10 : nullptr;
-#else
-    unsigned long long *stamps = nullptr;
-#endif
-    VG_STAMP(stamps, 0);
-#ifdef VG_GRAM_STAMPS
-    if (stamps && (threadIdx.x & 63) == 0) stamps[8] = wall_clock64();   // 100 MHz, common to all XCDs: the launch's timeline
-#endif
 
     // The member's six parameters are the head of the wave's longest dependent chain (load -> rsqrt -> sincos -> frame ->
     // every corner): requested FIRST, so that waiting for them does not wait for the twelve loads behind them (vmcnt counts
@@ -386,7 +358,6 @@ __device__ __forceinline__ void gram_valu_body(const GramValuArgs &a, const unsi
     // waves of a workgroup drift apart and cover each other's latencies (with one walker per workgroup three waves
     // sat at the barrier for the whole dependent chain: 42 % of all wave cycles were waits)
     double *fr_mine = fr_lds + (tid / kValuLanesPerImage) * FS;
-    VG_STAMP(stamps, 1);
     if (INLINE) {
         if (sl == 0 && bvalid) build_frame_single_direct_fast(xi_reg, fr_mine);
     } else if (bvalid) {
@@ -395,7 +366,6 @@ __device__ __forceinline__ void gram_valu_body(const GramValuArgs &a, const unsi
     }
     wave_lds_fence();
     const double *fr = fr_mine;
-    VG_STAMP(stamps, 2);
 
     double out[kOut];
 #pragma unroll
@@ -403,7 +373,7 @@ __device__ __forceinline__ void gram_valu_body(const GramValuArgs &a, const unsi
 
     unsigned int c0 = 0;
     for (unsigned int m = 0; m < n_full; m++) {
-        valu_chunk<MODEL, L, CH, kOut>(a.g.intr, fr, in_full, sl, out, stamps);
+        valu_chunk<MODEL, L, CH, kOut>(a.g.intr, fr, in_full, sl, out);
         c0 += kFull;
         if (m + 1 < n_full) in_full.load(a.g, b, b0, bvalid, sl, c0);
     }
@@ -465,12 +435,10 @@ __device__ __forceinline__ void gram_valu_body(const GramValuArgs &a, const unsi
             if (have && lane < kValuLanesPerImage) red[wave * E + base + k] = tot;
         }
     }
-    VG_STAMP(stamps, 5);
     if (a.partials) {
         // the one barrier of the kernel, at its very end: the waves that arrive have nothing left to do (a barrier at the head
         // -- needed by a "last wave adds" ticket -- delays every wave's first load instead: measured +480 cycles per wave)
         __syncthreads();
-        VG_STAMP(stamps, 6);
         for (int e = tid; e < E; e += kValuThreads) {  // E = 276 for the 23-wide block: more entries than threads
             double s = red[e];
 #pragma unroll
@@ -478,28 +446,13 @@ __device__ __forceinline__ void gram_valu_body(const GramValuArgs &a, const unsi
             a.partials[(size_t)e * a.n_wg + block] = s;
         }
     }
-    VG_STAMP(stamps, 7);
-#ifdef VG_GRAM_STAMPS
-    if (stamps && (threadIdx.x & 63) == 0) stamps[9] = wall_clock64();
-#endif
 }
 
-// waves per SIMD the register budget is cut for: two (256 registers); the tools/exp build -DVG_GRAM_CH2 asks for three with two
-// corners per lane on the 13-wide blocks (A/B of occupancy against the second reduction tree per image)
-template <int MODEL, int L, int CH>
-__host__ __device__ constexpr int valu_min_waves()
-{
-#ifdef VG_GRAM_CH2
-    return (CameraTraits<MODEL>::K + 6 * L + 1 <= 13 && CH <= 2) ? 3 : 2;
-#elif defined(VG_GRAM_WAVES3)   // tools/exp A/B build: three waves per SIMD by register limit (168) with THREE corners per lane -- the rows alone are 156
-    return (CameraTraits<MODEL>::K + 6 * L + 1 <= 13) ? 3 : 2;
-#else
-    return 2;
-#endif
-}
+// waves per SIMD the register budget is cut for: two (256 registers)
+constexpr int kValuMinWaves = 2;
 
 template <int MODEL, int L, bool INLINE, int CH>
-__global__ __launch_bounds__(kValuThreads, (valu_min_waves<MODEL, L, CH>())) void vg_gram_valu_kernel(GramValuArgs a)
+__global__ __launch_bounds__(kValuThreads, kValuMinWaves) void vg_gram_valu_kernel(GramValuArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double valu_lds[];
     gram_valu_body<MODEL, L, INLINE, CH>(a, blockIdx.x, valu_lds);
@@ -582,20 +535,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
     double *stage_lds = board_lds + 3 * 32 * kPersCorners;
     int *counter = reinterpret_cast<int *>(stage_lds + kPersWaves * 2 * kPersCorners * kWave * 2);   // [4]: next pair of each SIMD's range
     if (gate_closed(a.g.gate, a.g.gate_expect)) return;
-#ifdef VG_GRAM_STAMPS   // measurement build (tools/exp/gram_pers_stamps_probe.py): 16 wall-clock stamps (100 MHz) per wave -- 0 entry,
-                        // 1 walk + barrier done, 2 first pair's observations in LDS, 3..9 end of every pair (its stores issued); inside a
-                        // wave's FIRST pair: 10 inputs read + next pair requested, 11 rows / products / tree done, 12 the wait passed;
-                        // 13 shader-clock cycles of rows / products / tree (first pair: low word, second: high word); 14 chunk barrier
-                        // passed, 15 end
-    unsigned long long *pstamps = a.g.res ? reinterpret_cast<unsigned long long *>(const_cast<double *>(a.g.res)) + ((size_t)blockIdx.x * (THREADS / kWave) + (threadIdx.x >> 6)) * 16 : nullptr;
-    int pstamp_unit = 3;
-#define VG_PSTAMP(i) do { if (pstamps && (threadIdx.x & 63) == 0) pstamps[i] = wall_clock64(); } while (0)
-    if (pstamps && (threadIdx.x & 63) == 0)   // the per-pair slots of an earlier launch of a train must not survive
-        for (int i = 3; i < 14; i++) pstamps[i] = 0ull;
-#else
-#define VG_PSTAMP(i) do { } while (0)
-#endif
-    VG_PSTAMP(0);
 
     const unsigned int block = blockIdx.x, n_wg = gridDim.x;
     // pairs [p_first, p_end) of this workgroup
@@ -625,7 +564,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
         gram_pers_walk(a.chain_params, a.seq_index, a.chain_stride, img0, chunk_images, (int)((block + chunk_no) & (unsigned)(kPersWaves - 1)), fr_lds);
         if (threadIdx.x < 4) counter[threadIdx.x] = 0;
         __syncthreads();
-        VG_PSTAMP(1);
         // ---- pairs of the chunk, taken from the counter; the observations of a wave's NEXT pair are on their way while it
         // computes the current one
         {
@@ -668,7 +606,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 request(u, 0);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
-            VG_PSTAMP(2);
             while ((unsigned)u < chunk_pairs) {
                 const unsigned int li = 2u * (unsigned)u + (unsigned)h;
                 const unsigned int b = img0 + li;
@@ -702,24 +639,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 double out[kOut];
 #pragma unroll
                 for (int k = 0; k < kOut; k++) out[k] = 0.;
-#ifdef VG_GRAM_STAMPS
-                unsigned long long cyc0 = 0;
-                if (pstamp_unit <= 4) {
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    if (pstamp_unit == 3) VG_PSTAMP(10);
-                    cyc0 = __builtin_readcyclecounter();
-                }
-#endif
                 valu_chunk<MODEL, 1, CH, kOut>(intr_r, fr, in, sl, out);
                 if constexpr (CB > 0) valu_chunk<MODEL, 1, CB, kOut>(intr_r, fr, in_b, sl, out);
-#ifdef VG_GRAM_STAMPS
-                if (pstamp_unit <= 4) {
-                    asm volatile("" : "+v"(out[0]));
-                    const unsigned long long dc = __builtin_readcyclecounter() - cyc0;
-                    if (pstamp_unit == 3) VG_PSTAMP(11);
-                    if (pstamps && (threadIdx.x & 63) == 0) pstamps[13] = pstamp_unit == 3 ? (dc & 0xffffffffull) : (pstamps[13] | (dc << 32));
-                }
-#endif
                 // the next pair's observations have had the whole pair to arrive: waiting HERE, in front of this pair's
                 // stores, is free -- at the head of the next pair the same wait would also wait for those stores
                 static_assert(kOut >= 1 && kOut <= 5, "the wait is tied to every entry the stores need");
@@ -728,9 +649,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 else if constexpr (kOut == 3) asm volatile("s_waitcnt vmcnt(0)" : "+v"(out[0]), "+v"(out[1]), "+v"(out[2])::"memory");
                 else if constexpr (kOut == 2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(out[0]), "+v"(out[1])::"memory");
                 else asm volatile("s_waitcnt vmcnt(0)" : "+v"(out[0])::"memory");
-#ifdef VG_GRAM_STAMPS
-                if (pstamp_unit == 3) VG_PSTAMP(12);
-#endif
                 int base = 0, real = E;
                 if constexpr (kPackedOut) {
                     base = (int)((lane_out >> 54) & 0xff);
@@ -771,13 +689,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 }
                 u = u_next;
                 parity ^= 1;
-#ifdef VG_GRAM_STAMPS
-                if (pstamp_unit < 10) { VG_PSTAMP(pstamp_unit); pstamp_unit++; }
-#endif
             }
         }
         __syncthreads();
-        VG_PSTAMP(14);
         if (a.partials) {
             const int tid = threadIdx.x;
             if (tid < E) {
@@ -792,8 +706,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
         const int tid = threadIdx.x;
         if (tid < E) a.partials[(size_t)tid * n_wg + block] = (p_first < p_end) ? wg_sum : 0.;
     }
-    VG_PSTAMP(15);
-#undef VG_PSTAMP
 }
 
 // ------------------------------------------------------------------------------------------

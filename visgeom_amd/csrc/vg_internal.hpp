@@ -24,23 +24,15 @@ int fail(int code, const std::string &msg);
 // vg_debug_set() fails.
 enum DebugHook {
     kHookInlineChainMaxBytes = 0,  // largest evaluation (bytes) whose single-member chain is walked in the emit kernel
-    kHookGramForceMfma,            // single-member chains on the matrix-core Gram kernel as well
-    kHookGramCh1,                  // one corner per lane in the vector-pipe Gram kernel
-    kHookGramNoMerge,              // 1: one Gram launch per dataset; 2: merged launch in dataset order instead of heaviest first
+    kHookGramNoMerge,              // one Gram launch per dataset (the launches a lone dataset takes)
     kHookMaxObsPerLaunch,          // chunk size of the emit launches (the chunked path without a 240 GB problem)
     kHookSolverTiming,             // print where the solver's set-up time goes
     kHookSolverHostLoop,           // force the host-driven LM loop
     kHookSolverDeviceLoop,         // force the device-resident LM loop
-    kHookSolverNoSpeculation,      // queue one LM iteration at a time
-    kHookEmitEqualTiles,           // merged emit launch: contiguous XCD pieces of 1 = equal tile counts, 2 = equal bytes (default: an eighth of every dataset, widest rows first; 4: in problem order)
-    kHookSchurPrivateGather,       // Schur rows kernel: every lane of a pose gathers V_i / g_i itself (the route before round 4), for A/B
-    kHookSolverEventWait,          // device-resident loop: wait for an event behind every accept kernel instead of spinning on its sequence word (A/B)
     kHookSolverNoFoldFrames,       // LM loops: launch the chain prep in front of every candidate evaluation instead of building the candidate's frames in the back-substitution kernel (A/B, bit-equality test)
-    kHookSolverOneWaveFold,        // vg_backsub_solve_kernel: the reduced system by the first wave alone, a row per lane (the route before the entry-parallel L D L^T; A/B)
     kHookSolverFoldMaxGroups,      // largest number of back-substitution workgroups whose launch also solves the reduced system (each workgroup redundantly); beyond: a one-workgroup solve launch in front (0 = the default, kFoldMaxGroups)
     kHookEmitNtMinBytes,           // smallest launch output (bytes) written with non-temporal stores (0 = the default; 1 = always; a huge value = never)
     kHookHostChunkBytes,           // chunk size of vg_dataset_evaluate_to_host in bytes (0 = the default, 32 MiB): tests force many small chunks
-    kHookGramStamps,               // measurement build (-DVG_GRAM_STAMPS) only: device address of the per-wave clock stamps of the Gram kernel
     kHookGramPersistent,           // persistent form of the direct Gram kernel (vg_gram_valu_pers_kernel): 1 = never, 2 / 3 = its four- / eight-wave shape whenever it applies, 0 = by size
     kHookEmitMapWindow,            // tile map of the emit launches: W > 0 = windows of 8 W tiles, XCD x the x-th run of W tiles in each (1 = linear map); -1 = one contiguous eighth per XCD (the map before round 6); 0 = the default (kEmitMapWindow)
     kHookCount

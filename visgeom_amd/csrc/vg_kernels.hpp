@@ -329,9 +329,6 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
             if (const unsigned int f = tid; f < nf) {
                 const long long bi = (long long)b_first + f;
                 const long long si = a.seq_index ? (long long)a.seq_index[bi] : a.first_block + bi;
-#ifdef VG_EMIT_REFERENCE_WALK   // A/B library: the reference-order walk of rounds 1-5 (~300 dependent instructions)
-                build_frame_single_direct(a.chain_params + a.chain_stride * si, fr_lds + f * a.frame_stride_d);
-#else
                 {   // The short walk of the Gram kernels (one sincos at the half angle, R12 = I, M12 from uhat^2 = u u^T - I: the
                     // reference's frame to 1e-16; inside and just above its first-order branches it IS the reference-order
                     // routine).  While <= 4 lanes walk, the tile's other 252 wait at the barrier below with no store in
@@ -342,7 +339,6 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
                     for (int k = 0; k < 6; k++) xi_r[k] = (a.chain_params + a.chain_stride * si)[k];
                     build_frame_single_direct_fast(xi_r, fr_lds + f * a.frame_stride_d);
                 }
-#endif
             }
         } else {
             const int n16 = (int)(nf * (unsigned)a.frame_stride_d) >> 1;
@@ -435,9 +431,9 @@ __global__ __launch_bounds__(kEmitThreads) __attribute__((amdgpu_waves_per_eu(VG
 // works inside one dataset's output arrays at a time and every die gets the same bytes and the same arithmetic whatever the
 // mix of models (a rig's Mei tile writes 1.85 x the bytes of its UCM tile: with one contiguous piece of equal tile count
 // per die, the dies holding the wide datasets finished last -- rig, 591 MB: 116 us against 109 us; profiles/NOTES.md "Merged
-// emit launch").  The earlier cuts (one contiguous piece per die, of equal tile count or equal bytes: xcd_first / xcd_count)
-// stay behind the emit_equal_tiles hook for A/B.  The grid is 8 x the longest piece; surplus workgroups leave at once.  Per-dataset arguments travel by value in the kernel argument segment (no table upload per
-// evaluation); the camera model and the chain route are wave-uniform run-time switches over the same tile routine.
+// emit launch").  The grid is 8 x the sum of the datasets' longest eighths; surplus workgroups leave at once.  Per-dataset
+// arguments travel by value in the kernel argument segment (no table upload per evaluation); the camera model and the chain
+// route are wave-uniform run-time switches over the same tile routine.
 // ------------------------------------------------------------------------------------------
 constexpr int kEmitMultiMax = 8;
 
@@ -447,8 +443,6 @@ struct EmitMultiArgs {
     int model[kEmitMultiMax];
     int inline_chain[kEmitMultiMax];
     int n;
-    unsigned int xcd_first[8], xcd_count[8];   // tiles of XCD x: [xcd_first[x], xcd_first[x] + xcd_count[x])
-    int per_dataset;                           // 1: XCD x takes the x-th eighth of EVERY dataset, dataset after dataset
 };
 
 template <int MODEL>
@@ -464,21 +458,15 @@ __global__ __launch_bounds__(kEmitThreads) __attribute__((amdgpu_waves_per_eu(VG
     const unsigned int x = blockIdx.x & 7u;   // workgroup b runs on XCD b % 8 (observed dispatch order)
     unsigned int j = blockIdx.x >> 3, t;
     int d = 0;
-    if (m.per_dataset) {
-        for (;; d++) {
-            if (d == m.n) return;
-            const unsigned int nt = m.first_tile[d + 1] - m.first_tile[d], q = nt >> 3, r = nt & 7u, cnt = q + (x < r ? 1u : 0u);
-            if (j < cnt) {
-                const unsigned int W = m.ds[d].map_window;   // XCD x's j-th tile of this dataset
-                t = m.first_tile[d] + (W ? xcd_window_block(j * 8u + x, nt, W) : x * q + (x < r ? x : r) + j);
-                break;
-            }
-            j -= cnt;
+    for (;; d++) {
+        if (d == m.n) return;
+        const unsigned int nt = m.first_tile[d + 1] - m.first_tile[d], q = nt >> 3, r = nt & 7u, cnt = q + (x < r ? 1u : 0u);
+        if (j < cnt) {
+            const unsigned int W = m.ds[d].map_window;   // XCD x's j-th tile of this dataset
+            t = m.first_tile[d] + (W ? xcd_window_block(j * 8u + x, nt, W) : x * q + (x < r ? x : r) + j);
+            break;
         }
-    } else {
-        if (j >= m.xcd_count[x]) return;
-        t = m.xcd_first[x] + j;
-        while (d + 1 < m.n && t >= m.first_tile[d + 1]) d++;
+        j -= cnt;
     }
     const unsigned int o0 = (t - m.first_tile[d]) * (unsigned)kEmitThreads;
     const bool inl = m.inline_chain[d] != 0;

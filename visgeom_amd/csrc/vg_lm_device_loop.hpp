@@ -18,7 +18,7 @@
 // so every rank queues the same launches and the same collectives; a collective of an iteration that skips itself is NOT
 // skipped -- it runs on every rank, on buffers nobody reads (whatever a real iteration reads it has rewritten or cleared before
 // its own collective).  Replaying the gated iteration as a hipGraph (one per parity) was slower than queueing its launches
-// (profiles/NOTES.md).  vg_debug_set("solver_no_speculation", 1) queues one iteration at a time.
+// (profiles/NOTES.md).
 #pragma once
 
 namespace {
@@ -33,25 +33,22 @@ struct LmSolve::DeviceLoop {
     vg::LmAcceptArgs aa;
     vg::LmSolveArgs ra;
     size_t accept_lds = 0, solve_lds = 0;
-    bool speculate = false, spin_wait = true;
+    bool speculate = false;
     DevBuf<double> *gset[2] = {nullptr, nullptr};
     vg::SolveDatasetDev *dset[2] = {nullptr, nullptr};
     double *xbuf[2] = {nullptr, nullptr};
     // The accept kernel writes its state into a pinned slot itself and a per-slot SEQUENCE WORD behind it (system-scope release);
     // the host learns the outcome of an iteration by SPINNING on that word -- not from an event recorded behind the kernel: the
     // event's marker packet kept the next iteration's first kernel waiting 5-6 us after every accept (rocprofv3 trace,
-    // tools/exp/trace_gaps.py).  vg_debug_set("solver_event_wait", 1) restores the event (A/B).
+    // tools/exp/trace_gaps.py).
     struct Slots {
         vg::LmState *p = nullptr;
         volatile unsigned long long *seq = nullptr;   // pinned, behind the states: what the accept kernel of a slot wrote last
         unsigned long long expect[kSlots] = {};
         bool owned = false;
-        hipEvent_t ev[kSlots] = {};
         ~Slots()
         {
             if (p && owned) (void)hipHostFree(p);
-            for (auto e : ev)
-                if (e) (void)hipEventDestroy(e);
         }
     } slots;
     unsigned long long seq_counter = 0ull;
@@ -63,23 +60,12 @@ struct LmSolve::DeviceLoop {
     void arm_slot(int slot, vg::LmAcceptArgs &args)
     {
         args.host_state = slots.p + slot;
-        if (spin_wait) {
-            slots.expect[slot] = ++seq_counter;
-            args.host_seq = const_cast<unsigned long long *>(slots.seq + slot);
-            args.seq = slots.expect[slot];
-        }
-    }
-    int queue_state(int slot)
-    {
-        if (!spin_wait) VG_HIP(hipEventRecord(slots.ev[slot], s.st));
-        return VG_OK;
+        slots.expect[slot] = ++seq_counter;
+        args.host_seq = const_cast<unsigned long long *>(slots.seq + slot);
+        args.seq = slots.expect[slot];
     }
     int wait_state(int slot)
     {
-        if (!spin_wait) {
-            VG_HIP(hipEventSynchronize(slots.ev[slot]));
-            return VG_OK;
-        }
         return s.spin_until(slots.seq + slot, slots.expect[slot], "the accept kernel of an LM iteration never reported");
     }
 
@@ -163,7 +149,7 @@ struct LmSolve::DeviceLoop {
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * vg::lm_entry_solve_lds_doubles(G))));
         aa.gate_expect = -1;
         ra.gate_expect = -1;
-        speculate = opt.soft_l1_scale <= 0. && vgi::debug_hook(vgi::kHookSolverNoSpeculation) != 1;
+        speculate = opt.soft_l1_scale <= 0.;
         gset[0] = s.gramA;
         gset[1] = s.gramB;
         dset[0] = s.d_dsA.p;
@@ -178,9 +164,6 @@ struct LmSolve::DeviceLoop {
         }
         slots.seq = reinterpret_cast<volatile unsigned long long *>(slots.p + kSlots);
         for (int k = 0; k < kSlots; k++) slots.seq[k] = 0ull;
-        spin_wait = !vgi::debug_hook(vgi::kHookSolverEventWait);
-        if (!spin_wait)
-            for (auto &e : slots.ev) VG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         return VG_OK;
     }
 
@@ -200,7 +183,7 @@ struct LmSolve::DeviceLoop {
         sa.gate_expect = par;
         if (s.n_poses) {
             // rows of every pose + the Gram of the rows, one launch; then ONE fixed-order sum over the workgroups
-            hipLaunchKernelGGL(vg::vg_schur_rows_gram_kernel, dim3(s.sg_wgs), dim3(vg::kSchurThreads * s.sg_batches), s.sg_lds, st, sa, s.sg_ppw, s.sg_batches, s.d_rgroups.p, s.sg_shared);
+            hipLaunchKernelGGL(vg::vg_schur_rows_gram_kernel, dim3(s.sg_wgs), dim3(vg::kSchurThreads * s.sg_batches), s.sg_lds, st, sa, s.sg_ppw, s.sg_batches, s.d_rgroups.p);
             VG_HIP(hipGetLastError());
             vg::launch_strided_sum(st, s.d_rgroups.p, s.sg_wgs, C * C + 1, s.d_rgram.p);  // the Gram and the count of bad pose blocks
             VG_HIP(hipGetLastError());
@@ -242,7 +225,6 @@ struct LmSolve::DeviceLoop {
             const unsigned int bs_grid = s.n_bs_groups ? s.n_bs_groups : 1u;
             if (fold_solve) {
                 r2.S = nullptr;  // the damped matrix in every workgroup's own LDS
-                r2.one_wave = vgi::debug_hook(vgi::kHookSolverOneWaveFold) ? 1 : 0;
                 // kJ = columns per lane of a pose's 16-lane group: 1 up to 15 global columns (every mono problem), 2 up to 31
                 const size_t fold_lds = sizeof(double) * std::max(vg::lm_entry_solve_lds_doubles(G), 2 * (size_t)G * G + 4 * (size_t)G + 2);
                 const bool fr = ba.fold != nullptr;   // the instantiation that also builds the candidate's frames
@@ -268,7 +250,7 @@ struct LmSolve::DeviceLoop {
         arm_slot(slot, a2);
         hipLaunchKernelGGL(vg::vg_lm_accept_kernel, dim3(1), dim3(vg::kLmThreads), accept_lds, st, a2);
         VG_HIP(hipGetLastError());
-        return queue_state(slot);
+        return VG_OK;
     }
 
     // the iterations: queue ahead, wait for the state of the iteration in flight, decide what the queue holds next
@@ -281,12 +263,10 @@ struct LmSolve::DeviceLoop {
         // closed-gate kernels (27 us at 10 k images, in front of the copy of the result: 5 % of the solve).  LM converges
         // quadratically at the tail, so once the last known step changed the cost by less than 1e-9 of it the iteration in flight
         // is the last or the one before it; not speculating past it costs one launch latency (~8 us) if it was not.
-        // (vg_debug_set("solver_no_speculation", 2): always speculate, for A/B.)
-        const bool always_speculate = vgi::debug_hook(vgi::kHookSolverNoSpeculation) == 2;
         double last_rel_change = 1.;
         for (iter = 1; iter <= opt.max_num_iterations; iter++) {
             int spec = -1;
-            const bool near_end = !always_speculate && last_rel_change <= 1e-9;
+            const bool near_end = last_rel_change <= 1e-9;
             if (speculate && !near_end && iter < opt.max_num_iterations) VG_TRY(queue_iteration(parity ^ 1, true, spec));
             VG_TRY(wait_state(pending));  // the one wait of the iteration; the GPU already holds the next one
             const vg::LmState &S = slots.p[pending];
@@ -326,7 +306,6 @@ struct LmSolve::DeviceLoop {
         VG_HIP(hipGetLastError());
         aa.init = 0;
         if (opt.max_num_iterations >= 1) VG_TRY(queue_iteration(parity, speculate, pending));
-        else VG_TRY(queue_state(pending));
         VG_TRY(iterate(iter, parity, pending));
         VG_TRY(wait_state(pending));
         s.x_cur = xbuf[parity];       // the DevBuf handles keep their own buffers; the solve's current point is x_cur

@@ -101,12 +101,12 @@ struct LmSolve::HostLoop {
         const bool rgram_in_place = s.host_direct && s.n_poses > 0;
         if (!rgram_in_place) std::fill(s.h_rgram.begin(), s.h_rgram.end(), 0.);
         q.rg = rgram_in_place ? s.pin_rgram.p : s.h_rgram.data();
-        const bool schur_spin = s.host_spin && s.n_poses > 0 && s.coupled.empty();
+        const bool schur_spin = rgram_in_place;   // the strided sum below signals the host (host_direct: no coupled sequences)
         q.coupled_ok = true;
         if (s.n_poses) {
             if (s.coupled.empty()) {
                 sa.zero_u64 = s.d_gmax;  // the step's max |g_pose|, cleared here instead of by a memset in front of the back-substitution
-                hipLaunchKernelGGL(vg::vg_schur_rows_gram_kernel, dim3(s.sg_wgs), dim3(vg::kSchurThreads * s.sg_batches), s.sg_lds, st, sa, s.sg_ppw, s.sg_batches, s.d_rgroups.p, s.sg_shared);
+                hipLaunchKernelGGL(vg::vg_schur_rows_gram_kernel, dim3(s.sg_wgs), dim3(vg::kSchurThreads * s.sg_batches), s.sg_lds, st, sa, s.sg_ppw, s.sg_batches, s.d_rgroups.p);
             } else {
                 VG_HIP(hipMemsetAsync(s.d_bad, 0, sizeof(double), st));
                 hipLaunchKernelGGL(vg::vg_schur_rows_kernel, dim3((unsigned)((s.n_poses * C + 255) / 256)), dim3(256), 0, st, sa);

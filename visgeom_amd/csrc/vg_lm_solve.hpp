@@ -50,7 +50,7 @@ struct LmSolve {
     std::vector<double> glo, ghi;                  // box bounds of the global columns (intrinsics only)
     std::vector<CoupledSeq> coupled;               // sequences coupled by odometry blocks / unary priors: host elimination
     const vg_comm *comm = nullptr;
-    bool multi_rank = false, coupled_multi = false, device_loop = false, host_direct = false, host_spin = false;
+    bool multi_rank = false, coupled_multi = false, device_loop = false, host_direct = false;
 
     // per dataset: local -> global column map, pose column offset, pose references (CSR over the poses)
     std::vector<std::vector<int>> lmap;
@@ -60,7 +60,7 @@ struct LmSolve {
 
     // ------------------------------------------------------------------------------------------ launch geometry
     unsigned int n_rows = 0, rows_per_group = 96, n_groups = 0, n_slabs = 0, sg_wgs = 0, n_bs_groups = 0;
-    int sg_ppw = 1, sg_batches = 1, sg_shared = 1;
+    int sg_ppw = 1, sg_batches = 1;
     size_t sg_lds = 0, n_sums = 0, n_pack = 0;
 
     // ------------------------------------------------------------------------------------------ memory (the arena first: it is released last)
@@ -335,7 +335,6 @@ struct LmSolve {
         while (sg_batches > 1 && sizeof(double) * (size_t)sg_batches * sg_ppw * (6 * (G + 2) + 28) + 24 * (size_t)vg::kSchurMaxRefs > 64 * 1024) sg_batches--;   // two 1024-thread workgroups fill a CU: 64 KB each is free
         // + V_i | g_i of every pose of the workgroup, gathered once and shared by the pose's lanes (28 doubles per pose)
         sg_lds = sizeof(double) * ((size_t)sg_batches * sg_ppw * 6 * (G + 2) + (size_t)sg_batches * sg_ppw * 28) + 24 * (size_t)vg::kSchurMaxRefs;
-        sg_shared = vgi::debug_hook(vgi::kHookSchurPrivateGather) ? 0 : 1;   // A/B hook: every lane gathers for itself
         if (sg_lds > 48 * 1024)
             VG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vg::vg_schur_rows_gram_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg_lds));
         sg_wgs = (unsigned int)((n_poses + (int64_t)sg_ppw * sg_batches - 1) / ((int64_t)sg_ppw * sg_batches));
@@ -462,9 +461,7 @@ struct LmSolve {
         // (tools/exp/host_wait.hip).  The strided sum of the pose elimination (133 workgroups at G = 45) stores it when its last
         // workgroup is done (vg::HostSignal); behind an evaluation, whose last launch has 800 workgroups at the rig's size (an atomic
         // each cost more than the wait saves), a one-thread kernel does.  Rig, same box: 0.163-0.170 -> 0.157-0.158 ms per iteration.
-        // vg_debug_set("solver_event_wait", 1): the runtime's wait (A/B).
-        host_spin = host_direct && !vgi::debug_hook(vgi::kHookSolverEventWait);
-        if (host_spin) {
+        if (host_direct) {
             VG_TRY(pin_seq.alloc(2));
             VG_TRY(d_sigcnt.alloc(2));
             init.add_zero(reinterpret_cast<double *>(d_sigcnt.p), 1);   // two 32-bit counters
@@ -668,7 +665,7 @@ struct LmSolve {
     {
         const double t0 = now_s();
         int r;
-        const bool spin = host_spin;   // a one-thread kernel behind the evaluation reports (see host_spin)
+        const bool spin = host_direct;   // a one-thread kernel behind the evaluation reports (see setup_device_state)
         r = enqueue_evaluate(x_dev, set, frames_ready, step_scalars, gmax_out);
         if (r != VG_OK) return r;
         if (spin) {

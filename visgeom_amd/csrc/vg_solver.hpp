@@ -217,15 +217,10 @@ constexpr int kSchurLdsDatasets = 32;  // dataset descriptors kept in LDS (reque
 
 #ifdef VG_TU_SOLVER  // this kernel is launched by one translation unit only; the others see the header without it
 __global__ __launch_bounds__(kSchurThreads * kSchurMaxBatches) void vg_schur_rows_gram_kernel(SchurArgs a, int poses_per_wg, int batches,
-                                                                            double *__restrict__ partials /* [n_wg][C*C + 1] */,
-                                                                            int shared_gather)
+                                                                            double *__restrict__ partials /* [n_wg][C*C + 1] */)
 {
     extern __shared__ __attribute__((aligned(16))) double sm_rows[];  // [batches * poses_per_wg * 6][C + 1] (odd-ish stride)
-#ifdef VG_SCHUR_EVEN_STRIDE   // A/B library: the stride before round 6
-    const int C = a.G + 1, CS = C + 1, tid = threadIdx.x % kSchurThreads;
-#else
     const int C = a.G + 1, CS = C | 1, tid = threadIdx.x % kSchurThreads;   // odd row stride (the LDS is sized for C + 1): with C = 7 a stride of 8 doubles put every fourth row on the same banks
-#endif
     const int pl = tid / C, gcol = tid - pl * C;        // pose of the batch, column
     const bool lane_on = pl < poses_per_wg;
     // every batch has its own 256 lanes (blockDim.x = kSchurThreads * batches): the chains pose -> reference list -> Gram
@@ -271,7 +266,7 @@ __global__ __launch_bounds__(kSchurThreads * kSchurMaxBatches) void vg_schur_row
         int W, o, d, pad;
     };
     RefMeta *sm_ref = reinterpret_cast<RefMeta *>(sm_V + (size_t)batches * poses_per_wg * 28);   // [kSchurMaxRefs]
-    const bool meta_lds = shared_gather && q_end - q_first <= kSchurMaxRefs;
+    const bool meta_lds = q_end - q_first <= kSchurMaxRefs;
     if (meta_lds) {
         for (int t = threadIdx.x; t < q_end - q_first; t += blockDim.x) {
             const int d = a.ref_ds[q_first + t];
@@ -321,48 +316,42 @@ __global__ __launch_bounds__(kSchurThreads * kSchurMaxBatches) void vg_schur_row
     // triangle, then g) over the pose's references in order and parks it in LDS; every lane then reads the 27 values back.
     // (Each of the C lanes used to walk the whole gather itself -- 27 loads per reference and lane.)  Same order of additions:
     // same bits.
-    if (shared_gather) {
-        if (pose_on) {
-            double *Vs = sm_V + (size_t)(bt * poses_per_wg + pl) * 28;
-            for (int e = gcol; e < 27; e += C) {
-                int r, c;   // entry e: (r, c) of the packed lower triangle, or (e - 21, residual column)
-                if (e < 21) {
-                    r = 0;
+    if (pose_on) {
+        double *Vs = sm_V + (size_t)(bt * poses_per_wg + pl) * 28;
+        for (int e = gcol; e < 27; e += C) {
+            int r, c;   // entry e: (r, c) of the packed lower triangle, or (e - 21, residual column)
+            if (e < 21) {
+                r = 0;
 #pragma unroll
-                    for (int k = 1; k < 6; k++) r += e >= k * (k + 1) / 2 ? 1 : 0;
-                    c = e - r * (r + 1) / 2;
-                } else {
-                    r = e - 21;
-                    c = -1;
-                }
-                double v = 0.;
-                for (int q = r0; q < r1; q++) {
-                    const double *Gb;
-                    int W, o, d;
-                    ref_of(q, Gb, W, o, d);
-                    v += Gb[(o + r) * W + (c < 0 ? W - 1 : o + c)];
-                }
-                Vs[e] = v;
+                for (int k = 1; k < 6; k++) r += e >= k * (k + 1) / 2 ? 1 : 0;
+                c = e - r * (r + 1) / 2;
+            } else {
+                r = e - 21;
+                c = -1;
             }
-            if (gcol == 0) Vs[27] = r1 > r0 ? 1. : 0.;
+            double v = 0.;
+            for (int q = r0; q < r1; q++) {
+                const double *Gb;
+                int W, o, d;
+                ref_of(q, Gb, W, o, d);
+                v += Gb[(o + r) * W + (c < 0 ? W - 1 : o + c)];
+            }
+            Vs[e] = v;
         }
-        __syncthreads();
+        if (gcol == 0) Vs[27] = r1 > r0 ? 1. : 0.;
     }
+    __syncthreads();
     {
         double y[6] = {0., 0., 0., 0., 0., 0.};
         if (pose_on) {
             PoseFactor f;
-            if (shared_gather) {
-                const double *Vs = sm_V + (size_t)(bt * poses_per_wg + pl) * 28;
-                double V[21];
+            const double *Vs = sm_V + (size_t)(bt * poses_per_wg + pl) * 28;
+            double V[21];
 #pragma unroll
-                for (int k = 0; k < 21; k++) V[k] = Vs[k];
+            for (int k = 0; k < 21; k++) V[k] = Vs[k];
 #pragma unroll
-                for (int k = 0; k < 6; k++) f.gp[k] = Vs[21 + k];
-                pose_factor_from(a, pose_mode, mu_now, V, Vs[27] != 0., f);
-            } else {
-                pose_factor(a, i, f);
-            }
+            for (int k = 0; k < 6; k++) f.gp[k] = Vs[21 + k];
+            pose_factor_from(a, pose_mode, mu_now, V, Vs[27] != 0., f);
             if (gcol >= a.G) {
 #pragma unroll
                 for (int c = 0; c < 6; c++) w[c] = f.gp[c];

@@ -76,7 +76,6 @@ struct LmSolveArgs {
     int G, use_bounds;
     int gate_expect;                   // run only if st->gate == gate_expect (-1: no test)
     double dmin, dmax;
-    int one_wave = 0;                  // vg_backsub_solve_kernel: the first wave alone, a row per lane (the route before round 4; A/B hook)
 };
 
 constexpr int kLmThreads = 256;
@@ -200,7 +199,7 @@ __global__ __launch_bounds__(kLmThreads) void vg_lm_reduced_solve_kernel(LmSolve
 // once-updated column j + 1 that every thread forms for its own rows; one barrier per step, no square root, no division.
 // Then x_j = (z_j - sum_{i > j} A_ij x_i) / d_j from the last column up in the first wave (v_readlane broadcasts,
 // reciprocals taken in parallel beforehand).
-// History (G = 45, one active-set pass; rocprofv3 in the rig's loop / tools/exp/solve_kernel_probe.hip): a row per lane
+// History (G = 45, one active-set pass; rocprofv3 in the rig's loop / profiles/NOTES.md "The rig's loop (G = 45)"): a row per lane
 // (lm_reduced_solve_body) 107 us; entry-parallel Cholesky with scaled columns, 256 threads (sqrt + division + two barriers per
 // column) 40.9 us; L D L^T, one barrier per column, LDS reads of a step batched 34 us; 1024 threads 24 us; two columns per
 // step 22 us.  What is left is 22 steps of ~1 500 cycles: a 16-wave barrier (~400), the LDS round trip in front of it and a
@@ -209,7 +208,7 @@ __global__ __launch_bounds__(kLmThreads) void vg_lm_reduced_solve_kernel(LmSolve
 // to rounding, which is what tests/test_gpu_solve.py::test_wide_system_on_the_device_resident_loop holds them to.
 constexpr int kEntrySolveMaxG = 63;
 constexpr int kEntryThreads = 1024;   // 16 waves, two entries per thread at G = 45: with 256 threads (five entries each, nine slots in the code) a column
-                                      // step was ~150 instructions of ONE wave per SIMD, 1 300 cycles (tools/exp/solve_kernel_probe.hip)
+                                      // step was ~150 instructions of ONE wave per SIMD, 1 300 cycles (profiles/NOTES.md "The rig's loop (G = 45)")
 constexpr int kEntrySolveSlots = ((kEntrySolveMaxG + 1) * (kEntrySolveMaxG + 2) / 2 + kEntryThreads - 1) / kEntryThreads;   // 3
 
 __device__ __forceinline__ double readlane_f64(double v, int lane /* uniform */)
@@ -247,19 +246,6 @@ __host__ __device__ inline size_t lm_entry_solve_lds_doubles(int G)
     const size_t C = (size_t)G + 1;
     return 2 * C * (size_t)lm_entry_solve_stride(G) + C * (C + 1) / 2 + 2 * (size_t)G + 2;
 }
-
-// -DVG_SOLVE_STAMPS (tools/exp/solve_kernel_probe.hip only): thread 0 stores the shader clock at the phase boundaries through
-// a.S, which this kernel does not use otherwise
-#ifdef VG_SOLVE_STAMPS
-#define VG_SOLVE_STAMP(i)                                                                  \
-    do {                                                                                   \
-        if (threadIdx.x == 0 && a.S) reinterpret_cast<long long *>(a.S)[i] = (long long)clock64(); \
-    } while (0)
-#else
-#define VG_SOLVE_STAMP(i) \
-    do {                  \
-    } while (0)
-#endif
 
 // The solve itself, by ALL kT threads of a workgroup (kSlots entries per thread at most); returns where the step lies in LDS;
 // `publish`: also to a.dg / st->step_ok.  Used by the stand-alone kernel below (1024 threads, up to 63 columns) and by
@@ -320,7 +306,6 @@ __device__ __forceinline__ double *lm_entry_solve_body(const LmSolveArgs &a, dou
         }
     }
     __syncthreads();
-    VG_SOLVE_STAMP(1);
     bool ok = true;
     for (int pass = 0; pass <= G; pass++) {
         // constant blocks and the active set of the box bounds leave the system (unit row / column, zero right-hand side)
@@ -333,9 +318,8 @@ __device__ __forceinline__ double *lm_entry_solve_body(const LmSolveArgs &a, dou
         }
         if (tid == 0) flag[0] = 0.;
         __syncthreads();
-        VG_SOLVE_STAMP(2 + 3 * (pass < 2 ? pass : 2));
         ok = true;
-        // TWO columns per step (a barrier and two LDS round trips per step are most of its ~950 cycles, tools/exp/solve_kernel_probe.hip):
+        // TWO columns per step (a barrier and two LDS round trips per step are most of its ~950 cycles, profiles/NOTES.md "The rig's loop (G = 45)"):
         // with the pivots d0 = A_jj, b = A_j+1,j, d1 = A_j+1,j+1 - b^2 / d0 every thread forms the once-updated column j + 1 of its rows
         // itself (a_i1 = A_i,j+1 - A_ij b / d0) and subtracts both columns' products.  The final column j + 1 goes to a second
         // array F (other threads still read its old values in A during the step): odd columns of the factor live in F.
@@ -385,7 +369,6 @@ __device__ __forceinline__ double *lm_entry_solve_body(const LmSolveArgs &a, dou
             const double d = A[j * P + j];
             if (!(d > 0.) || !isfinite(d)) ok = false;
         }
-        VG_SOLVE_STAMP(3 + 3 * (pass < 2 ? pass : 2));
         // D L~^T x = z (row G) from the last column up: first wave, the running right-hand side in registers; lane t holds
         // column t (odd columns: in F)
         if (tid < kWave) {
@@ -411,7 +394,6 @@ __device__ __forceinline__ double *lm_entry_solve_body(const LmSolveArgs &a, dou
             if (tid == 0) flag[1] = ok ? 1. : 0.;   // the first wave saw every pivot
         }
         __syncthreads();
-        VG_SOLVE_STAMP(4 + 3 * (pass < 2 ? pass : 2));
         if (flag[0] == 0. || flag[1] == 0.) break;
         __syncthreads();   // everybody has read the flag before the next pass clears it
     }
@@ -419,7 +401,6 @@ __device__ __forceinline__ double *lm_entry_solve_body(const LmSolveArgs &a, dou
         if (tid < G) a.dg[tid] = x[tid];
         if (tid == 0) st->step_ok = (G == 0 || ok) ? 1 : 0;
     }
-    VG_SOLVE_STAMP(11);
     return x;
 }
 
@@ -428,7 +409,6 @@ __global__ __launch_bounds__(kEntryThreads) void vg_lm_reduced_solve_entries_ker
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     LmState *st = a.st;
-    VG_SOLVE_STAMP(0);
     if (st->done || (a.gate_expect >= 0 && st->gate != a.gate_expect)) return;
     lm_entry_solve_body<kEntryThreads, kEntrySolveSlots>(a, sm, true);
 }
@@ -450,15 +430,9 @@ __global__ __launch_bounds__(kBsThreads) void vg_backsub_solve_kernel(BacksubArg
     LmState *st = a.st;
     if (st->done || (a.gate_expect >= 0 && st->gate != a.gate_expect)) return;
     if (gate_closed(b.s.gate, b.s.gate_expect)) return;
-    // (round 4: the entry-parallel L D L^T on all 256 threads; before, the first wave alone with a row per lane -- 17 of the
-    //  stereo problem's 33.7 us in this kernel at G = 18)
-    const double *step;
-    if (a.one_wave) {
-        if (threadIdx.x < kWave) lm_reduced_solve_body(a, sm, threadIdx.x, kWave, blockIdx.x == 0);
-        step = sm + (size_t)a.G * a.G + 2 * a.G;
-    } else {
-        step = lm_entry_solve_body<kBsThreads, kFoldSlots>(a, sm, blockIdx.x == 0);
-    }
+    // G = 0 has no reduced system (an empty step); the host folds only G > 0.  The uniform test also keeps the loads of b's
+    // kernel arguments behind the solve: without a branch around it they were hoisted in front of it and spilled SGPRs.
+    const double *step = a.G > 0 ? lm_entry_solve_body<kBsThreads, kFoldSlots>(a, sm, blockIdx.x == 0) : sm;
     __syncthreads();
     backsub_body<kJ, kFrames>(b, step);
 }
@@ -484,7 +458,7 @@ struct LmAcceptArgs {
     int gate_expect;                   // run only if st->gate == gate_expect (-1: no test)
     // the host does not wait for an event behind this kernel (a marker packet in the stream: 5-6 us before the next iteration's
     // first kernel starts, rocprofv3 trace) but spins on host_seq: written with system-scope release AFTER the state
-    unsigned long long *host_seq = nullptr;   // pinned; NULL: the host waits for an event (A/B hook)
+    unsigned long long *host_seq = nullptr;   // pinned; NULL: no sequence word
     unsigned long long seq = 0;               // the value this launch leaves there
     LmState *host_state;               // pinned host memory (device-visible): the state after this call, for the host's
                                        //   decisions -- written by the kernel itself: a copy command between two kernels of
