@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- corner residual + Jacobian evaluations per second on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: one rank per GPU.  Launched bare, bench.py re-executes itself through `python -m torch.distributed.run
    --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`; launched by torch.distributed.run it reads RANK / WORLD_SIZE.)
 
@@ -13,7 +13,11 @@ One step = one full evaluation of the hot path at the current parameters (vg_pro
   the Ceres block layout.  For this single-member DIRECT chain the emit kernel derives the per-image frames itself,
   so the step is ONE launch; multi-member chains and the Gram kernels use the separate chain-prep kernel.
 Inputs are resident in HBM before the timed region.  Multi-GPU: images are sharded over ranks
-(weak scaling, no data-path collective in this pass).  The normal-equation build that needs the exchange step is
+(weak scaling, no data-path collective in this pass).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline fields.  Everything else
+runs with --full only: the roofline of the step's kernel, the CPU baseline, the other configurations and sizes, and the
+solves.  With --full, the normal-equation build that needs the exchange step is
 reported under "jtj" (same weak-scaled set) and under "sharded_mei" (BASELINE.json config 4: Mei, 10 000 images x 96
 corners in TOTAL, split over the N ranks -- strong scaling; one iteration = fused J^T J + ONE packed in-place RCCL
 all-reduce of [H | g | cost | n_failed] on the device buffer through the native vg_comm entry), and the full LM solves
@@ -45,6 +49,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--images", type=int, default=10000, help="images per GPU")
     ap.add_argument("--model", default="eucm", choices=["eucm", "ucm", "mei"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other section too (roofline, jtj, sharded and full solves, the other "
+                         "configurations and sizes, pcie_inclusive, calib_e2e, pose_init, cpu_baseline); --sharded-images, "
+                         "--sharded-solve-images, --no-cpu-baseline, --no-secondary-configs, --headline-kernels-only and "
+                         "--cpu-seconds shape these sections and apply only with --full")
     ap.add_argument("--sharded-images", type=int, default=10000, help="total images of the sharded Mei case (config 4)")
     ap.add_argument("--sharded-solve-images", type=int, default=100000,
                     help="total images of the large sharded LM solve (0: skip)")
@@ -296,9 +305,9 @@ def main():
 
     # the native RCCL communicator (vg_comm): the normal-equation blocks are reduced through it, on the device buffers.
     # torch.distributed only carries the unique id and the fences; with the gloo rehearsal backend (several ranks on ONE
-    # GPU, which RCCL refuses) the blocks go through torch instead.
+    # GPU, which RCCL refuses) the blocks go through torch instead.  Only the --full sections use it.
     comm = None
-    if dist is not None and backend == "nccl":
+    if a.full and dist is not None and backend == "nccl":
         from visgeom_amd import distributed as vdist_
 
         # created in a helper thread with a deadline and agreed on by all ranks: if the native communicator cannot be
@@ -452,13 +461,29 @@ def main():
                    "images_per_gpu": n_img, "corners_per_image": N, "camera_model": a.model, "chain": ["DIRECT"],
                    "seed": int(d["seed"]), "sharding": "images sharded over ranks, no data-path collective"},
     }
+
+    import threading
+
+    secondary_done = threading.Event()   # set once the --full sections are through (the deadline below waits on it)
+
+    def close_and_print():
+        p.close()
+        if comm is not None:
+            comm.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        secondary_done.set()
+        if rank == 0:
+            print(json.dumps(out))
+
+    if not a.full:
+        close_and_print()
+        return
+
     # The secondary sections with several ranks contain collectives that have never run on more than one GPU in this
     # project's own sessions.  A deadline keeps the headline: if they are not through in time, rank 0
     # prints the line with what is finished and every rank leaves.
-    import threading
-
-    secondary_done = threading.Event()
-
     def _deadline():
         limit = float(os.environ.get("VG_BENCH_SECONDARY_TIMEOUT", "420" if world > 1 else "1500"))
         if secondary_done.wait(limit):
@@ -979,15 +1004,7 @@ def main():
         ex = out["cpu_baseline"].get("extrapolated_all_physical_cores")
         if ex:   # the same ratio against every physical core of the host, by linear extrapolation of the measured per-thread rate
             out["gpu_over_cpu_extrapolated_all_physical_cores"] = value / ex["value"]
-    p.close()
-    if comm is not None:
-        comm.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    secondary_done.set()
-    if rank == 0:
-        print(json.dumps(out))
+    close_and_print()
 
 
 if __name__ == "__main__":

@@ -249,6 +249,20 @@ def test_bench_starts_its_own_ranks(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_runs_the_secondary_sections_only_with_full(monkeypatch):
+    """a plain `bench.py --gpus 1 --steps K --warmup W` measures the headline alone; every other section needs --full"""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and (a.steps, a.warmup, a.gpus) == (7, 2, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--full"])
+    assert bench.parse().full is True
+
+
 def test_odometry_cost_host_block_matches_oracle(lib):
     """vg_odometry_cost_evaluate (host arithmetic, no GPU): OdometryCost with parameter blocks (xi1[6], xi2[6],
     [radius_left, radius_right, track_gauge]) (odometry_cost_function.cpp:147-266) against the C restatement, which

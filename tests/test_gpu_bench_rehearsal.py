@@ -8,6 +8,7 @@ communicator set-up.
   RCCL, 1 rank    `VG_BENCH_FORCE_DIST=1` under torch.distributed.run with one process: init_process_group("nccl"),
                   vg_comm_unique_id -> broadcast -> vg_comm_create (ncclCommInitRank) in the helper thread, the gloo side-group
                   agreement, the all-reduces of the sections through the native communicator.
+Every section runs with --full; a plain run prints the headline fields alone.
 Sizes are cut down (the code paths, not the numbers, are under test)."""
 import json
 import os
@@ -20,7 +21,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--images", "500", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.2", "--sharded-images", "600",
+SMALL = ["--full", "--images", "500", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.2", "--sharded-images", "600",
          "--sharded-solve-images", "1500"]
 SECTIONS = ("roofline", "jtj", "sharded_mei", "sharded_solve", "solve", "pcie_inclusive", "config3_stereo", "config5_rig", "eucm_100k",
             "emit_sweep", "calib_e2e", "pose_init")
@@ -55,6 +56,28 @@ def check_sections(line):
             assert rf["frac"] > 0 and rf["avg_launch_ms"] > 0 and rf["kernel"].startswith("vg_")
         assert line[k]["solve"]["iterations"] >= 1
     assert line["eucm_100k"]["roofline"]["bound"] == "hbm"
+
+
+HEADLINE = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data", "library", "config")
+
+
+def test_plain_run_prints_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """without --full: set-up, warm-up, the K timed steps, the dump and the headline fields -- no other section, no
+    communicator, no CPU baseline"""
+    import numpy as np
+
+    line, err = run([sys.executable, "bench.py", "--gpus", "1", "--images", "500", "--steps", "3", "--warmup", "1",
+                     "--dump-outputs", str(tmp_path)], {})
+    assert list(line) == list(HEADLINE), list(line)
+    assert line["metric"] == "corner residual+Jacobian evals/sec" and line["unit"] == "evals/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["steps"] == 3 and line["warmup"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["config"]["images_per_gpu"] == 500
+    assert abs(line["value"] - 500 * 96 * 1e3 / line["ms_per_step"]) <= 1e-9 * line["value"]
+    assert "native RCCL communicator" not in err
+    res = np.load(tmp_path / "residuals.npy")
+    assert res.shape == (500, 192) and np.all(np.isfinite(res))
+    assert np.array_equal(np.load(tmp_path / "image_index.npy"), np.arange(500.0))
 
 
 @pytest.fixture(scope="module")

@@ -47,7 +47,7 @@ def markdown(rows, poses, tag):
             out.append("| %s | %.3f | %.1f / %.0f / %d | %d | %.3g |" % (
                 r["workload"].split(",")[0] + "," + r["workload"].split(",")[1], r["refine_call_ms"], r["iterations_mean"],
                 r["iterations_p99"], r["iterations_max"], r["converged"], r["max_pose_error_vs_generating"]))
-        out += ["", "(CPU baseline of this phase: `bench.py`, section `pose_init.cpu_baseline`.)"]
+        out += ["", "(CPU baseline of this phase: `bench.py --full`, section `pose_init.cpu_baseline`.)"]
     return "\n".join(out) + "\n"
 
 

@@ -12,7 +12,7 @@ export VISGEOM_AMD_LIBRARY=production
   echo "## smoke()"
   python -c 'import __graft_entry__ as g; g.smoke()' 2>&1 | tail -2
   echo "## bench.py (headline line: value, ms_per_step, roofline.frac, jtj)"
-  python bench.py --steps 20 --warmup 5 > /tmp/bench_prod.json 2>/tmp/bench_prod.err
+  python bench.py --full --steps 20 --warmup 5 > /tmp/bench_prod.json 2>/tmp/bench_prod.err
   python - <<'PY'
 import json
 d = json.loads(open("/tmp/bench_prod.json").read().strip().splitlines()[-1])
@@ -22,7 +22,7 @@ print("jtj", json.dumps(d.get("jtj"))[:900])
 PY
   unset VISGEOM_AMD_LIBRARY
   echo "## the same bench on the hooks library (same box)"
-  python bench.py --steps 20 --warmup 5 > /tmp/bench_hooks.json 2>/tmp/bench_hooks.err
+  python bench.py --full --steps 20 --warmup 5 > /tmp/bench_hooks.json 2>/tmp/bench_hooks.err
   python - <<'PY'
 import json
 d = json.loads(open("/tmp/bench_hooks.json").read().strip().splitlines()[-1])

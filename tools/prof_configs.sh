@@ -28,7 +28,7 @@ for C in $CONFIGS; do
 done
 # calibration of the two counters on known byte counts (bench.py streams 512 MiB each way with the emit store pattern)
 for CN in FETCH_SIZE WRITE_SIZE; do
-  timeout 300 rocprofv3 --pmc $CN --kernel-trace --output-format csv -d "$P/cal_$CN" -o t -- python "$R/bench.py" --steps 5 --warmup 1 --no-cpu-baseline > "$P/cal_$CN.log" 2>&1
+  timeout 300 rocprofv3 --pmc $CN --kernel-trace --output-format csv -d "$P/cal_$CN" -o t -- python "$R/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline > "$P/cal_$CN.log" 2>&1
   echo "calibration pmc $CN rc=$?"
 done
 find "$P" -name '*kernel_trace.csv' -size +6M -delete

@@ -86,7 +86,7 @@ if emit:
     cur[workload_key] = {"hbm_bytes_per_launch": traffic[emit[0]], "kernel": emit[0], "tag": tag,
                          "fetch_factor": f_cal, "write_factor": w_cal,
                          "trace_avg_ns": float(stats[emit[0]]["AverageNs"]) if emit[0] in stats else None}
-# the prepared-frames emit kernel runs in bench.py's default line only on the 100 k-image stream section (eucm_100k)
+# the prepared-frames emit kernel runs in bench.py's --full line only on the 100 k-image stream section (eucm_100k)
 prep = [k for k in traffic if "vg_emit_kernel" in k and ", true, true, " in k.split("<", 1)[1][:20] and not k.rstrip().endswith("true>")]
 if prep and workload_key == "eucm_10000":
     cur["eucm_100000_stream"] = {"hbm_bytes_per_launch": traffic[prep[0]], "kernel": prep[0], "tag": tag, "fetch_factor": f_cal, "write_factor": w_cal,
