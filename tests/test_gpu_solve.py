@@ -566,16 +566,22 @@ def test_degenerate_structures(vg):
     p.close()
 
 
-def test_no_device_memory_leak_over_repeated_problems(vg):
-    """create -> evaluate -> Gram -> solve -> close, many times: the library's own hipMalloc'ed workspaces (frames,
-    partials, solver buffers, pinned host memory) must all be returned; device-wide free memory stays put."""
+def test_no_device_memory_leak_over_repeated_problems(vg, tmp_path):
+    """create -> use -> close, many times, for every object of the library that owns HIP memory: its own hipMalloc'ed
+    workspaces (frames, partials, solver buffers, scratch, pinned host memory) must all be returned; device-wide free memory
+    stays put.  The refinement's cached blocks go back through vg_release_cached_memory."""
     import torch
 
-    from visgeom_amd import synthetic as S
+    from visgeom_amd import localization as loc, stereo, synthetic as S
+    from visgeom_amd.calibration import GenericCameraCalibration, refine_poses
+    from visgeom_amd.corners import CornerDetector
+    from visgeom_amd.distributed import Comm
+    from tests import stereo_scene
 
     d = S.make_mono("eucm", 300, 2, sigma=0.1)
+    rng = np.random.default_rng(5)
 
-    def once():
+    def problem():
         p, cam, seq, ds = mono_problem(vg, d, "eucm")
         res, ji, jm = p.alloc_outputs(ds)
         gram, gsum = p.alloc_gram(ds)
@@ -591,17 +597,79 @@ def test_no_device_memory_leak_over_repeated_problems(vg):
         p.close()
         del res, ji, jm, gram, gsum
 
-    for _ in range(3):
-        once()
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    free0, _ = torch.cuda.mem_get_info()
-    for _ in range(40):
-        once()
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    free1, _ = torch.cuda.mem_get_info()
-    assert free0 - free1 < 8 << 20, "leaked %.1f MiB over 40 problems" % ((free0 - free1) / 2**20)
+    prm = stereo.make_params(u_max=125, v_max=93, u0=15, v0=15, equal_margins=1, disp_max=32, error_max=150, flaw_cost=25,
+                             desc_length=5, scales=[1, 2, 3, 5], desc_resp_thresh=2, use_uv_cache=0, epipole_margin=2500)
+    pair = [torch.from_numpy(rng.integers(0, 256, (2, 93, 125), dtype=np.uint8)).cuda() for _ in range(2)]
+
+    def dense_stereo():
+        s = stereo.Stereo(stereo_scene.CAM1, stereo_scene.CAM2, stereo_scene.RIGS["sideways"], prm)
+        s.compute(*pair)
+        s.close()
+
+    images = torch.from_numpy(rng.integers(0, 256, (2, 96, 128), dtype=np.uint8)).cuda()
+
+    def corner_detector():
+        det = CornerDetector(5, 4)
+        det.detect(images)
+        det.close()
+
+    intr, xb = d["gt_intrinsics"], np.array([0.01, 0.02, 0.03, 0.0, 0.0, 0.1])
+    x1 = np.column_stack([rng.uniform(-1, 1, (64, 2)), rng.uniform(2, 4, 64)])
+    x2, p2, size = x1 + 0.1, rng.uniform(100, 200, (64, 2)), rng.uniform(0.5, 2, 64)
+
+    def mono_reproject():
+        cost = loc.MonoReprojectCost("eucm", intr, x1[:5], p2[:5], xb)
+        cost.Evaluate([np.zeros(6), np.full(5, 3.0)])
+        cost.close()
+
+    def sparse_reproject():
+        cost = loc.SparseReprojectCost("eucm", intr, x1, x2, p2, size, xb)
+        cost.Evaluate([np.zeros(6)])
+        cost.close()
+
+    def block_group():
+        group = vg.BlockGroup(0)
+        blocks = [vg.GenericProjectionJac(d["corners"][i], d["board"], "eucm", [0], group=group) for i in range(4)]
+        for _ in range(2):
+            for i, b in enumerate(blocks):
+                b.Evaluate([d["init_intrinsics"], d["init_poses"][i]])
+        for b in blocks:
+            b.close()
+        group.close()
+
+    def local_comm():
+        (c,) = Comm.local_group(1)
+        buf = torch.ones(1000, dtype=torch.float64, device="cuda")
+        c.allreduce_sum(buf)
+        torch.cuda.synchronize()
+        c.close()
+
+    small = S.make_mono("eucm", 20, 0, sigma=0.1)
+    calib_json = S.write_calibration_json(str(tmp_path), small, "eucm", prior=False, init=True)
+
+    def calibration():
+        c = GenericCameraCalibration()
+        c.addResiduals(calib_json)
+        c.compute(max_num_iterations=5)
+        c.close()
+
+    def refinement():
+        refine_poses("eucm", d["gt_intrinsics"], d["board"], d["corners"], d["init_poses"], max_num_iterations=5)
+        vg.release_cached_memory()
+
+    for once in (problem, dense_stereo, corner_detector, mono_reproject, sparse_reproject, block_group, local_comm, calibration,
+                 refinement):
+        for _ in range(3):
+            once()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        free0, _ = torch.cuda.mem_get_info()
+        for _ in range(40):
+            once()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        free1, _ = torch.cuda.mem_get_info()
+        assert free0 - free1 < 8 << 20, "%s leaked %.1f MiB over 40 cycles" % (once.__name__, (free0 - free1) / 2**20)
 
 
 def test_argument_errors_of_the_block_level_entries(vg):

@@ -43,7 +43,8 @@ struct vg_block_group {
         int64_t cam_off = 0, tf_off[vg::kMaxChain] = {0};
     };
     std::vector<DS> dss;
-    double *d_out = nullptr, *h_mirror = nullptr, *h_params = nullptr;  // device outputs, pinned mirror, pinned parameters
+    vgi::DeviceMem<double> d_out;                 // device outputs
+    vgi::PinnedMem<double> h_mirror, h_params;    // pinned mirror, pinned parameters
     size_t total = 0;
     bool point_has_jac = false;
     int n_known = 0;            // blocks called at least twice: whether their pointers move is known
@@ -131,9 +132,9 @@ inline int seal(vg_block_group *g)
     }
     g->total = off;
     VG_HIP(hipSetDevice(g->device));
-    VG_HIP(hipMalloc(&g->d_out, sizeof(double) * (off ? off : 1)));
-    VG_HIP(hipHostMalloc(reinterpret_cast<void **>(&g->h_mirror), sizeof(double) * (off ? off : 1), hipHostMallocDefault));
-    VG_HIP(hipHostMalloc(reinterpret_cast<void **>(&g->h_params), sizeof(double) * (size_t)vg_problem_num_parameters(g->p), hipHostMallocDefault));
+    VG_HIP(g->d_out.alloc(sizeof(double) * (off ? off : 1)));
+    VG_HIP(g->h_mirror.alloc(sizeof(double) * (off ? off : 1), hipHostMallocDefault));
+    VG_HIP(g->h_params.alloc(sizeof(double) * (size_t)vg_problem_num_parameters(g->p), hipHostMallocDefault));
     g->sealed = true;
     return VG_OK;
 }

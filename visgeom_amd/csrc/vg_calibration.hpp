@@ -237,14 +237,11 @@ inline void refine_on_gpu(vg_calibration *c, const ImageData &data, const std::v
                           double soft_l1_scale)
 {
     vg_problem *p = nullptr;
-    auto chk = [&](int rc) {
-        if (rc != VG_OK) {
-            const std::string m = vg_last_error();
-            if (p) vg_problem_destroy(p);
-            throw Error{rc, m};
-        }
+    auto chk = [](int rc) {
+        if (rc != VG_OK) throw Error{rc, vg_last_error()};
     };
     chk(vg_problem_create(&p, c->device, nullptr));
+    std::unique_ptr<vg_problem, void (*)(vg_problem *)> guard(p, vg_problem_destroy);
     int cam = -1;
     chk(vg_problem_add_camera(p, c->cameraModelMap[data.cameraName], c->intrinsicMap[data.cameraName].data(), 1, &cam));
     std::vector<int> tids(chain_names.size());
@@ -290,7 +287,6 @@ inline void refine_on_gpu(vg_calibration *c, const ImageData &data, const std::v
             for (int k = 0; k < 6; k++) (*chain_values[l])[0][k] = x[(size_t)off + k];
         }
     }
-    vg_problem_destroy(p);
 }
 
 // geometric part of estimateInitialGrid  unified_calibration.cpp:1066-1135, on plain arrays: b* / c* = board point and
@@ -752,22 +748,16 @@ inline void extract_grid_projections(vg_calibration *c, ImageData &data, const v
     if (int rc = vg_corner_detector_create(&det, c->device, nullptr, data.Nx, data.Ny, data.improveDetection ? 1 : 0))
         throw Error{rc, vg_last_error()};
     std::unique_ptr<vg_corner_detector, void (*)(vg_corner_detector *)> guard(det, vg_corner_detector_destroy);
-    uint8_t *dev = nullptr;
+    vgi::DeviceMem<uint8_t> dev;
     size_t dev_bytes = 0;
-    struct DevFree {
-        uint8_t **p;
-        ~DevFree() { if (*p) (void)hipFree(*p); }
-    } dev_free{&dev};
     std::map<std::pair<int, int>, std::vector<std::pair<size_t, std::vector<uint8_t>>>> buckets;   // (w, h) -> (image, pixels)
     auto flush = [&](const std::pair<int, int> &size) {
         auto &b = buckets[size];
         if (b.empty()) return;
         const size_t plane = (size_t)size.first * size.second, k = b.size();
         if (dev_bytes < k * plane) {
-            if (dev) (void)hipFree(dev);
-            dev = nullptr;
             dev_bytes = 0;
-            if (hipMalloc(&dev, k * plane) != hipSuccess) {
+            if (dev.alloc(k * plane) != hipSuccess) {
                 (void)hipGetLastError();
                 throw Error{VG_ERR_ALLOC, "corner detection: device image buffer allocation failed"};
             }
@@ -1077,19 +1067,16 @@ int vg_calibration_compute(vg_calibration *c, const vg_solve_options *options, v
     std::unique_ptr<vgcal::PhaseClock> clk(new vgcal::PhaseClock(c->timings.assemble_s));
     int rc = vg_problem_create(&p, c->device, nullptr);
     if (rc != VG_OK) return rc;
-    auto bail = [&](int code) {
-        vg_problem_destroy(p);
-        return code;
-    };
+    std::unique_ptr<vg_problem, void (*)(vg_problem *)> guard(p, vg_problem_destroy);
     std::map<std::string, int> camId, tfId;
     std::map<std::string, int> wheelId;  // intrinsicMap also holds the wheel geometry of odometry_intrinsic entries
     for (auto &x : c->intrinsicMap) {
         if (c->cameraModelMap.find(x.first) == c->cameraModelMap.end()) {
-            if ((rc = vg_problem_add_parameter_block(p, (int)x.second.size(), x.second.data(), 0, &wheelId[x.first])) != VG_OK) return bail(rc);
+            if ((rc = vg_problem_add_parameter_block(p, (int)x.second.size(), x.second.data(), 0, &wheelId[x.first])) != VG_OK) return rc;
             continue;
         }
         if ((rc = vg_problem_add_camera(p, c->cameraModelMap[x.first], x.second.data(), c->cameraConstantMap[x.first], &camId[x.first])) != VG_OK)
-            return bail(rc);
+            return rc;
     }
     for (auto &x : c->transformInfoMap) {
         const std::string &name = x.first;
@@ -1100,7 +1087,7 @@ int vg_calibration_compute(vg_calibration *c, const vg_solve_options *options, v
             for (auto &v : c->sequenceTransformMap[name]) vals.insert(vals.end(), v.begin(), v.end());
             rc = vg_problem_add_transform(p, 0, x.second.constant, (int)c->sequenceTransformMap[name].size(), vals.data(), &tfId[name]);
         }
-        if (rc != VG_OK) return bail(rc);
+        if (rc != VG_OK) return rc;
     }
     for (auto &data : c->dataVec) {  // addGridResidualBlocks :514-630
         std::vector<int> tids;
@@ -1116,36 +1103,36 @@ int vg_calibration_compute(vg_calibration *c, const vg_solve_options *options, v
         try {   // the block the initialisation uploaded, when there was one; uploaded now otherwise
             corners = vgcal::resident_corners(c, data, std::vector<int>(idx.begin(), idx.end()));
         } catch (const vgcal::Error &e) {
-            return bail(e.code);
+            return e.code;
         }
         if ((rc = vgi::problem_add_dataset_resident(p, camId[data.cameraName], (int)tids.size(), tids.data(), data.transStatusVec.data(),
                                                     (int)data.board.size(), board.data(), (int64_t)idx.size(), idx.data(),
                                                     corners, nullptr)) != VG_OK)
-            return bail(rc);
+            return rc;
     }
     for (auto &od : c->odometry) {  // one OdometryPrior per consecutive pair (:790-801), optional anchor (:803-806)
         for (size_t i = 0; i + 1 < od.poses.size(); i++)
             if ((rc = vg_problem_add_odometry_prior(p, tfId[od.transform], (int64_t)i, od.errV, od.errW, od.lambda, od.poses[i].data(),
                                                     od.poses[i + 1].data())) != VG_OK)
-                return bail(rc);
-        if (od.anchor && (rc = vg_problem_set_pose_constant(p, tfId[od.transform], 0)) != VG_OK) return bail(rc);
+                return rc;
+        if (od.anchor && (rc = vg_problem_set_pose_constant(p, tfId[od.transform], 0)) != VG_OK) return rc;
     }
     for (auto &od : c->odometryIntrinsic) {  // one OdometryCost per interval (:719-737), optional anchor (:738-741)
         for (size_t i = 0; i < od.deltaQ.size(); i++)
             if ((rc = vg_problem_add_odometry_cost(p, tfId[od.transform], (int64_t)i, od.errV, od.errW, od.lambda, (int)(od.deltaQ[i].size() / 2),
                                                    od.deltaQ[i].data(), wheelId[od.transform])) != VG_OK)
-                return bail(rc);
-        if (od.anchor && (rc = vg_problem_set_pose_constant(p, tfId[od.transform], 0)) != VG_OK) return bail(rc);
+                return rc;
+        if (od.anchor && (rc = vg_problem_set_pose_constant(p, tfId[od.transform], 0)) != VG_OK) return rc;
     }
     for (auto &pr : c->transformationPriors)
-        if ((rc = vg_problem_add_transformation_prior(p, tfId[pr.first], pr.second.data())) != VG_OK) return bail(rc);
-    if ((rc = vg_problem_finalize(p)) != VG_OK) return bail(rc);
+        if ((rc = vg_problem_add_transformation_prior(p, tfId[pr.first], pr.second.data())) != VG_OK) return rc;
+    if ((rc = vg_problem_finalize(p)) != VG_OK) return rc;
     vg_solve_summary local;
     clk.reset(new vgcal::PhaseClock(c->timings.solve_s));
-    if ((rc = vg_problem_solve(p, options, summary ? summary : &local)) != VG_OK) return bail(rc);
+    if ((rc = vg_problem_solve(p, options, summary ? summary : &local)) != VG_OK) return rc;
     clk.reset(new vgcal::PhaseClock(c->timings.readback_s));
     std::vector<double> x((size_t)vg_problem_num_parameters(p));
-    if ((rc = vg_problem_get_parameters(p, x.data())) != VG_OK) return bail(rc);
+    if ((rc = vg_problem_get_parameters(p, x.data())) != VG_OK) return rc;
     for (auto &kv : c->intrinsicMap) {
         const int64_t off = wheelId.count(kv.first) ? vg_problem_parameter_block_offset(p, wheelId[kv.first])
                                                     : vg_problem_camera_offset(p, camId[kv.first]);
@@ -1163,7 +1150,6 @@ int vg_calibration_compute(vg_calibration *c, const vg_solve_options *options, v
             }
         }
     }
-    vg_problem_destroy(p);
     return VG_OK;
 }
 
@@ -1303,6 +1289,7 @@ int vg_calibration_write_residuals(vg_calibration *c, int dataset, const char *p
         vg_problem *p = nullptr;
         int rc = vg_problem_create(&p, c->device, nullptr);
         if (rc != VG_OK) return rc;
+        std::unique_ptr<vg_problem, void (*)(vg_problem *)> guard(p, vg_problem_destroy);
         int cam = -1, seq = -1, ds = -1;
         const int st[1] = {VG_TRANSFORM_DIRECT};
         if ((rc = vg_problem_add_camera(p, c->cameraModelMap[data.cameraName], c->intrinsicMap[data.cameraName].data(), 1, &cam)) == VG_OK &&
@@ -1311,15 +1298,13 @@ int vg_calibration_write_residuals(vg_calibration *c, int dataset, const char *p
             (rc = vg_problem_finalize(p)) == VG_OK) {
             // projecting = the residual against zero observations.  One launch into a device block of this call, one copy back
             // (vg_dataset_evaluate_to_host would set up its pinned staging for a problem that lives for one evaluation)
-            double *d_res = nullptr;
-            if (hipMalloc(&d_res, sizeof(double) * proj.size()) != hipSuccess) rc = vgi::fail(VG_ERR_ALLOC, "out of device memory");
+            vgi::DeviceMem<double> d_res;
+            if (d_res.alloc(sizeof(double) * proj.size()) != hipSuccess) rc = vgi::fail(VG_ERR_ALLOC, "out of device memory");
             if (rc == VG_OK) rc = vg_dataset_evaluate(p, ds, d_res, nullptr, nullptr);
             if (rc == VG_OK) rc = vg_problem_synchronize(p);
             if (rc == VG_OK && hipMemcpy(proj.data(), d_res, sizeof(double) * proj.size(), hipMemcpyDeviceToHost) != hipSuccess)
                 rc = vgi::fail(VG_ERR_HIP, "copying the projections back failed");
-            if (d_res) (void)hipFree(d_res);
         }
-        vg_problem_destroy(p);
         if (rc != VG_OK) return rc;
     }
     vgcal::PhaseClock clk(c->timings.residual_format_s);

@@ -32,45 +32,20 @@ using vgi::Transform;
 using vgi::fail;
 using vgi::valid_dataset;
 
-namespace {
-
-int check_device(int device)
+int vgi::check_device(int device, const char *what)
 {
     int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail(VG_ERR_NO_DEVICE, std::string("no HIP device available (") +
-                                          (e == hipSuccess ? "device count 0" : hipGetErrorString(e)) +
-                                          "); visgeom_amd has no CPU fallback");
+    const hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n <= 0) {
+        (void)hipGetLastError();
+        return fail(VG_ERR_NO_DEVICE, std::string("no HIP device available (") + (e == hipSuccess ? "device count 0" : hipGetErrorString(e)) +
+                                          "): " + what + " has no CPU fallback");
+    }
     if (device < 0 || device >= n) return fail(VG_ERR_INVALID_ARGUMENT, "device index out of range");
     return VG_OK;
 }
 
-void free_dataset(Dataset &d)
-{
-    if (d.d_board) (void)hipFree(d.d_board);
-    if (d.d_obs && !d.resident) (void)hipFree(d.d_obs);   // a resident block is freed by its last owner
-    d.resident.reset();
-    if (d.d_frames) (void)hipFree(d.d_frames);
-    if (d.d_seq) (void)hipFree(d.d_seq);
-    if (d.d_failed) (void)hipFree(d.d_failed);
-    if (d.d_partials) (void)hipFree(d.d_partials);
-    if (d.d_wg_partials) (void)hipFree(d.d_wg_partials);
-    d.d_partials = d.d_wg_partials = nullptr;
-    if (d.d_host_stage) (void)hipFree(d.d_host_stage);
-    if (d.h_host_stage) (void)hipHostFree(d.h_host_stage);
-    d.d_host_stage = d.h_host_stage = nullptr;
-    d.d_host_stage_doubles = d.h_host_stage_doubles = 0;
-    for (hipEvent_t e : d.host_chunk_ready) (void)hipEventDestroy(e);
-    for (hipEvent_t e : d.host_chunk_copied) (void)hipEventDestroy(e);
-    d.host_chunk_ready.clear();
-    d.host_chunk_copied.clear();
-    if (d.host_copy_stream) (void)hipStreamDestroy(d.host_copy_stream);
-    d.host_copy_stream = nullptr;
-    d.d_board = d.d_obs = d.d_frames = nullptr;
-    d.d_seq = nullptr;
-    d.d_failed = nullptr;
-}
+namespace {
 
 template <int MODEL>
 size_t emit_lds_bytes(bool want_jac, bool frames_lds, int N, int frame_stride)
@@ -275,7 +250,7 @@ int vg_problem_create(vg_problem **out, int device, void *hip_stream)
 {
     if (!out) return fail(VG_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
-    int rc = check_device(device);
+    int rc = vgi::check_device(device, "visgeom_amd");
     if (rc != VG_OK) return rc;
     VG_HIP(hipSetDevice(device));
     vg_problem *p = new (std::nothrow) vg_problem();
@@ -290,9 +265,6 @@ void vg_problem_destroy(vg_problem *p)
 {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    for (auto &d : p->dss) free_dataset(d);
-    if (p->d_prep) (void)hipFree(p->d_prep);
-    if (p->d_params) (void)hipFree(p->d_params);
     delete p;
 }
 
@@ -531,7 +503,7 @@ int vg_problem_finalize(vg_problem *p)
     for (auto &t : p->tfs)
         if (t.count) std::memcpy(h.data() + t.offset, t.init.data(), sizeof(double) * 6 * (size_t)t.count);
     for (auto &b : p->pblocks) std::memcpy(h.data() + b.offset, b.init.data(), sizeof(double) * (size_t)b.size);
-    VG_HIP(hipMalloc(&p->d_params, sizeof(double) * (size_t)(off > 0 ? off : 1)));
+    VG_HIP(p->d_params.alloc(sizeof(double) * (size_t)(off > 0 ? off : 1)));
     if (off) VG_HIP(hipMemcpy(p->d_params, h.data(), sizeof(double) * (size_t)off, hipMemcpyHostToDevice));
 
     for (auto &d : p->dss) {
@@ -549,13 +521,13 @@ int vg_problem_finalize(vg_problem *p)
             d.chain.stride[l] = t.global ? 0 : 6;
         }
         const size_t nb = (size_t)d.n_blocks;
-        VG_HIP(hipMalloc(&d.d_board, sizeof(double) * 3 * (size_t)d.N));
+        VG_HIP(d.d_board.alloc(sizeof(double) * 3 * (size_t)d.N));
         VG_HIP(hipMemcpy(d.d_board, d.h_board.data(), sizeof(double) * 3 * (size_t)d.N, hipMemcpyHostToDevice));
-        if (d.resident) d.d_obs = d.resident->d_obs;
-        else VG_HIP(hipMalloc(&d.d_obs, sizeof(double) * (nb ? nb : 1) * 2 * d.N));
-        VG_HIP(hipMalloc(&d.d_seq, sizeof(int32_t) * (nb ? nb : 1)));
-        VG_HIP(hipMalloc(&d.d_frames, sizeof(double) * (nb ? nb : 1) * d.frame_stride));
-        VG_HIP(hipMalloc(&d.d_failed, sizeof(unsigned long long)));
+        if (!d.resident) VG_HIP(d.d_obs_own.alloc(sizeof(double) * (nb ? nb : 1) * 2 * d.N));
+        d.d_obs = d.resident ? d.resident->d_obs : d.d_obs_own;
+        VG_HIP(d.d_seq.alloc(sizeof(int32_t) * (nb ? nb : 1)));
+        VG_HIP(d.d_frames.alloc(sizeof(double) * (nb ? nb : 1) * d.frame_stride));
+        VG_HIP(d.d_failed.alloc(sizeof(unsigned long long)));
         VG_HIP(hipMemset(d.d_failed, 0, sizeof(unsigned long long)));
         if (nb) {
             if (d.resident) {}   // already in HBM (vgi::upload_corners)
@@ -588,7 +560,7 @@ int vg_problem_finalize(vg_problem *p)
     p->prep = prep;  // up to kPrepMax datasets travel by value in the arguments of vg_chain_prep_multi_kernel
     p->prep_blocks = first;
     if (prep.size() > (size_t)vg::kPrepMax) {  // more: one launch over a descriptor table in global memory
-        VG_HIP(hipMalloc(&p->d_prep, sizeof(vg::PrepDataset) * prep.size()));
+        VG_HIP(p->d_prep.alloc(sizeof(vg::PrepDataset) * prep.size()));
         VG_HIP(hipMemcpy(p->d_prep, prep.data(), sizeof(vg::PrepDataset) * prep.size(), hipMemcpyHostToDevice));
     }
     p->finalized = true;
@@ -887,7 +859,7 @@ int block_new(vg_block **out, int device, int model, int chain_len, const int *s
     for (int l = 0; l < chain_len; l++)
         if (status[l] != VG_TRANSFORM_DIRECT && status[l] != VG_TRANSFORM_INVERSE)
             return fail(VG_ERR_INVALID_ARGUMENT, "status must be DIRECT or INVERSE");
-    int rc = check_device(device);
+    int rc = vgi::check_device(device, "visgeom_amd");
     if (rc != VG_OK) return rc;
     vg_block *b = new (std::nothrow) vg_block();
     if (!b) return fail(VG_ERR_ALLOC, "out of host memory");
@@ -920,11 +892,9 @@ int vgg::ensure_private(vg_block *b)
     if (rc == VG_OK) {
         const size_t rows = 2 * (size_t)b->N;
         const size_t total = rows * (1 + (size_t)b->K + 6 * (size_t)b->L);
-        hipError_t e = hipMalloc(&b->d_out, sizeof(double) * total);
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&b->h_out), sizeof(double) * total, hipHostMallocDefault);
-        if (e == hipSuccess)
-            e = hipHostMalloc(reinterpret_cast<void **>(&b->h_params), sizeof(double) * ((size_t)b->K + 6 * (size_t)b->L),
-                              hipHostMallocDefault);
+        hipError_t e = b->d_out.alloc(sizeof(double) * total);
+        if (e == hipSuccess) e = b->h_out.alloc(sizeof(double) * total, hipHostMallocDefault);
+        if (e == hipSuccess) e = b->h_params.alloc(sizeof(double) * ((size_t)b->K + 6 * (size_t)b->L), hipHostMallocDefault);
         if (e != hipSuccess) rc = fail(VG_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
         else {
             b->d_res = b->d_out;
@@ -981,10 +951,9 @@ void group_unseal(vg_block_group *g)
     if (g->p) vg_problem_destroy(g->p);
     g->p = nullptr;
     (void)hipSetDevice(g->device);
-    if (g->d_out) (void)hipFree(g->d_out);
-    if (g->h_mirror) (void)hipHostFree(g->h_mirror);
-    if (g->h_params) (void)hipHostFree(g->h_params);
-    g->d_out = g->h_mirror = g->h_params = nullptr;
+    (void)g->d_out.release();
+    (void)g->h_mirror.release();
+    (void)g->h_params.release();
     g->dss.clear();
     g->sealed = false;
     g->cooldown = 0;
@@ -1012,7 +981,7 @@ int vg_block_group_create(vg_block_group **out, int device, int mode)
     if (!out) return fail(VG_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
     if (mode != VG_GROUP_IN_PLACE && mode != VG_GROUP_STATE_VECTOR) return fail(VG_ERR_INVALID_ARGUMENT, "unknown group mode");
-    int rc = check_device(device);
+    int rc = vgi::check_device(device, "visgeom_amd");
     if (rc != VG_OK) return rc;
     vg_block_group *g = new (std::nothrow) vg_block_group();
     if (!g) return fail(VG_ERR_ALLOC, "out of host memory");
@@ -1145,9 +1114,6 @@ void vg_block_destroy(vg_block *b)
         if (b->stale && g->n_stale > 0) g->n_stale--;
     }
     (void)hipSetDevice(b->device);
-    if (b->d_out) (void)hipFree(b->d_out);
-    if (b->h_out) (void)hipHostFree(b->h_out);
-    if (b->h_params) (void)hipHostFree(b->h_params);
     vg_problem_destroy(b->p);
     delete b;
 }
@@ -1190,12 +1156,10 @@ int vg_calib_d2h_copies(int device, int64_t bytes, int reps, double *seconds_out
 {
     if (bytes <= 0 || reps <= 0 || !seconds_out) return fail(VG_ERR_INVALID_ARGUMENT, "bad arguments");
     VG_HIP(hipSetDevice(device));
-    void *dev = nullptr, *host = nullptr;
-    VG_HIP(hipMalloc(&dev, (size_t)bytes));
-    if (hipHostMalloc(&host, (size_t)bytes, hipHostMallocDefault) != hipSuccess) {
-        (void)hipFree(dev);
-        return fail(VG_ERR_ALLOC, "hipHostMalloc failed");
-    }
+    vgi::DeviceMem<void> dev;
+    vgi::PinnedMem<void> host;
+    VG_HIP(dev.alloc((size_t)bytes));
+    if (host.alloc((size_t)bytes, hipHostMallocDefault) != hipSuccess) return fail(VG_ERR_ALLOC, "hipHostMalloc failed");
     int rc = VG_OK;
     if (hipMemset(dev, 1, (size_t)bytes) != hipSuccess) rc = fail(VG_ERR_HIP, "hipMemset failed");
     std::memset(host, 0, (size_t)bytes);
@@ -1205,8 +1169,6 @@ int vg_calib_d2h_copies(int device, int64_t bytes, int reps, double *seconds_out
         if (hipMemcpy(host, dev, (size_t)bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(VG_ERR_HIP, "hipMemcpy failed");
         seconds_out[r] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
-    (void)hipHostFree(host);
-    (void)hipFree(dev);
     return rc;
 }
 

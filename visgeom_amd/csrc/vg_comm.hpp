@@ -13,6 +13,7 @@
 
 #include <chrono>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 
 #include <rccl/rccl.h>  // types and prototypes only; every call goes through the table below
@@ -26,7 +27,7 @@ namespace vgc {
 struct LocalGroup {
     int n = 0, device = 0, refs = 0;
     size_t cap = 0;            // doubles per slot
-    double *slots = nullptr;   // device [n][cap]
+    vgi::DeviceMem<double> slots;   // device [n][cap]
     std::mutex m;
     std::condition_variable cv;
     int arrived = 0;
@@ -256,31 +257,28 @@ int vg_comm_create_local(vg_comm **out, int n_ranks, int device)
     for (int r = 0; r < (n_ranks > 0 ? n_ranks : 0); r++) out[r] = nullptr;
     if (n_ranks < 1 || n_ranks > 64) return vgi::fail(VG_ERR_INVALID_ARGUMENT, "n_ranks must be in [1, 64]");
     VG_HIP(hipSetDevice(device));
-    vgc::LocalGroup *g = new (std::nothrow) vgc::LocalGroup();
+    std::unique_ptr<vgc::LocalGroup> g(new (std::nothrow) vgc::LocalGroup());
     if (!g) return vgi::fail(VG_ERR_ALLOC, "out of host memory");
     g->n = n_ranks;
     g->device = device;
     g->cap = 1u << 16;  // 64 Ki doubles per rank and piece; longer messages are walked in pieces (allreduce_sum)
-    if (hipMalloc(reinterpret_cast<void **>(&g->slots), sizeof(double) * g->cap * (size_t)n_ranks) != hipSuccess) {
-        delete g;
+    if (g->slots.alloc(sizeof(double) * g->cap * (size_t)n_ranks) != hipSuccess)
         return vgi::fail(VG_ERR_ALLOC, "hipMalloc of the local communicator's slots failed");
-    }
     for (int r = 0; r < n_ranks; r++) {
         vg_comm *c = new (std::nothrow) vg_comm();
         if (!c) {
             for (int q = 0; q < r; q++) { delete out[q]; out[q] = nullptr; }
-            (void)hipFree(g->slots);
-            delete g;
             return vgi::fail(VG_ERR_ALLOC, "out of host memory");
         }
         c->n_ranks = n_ranks;
         c->rank = r;
         c->device = device;
         c->owned = false;
-        c->local = g;
+        c->local = g.get();
         g->refs++;
         out[r] = c;
     }
+    g.release();   // owned by its ranks from here on: the last vg_comm_destroy frees it
     return VG_OK;
 }
 
@@ -317,7 +315,6 @@ void vg_comm_destroy(vg_comm *c)
         }
         if (last) {
             (void)hipSetDevice(g->device);
-            (void)hipFree(g->slots);
             delete g;
         }
     }

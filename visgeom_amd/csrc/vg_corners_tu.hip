@@ -28,17 +28,6 @@ constexpr int kCornerMaxChunk = 64;
 constexpr int kGraphThreads = 16;                           // host threads of the graph stage
 const double kSigmas[3] = {1.4, 2., 1.};
 
-int check_device(int device)
-{
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        (void)hipGetLastError();
-        return fail(VG_ERR_NO_DEVICE, "no HIP device: corner detection has no CPU fallback");
-    }
-    if (device < 0 || device >= n_dev) return fail(VG_ERR_INVALID_ARGUMENT, "device index out of range");
-    return VG_OK;
-}
-
 // cv::getGaussianKernel(n, sigma, CV_64F) for sigma > 0: exp(-x^2 / (2 sigma^2)) normalised to sum 1, then rounded to float
 void gaussian(int n, double sigma, float *w)
 {
@@ -88,7 +77,7 @@ struct vg_corner_detector {
     int W = 0, H = 0, chunk = 0, tiles_x = 0, tiles = 0;
     int64_t cap = 0;
     size_t plane = 0;
-    char *dev = nullptr;
+    vgi::DeviceMem<char> dev;
     int64_t *d_list = nullptr;
     uint8_t *d_src2 = nullptr;
     float *d_gx = nullptr, *d_gy = nullptr, *d_imgrad = nullptr, *d_resp = nullptr;
@@ -98,7 +87,7 @@ struct vg_corner_detector {
     int *d_trans = nullptr;
     double *d_rinit = nullptr, *d_rprior = nullptr, *d_rrad = nullptr, *d_rout = nullptr;
     int *d_rslot = nullptr;
-    char *host = nullptr;   // pinned
+    vgi::PinnedMem<char> host;
     int64_t *h_list = nullptr;
     uint8_t *h_src2 = nullptr;
     float *h_gx = nullptr, *h_gy = nullptr;
@@ -106,14 +95,6 @@ struct vg_corner_detector {
     double *h_gthresh = nullptr, *h_rinit = nullptr, *h_rprior = nullptr, *h_rrad = nullptr, *h_rout = nullptr;
     double stats[8] = {0};   // gpu_s, d2h_s, d2h_bytes, graph_s, graph_images, refine_s, refine_corners, calls
 
-    ~vg_corner_detector() { release(); }
-    void release()
-    {
-        if (dev) (void)hipFree(dev);
-        if (host) (void)hipHostFree(host);
-        dev = host = nullptr;
-        W = H = chunk = 0;
-    }
     int n_corners() const { return Nx * Ny; }
     int max_hyp() const { return 10 * Nx * Ny; }   // MAX_CANDIDATE_COUNT
 
@@ -137,25 +118,27 @@ struct vg_corner_detector {
     int ensure(int w, int h)
     {
         if (w == W && h == H && dev) return VG_OK;
-        release();
+        (void)dev.release();
+        (void)host.release();
+        W = H = chunk = 0;
         const int tx = (w + vg::kCornerTileW - 1) / vg::kCornerTileW, ty = (h + vg::kCornerTileH - 1) / vg::kCornerTileH;
         const int64_t cp = (int64_t)((w + 1) / 2) * ((h + 1) / 2);
         const int nc = n_corners();
         int c = kCornerMaxChunk;
         while (c > 1 && device_bytes(w, h, c, cp, tx * ty, nc) > (size_t)kCornerDeviceBudget) c--;
         VG_HIP(hipSetDevice(device));
-        char *d = nullptr, *hp = nullptr;
-        if (hipMalloc(&d, device_bytes(w, h, c, cp, tx * ty, nc)) != hipSuccess) {
+        vgi::DeviceMem<char> d;
+        vgi::PinnedMem<char> hp;
+        if (d.alloc(device_bytes(w, h, c, cp, tx * ty, nc)) != hipSuccess) {
             (void)hipGetLastError();
             return fail(VG_ERR_ALLOC, "corner detector: device scratch allocation failed");
         }
-        if (hipHostMalloc(&hp, host_bytes(w, h, c, nc), hipHostMallocDefault) != hipSuccess) {
+        if (hp.alloc(host_bytes(w, h, c, nc), hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
-            (void)hipFree(d);
             return fail(VG_ERR_ALLOC, "corner detector: pinned host allocation failed");
         }
-        dev = d;
-        host = hp;
+        dev = std::move(d);
+        host = std::move(hp);
         W = w;
         H = h;
         chunk = c;
@@ -480,7 +463,7 @@ int vg_corner_detector_create(vg_corner_detector **out, int device, void *hip_st
     if (cols < 2 || rows < 2 || cols * rows > 400)
         return fail(VG_ERR_INVALID_ARGUMENT, "the board needs cols, rows >= 2 and at most 400 corners");
     if (improve != 0 && improve != 1) return fail(VG_ERR_INVALID_ARGUMENT, "improve must be 0 or 1");
-    if (const int rc = check_device(device)) return rc;
+    if (const int rc = vgi::check_device(device, "corner detection")) return rc;
     vg_corner_detector *d = new (std::nothrow) vg_corner_detector();
     if (!d) return fail(VG_ERR_ALLOC, "out of host memory");
     d->device = device;

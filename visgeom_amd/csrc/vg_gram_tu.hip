@@ -207,7 +207,7 @@ int vgi::gram_fused_at(vg_problem *p, int dataset_id, const double *d_params, do
         // room for either kernel's partials: one per octet (one-shot), one per resident workgroup (persistent: at most one per
         // image pair and never more than 1 024)
         const size_t n_part = gram_partial_count(d.n_blocks);
-        if (!d.d_wg_partials) VG_HIP(hipMalloc(&d.d_wg_partials, sizeof(double) * (size_t)E * n_part));
+        if (!d.d_wg_partials) VG_HIP(d.d_wg_partials.alloc(sizeof(double) * (size_t)E * n_part));
         a.partials = d.d_wg_partials;
     }
     const int pers = (inl && d.L == 1) ? gram_pers_shape(a, sum != nullptr) : 0;
@@ -343,7 +343,7 @@ int vg_problem_gram_fused_sum(vg_problem *p, double *const *grams, double *const
         if (!d.n_blocks || d.n_blocks > 0x7fffffff) continue;
         const int W = p->cams[d.camera].K + 6 * d.L + 1, E = W * (W + 1) / 2;
         const size_t n_part = gram_partial_count(d.n_blocks);   // as in gram_fused_at: the buffer is shared
-        if (!d.d_wg_partials) VG_HIP(hipMalloc(&d.d_wg_partials, sizeof(double) * (size_t)E * n_part));
+        if (!d.d_wg_partials) VG_HIP(d.d_wg_partials.alloc(sizeof(double) * (size_t)E * n_part));
         parts[(size_t)i] = d.d_wg_partials;
     }
     std::vector<char> taken;
@@ -433,7 +433,7 @@ int vgi::gram_sum_into(vg_problem *p, int dataset_id, const double *gram, double
     if (!gram) return fail(VG_ERR_INVALID_ARGUMENT, "gram is NULL");
     const unsigned int n = (unsigned int)d.n_blocks;
     const unsigned int parts = (n + vg::kSlab - 1) / vg::kSlab;
-    if (!d.d_partials) VG_HIP(hipMalloc(&d.d_partials, sizeof(double) * (size_t)parts * entries));
+    if (!d.d_partials) VG_HIP(d.d_partials.alloc(sizeof(double) * (size_t)parts * entries));
     hipLaunchKernelGGL(vg::vg_gram_slab_sum_kernel, dim3(parts), dim3(256), 0, p->stream, gram, n, entries, d.d_partials);
     VG_HIP(hipGetLastError());
     hipLaunchKernelGGL(vg::vg_gram_final_sum_kernel, dim3((entries + 3) / 4), dim3(256), 0, p->stream,

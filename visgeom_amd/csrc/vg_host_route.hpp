@@ -80,45 +80,33 @@ extern "C" int vg_dataset_evaluate_to_host(vg_problem *p, int dataset_id, double
 
     const size_t total = per_image * (size_t)d.n_blocks;
     if (d.d_host_stage_doubles < total) {
-        if (d.d_host_stage) (void)hipFree(d.d_host_stage);
-        d.d_host_stage = nullptr;
         d.d_host_stage_doubles = 0;
-        VG_HIP(hipMalloc(&d.d_host_stage, sizeof(double) * total));
+        VG_HIP(d.d_host_stage.alloc(sizeof(double) * total));
         d.d_host_stage_doubles = total;
     }
     if (!direct && d.h_host_stage_doubles < total) {
-        if (d.h_host_stage) (void)hipHostFree(d.h_host_stage);
-        d.h_host_stage = nullptr;
         d.h_host_stage_doubles = 0;
-        VG_HIP(hipHostMalloc(&d.h_host_stage, sizeof(double) * total, hipHostMallocDefault));
+        VG_HIP(d.h_host_stage.alloc(sizeof(double) * total, hipHostMallocDefault));
         d.h_host_stage_doubles = total;
         // first touch now, by several threads, not inside the first timed copy
         vgpar::parallel_ranges(total, (size_t)1 << 20, [&](size_t b, size_t e, int) { std::memset(d.h_host_stage + b, 0, sizeof(double) * (e - b)); });
     }
-    if (!d.host_copy_stream) VG_HIP(hipStreamCreateWithFlags(&d.host_copy_stream, hipStreamNonBlocking));
+    if (!d.host_copy_stream) VG_HIP(d.host_copy_stream.create(hipStreamNonBlocking));
     while ((int)d.host_chunk_ready.size() < n_chunks) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        VG_HIP(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-        d.host_chunk_ready.push_back(e0);
-        VG_HIP(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-        d.host_chunk_copied.push_back(e1);
+        vgi::Event e0, e1;
+        VG_HIP(e0.create(hipEventDisableTiming));
+        d.host_chunk_ready.push_back(std::move(e0));
+        VG_HIP(e1.create(hipEventDisableTiming));
+        d.host_chunk_copied.push_back(std::move(e1));
     }
 
     const bool inline_chain = single_launch_dataset(p, d);
     if (!inline_chain && (rc = vgi::ensure_frames(p)) != VG_OK) return rc;
     hipStream_t cs = d.host_copy_stream;
     // From the first launch on, a failure must not return while copies into the caller's arrays (or the staging the next call
-    // reuses) are still queued: whichever way the function is left, both streams are drained first.
-    struct Drain {
-        hipStream_t a, b;
-        bool armed;
-        ~Drain()
-        {
-            if (!armed) return;
-            (void)hipStreamSynchronize(a);
-            (void)hipStreamSynchronize(b);
-        }
-    } drain{p->stream, cs, true};
+    // reuses) are still queued: whichever way the function is left, both streams are drained first.  (Destroyed
+    // in reverse order: the launch stream drains before the copy stream.)
+    vgi::StreamDrain drain_copies{cs}, drain_launches{p->stream};
     // queue everything: evaluate chunk k, mark it, copy it behind the mark
     size_t off = 0;  // doubles into the staging blocks
     for (int k = 0; k < n_chunks; k++) {
@@ -163,7 +151,7 @@ extern "C" int vg_dataset_evaluate_to_host(vg_problem *p, int dataset_id, double
     }
     if (direct) {
         VG_HIP(hipStreamSynchronize(cs));
-        drain.armed = false;   // the copy stream waited for every launch: nothing is in flight
+        drain_copies.armed = drain_launches.armed = false;   // the copy stream waited for every launch: nothing is in flight
         return VG_OK;
     }
     // the host's threads move chunk k into the caller's arrays while chunk k + 1 is on the bus
@@ -202,6 +190,6 @@ extern "C" int vg_dataset_evaluate_to_host(vg_problem *p, int dataset_id, double
         });
         off += chunk_doubles;
     }
-    drain.armed = false;   // every chunk's copy event has been waited for
+    drain_copies.armed = drain_launches.armed = false;   // every chunk's copy event has been waited for
     return VG_OK;
 }

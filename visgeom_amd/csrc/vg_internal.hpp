@@ -53,6 +53,92 @@ constexpr long long debug_hook(DebugHook) { return 0; }
         }                                                                                         \
     } while (0)
 
+// VG_OK when `device` names a HIP device; VG_ERR_NO_DEVICE when there is none ("<what> has no CPU fallback"),
+// VG_ERR_INVALID_ARGUMENT when the index is out of range
+int check_device(int device, const char *what);
+
+// ---- owners of the library's HIP resources: move-only, null by default, host only.  A destructor ignores the error of
+// its release, never throws and never calls hipSetDevice: hipFree / hipHostFree / hipStreamDestroy / hipEventDestroy act
+// on the resource's own device, and callers such as torch rely on their current device being left alone.  release()
+// frees early and returns the error; alloc() / create() release what the owner held first, so a grow-only buffer never
+// holds two blocks at once.
+template <class H, hipError_t (*Free)(H)>
+class HipOwner {
+public:
+    HipOwner() = default;
+    HipOwner(HipOwner &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    HipOwner &operator=(HipOwner &&o) noexcept
+    {
+        if (this != &o) {
+            (void)release();
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    ~HipOwner() { (void)release(); }
+    hipError_t release()
+    {
+        H h = h_;
+        h_ = nullptr;
+        return h ? Free(h) : hipSuccess;
+    }
+
+protected:
+    H h_ = nullptr;
+};
+
+template <class T>
+struct DeviceMem : HipOwner<void *, hipFree> {
+    T *get() const { return static_cast<T *>(h_); }
+    operator T *() const { return get(); }
+    hipError_t alloc(size_t bytes)
+    {
+        (void)release();
+        return hipMalloc(&h_, bytes);
+    }
+};
+
+template <class T>
+struct PinnedMem : HipOwner<void *, hipHostFree> {
+    T *get() const { return static_cast<T *>(h_); }
+    operator T *() const { return get(); }
+    hipError_t alloc(size_t bytes, unsigned int flags)   // hipHostMallocDefault, ...Coherent or ...Mapped
+    {
+        (void)release();
+        return hipHostMalloc(&h_, bytes, flags);
+    }
+};
+
+struct Stream : HipOwner<hipStream_t, hipStreamDestroy> {
+    operator hipStream_t() const { return h_; }
+    hipError_t create(unsigned int flags)
+    {
+        (void)release();
+        return hipStreamCreateWithFlags(&h_, flags);
+    }
+};
+
+struct Event : HipOwner<hipEvent_t, hipEventDestroy> {
+    operator hipEvent_t() const { return h_; }
+    hipError_t create(unsigned int flags = hipEventDefault)
+    {
+        (void)release();
+        return hipEventCreateWithFlags(&h_, flags);
+    }
+};
+
+// synchronises `stream` when it goes out of scope while armed: a failure path does not return while work that reads or
+// writes the library's blocks (or the caller's arrays) is still queued
+struct StreamDrain {
+    hipStream_t stream;
+    bool armed = true;
+    ~StreamDrain()
+    {
+        if (armed) (void)hipStreamSynchronize(stream);
+    }
+};
+
 struct Camera {
     int model = 0, K = 0;
     bool constant = false;
@@ -80,13 +166,9 @@ struct ParamBlock {
 // unified_calibration.cpp:1137-1155 then :514-630).  Freed with the last owner.
 struct CornerBlock {
     int device = 0;
-    double *d_obs = nullptr;   // [n_images][N][2]
+    DeviceMem<double> d_obs;   // [n_images][N][2]
     int64_t n_images = 0;
     int N = 0;
-    CornerBlock() = default;
-    CornerBlock(const CornerBlock &) = delete;
-    CornerBlock &operator=(const CornerBlock &) = delete;
-    ~CornerBlock();
 };
 
 struct Dataset {
@@ -99,18 +181,20 @@ struct Dataset {
     bool seq_identity = true;  // image b uses element b of its sequence: no index array needed on the device
     bool zero_obs = false;     // added without corners: the observations are zeros (cleared on the device, nothing uploaded)
     std::shared_ptr<CornerBlock> resident;   // the observations live in a shared block (d_obs points into it, not owned)
-    double *d_board = nullptr, *d_obs = nullptr, *d_frames = nullptr;
-    int32_t *d_seq = nullptr;
-    unsigned long long *d_failed = nullptr;
+    double *d_obs = nullptr;                 // resident->d_obs or d_obs_own
+    DeviceMem<double> d_obs_own, d_board, d_frames;
+    DeviceMem<int32_t> d_seq;
+    DeviceMem<unsigned long long> d_failed;
     // vg_dataset_evaluate_to_host (vg_host_route.hpp): the rows travel chunk by chunk -- device staging laid out chunk-major
     // [res | jac_intr | jac_member ...] per chunk, a copy stream of its own, one event pair per chunk, and (for destinations
     // that are not pinned) a pinned staging block of the same layout that the host's threads scatter into the caller's arrays
-    double *d_host_stage = nullptr, *h_host_stage = nullptr;
+    DeviceMem<double> d_host_stage;
+    PinnedMem<double> h_host_stage;
     size_t d_host_stage_doubles = 0, h_host_stage_doubles = 0;
-    hipStream_t host_copy_stream = nullptr;
-    std::vector<hipEvent_t> host_chunk_ready, host_chunk_copied;
-    double *d_partials = nullptr;  // [ceil(n_blocks / kSlab)][W*W] workspace of vg_dataset_gram_sum
-    double *d_wg_partials = nullptr;  // [W(W+1)/2][n_workgroups] per-workgroup sums of the vector-pipe Gram kernel
+    Stream host_copy_stream;
+    std::vector<Event> host_chunk_ready, host_chunk_copied;
+    DeviceMem<double> d_partials;  // [ceil(n_blocks / kSlab)][W*W] workspace of vg_dataset_gram_sum
+    DeviceMem<double> d_wg_partials;  // [W(W+1)/2][n_workgroups] per-workgroup sums of the vector-pipe Gram kernel
     unsigned long long epoch = 0;  // evaluation counter, tags d_failed
     int frame_stride = 0;
     vg::ChainDesc chain;
@@ -138,9 +222,9 @@ struct vg_problem {
     std::vector<vgodo::Block> odoms;                       // OdometryPrior blocks (consecutive elements of a sequence)
     std::vector<std::pair<int, int64_t>> const_poses;     // (sequence transform, index) held constant ("anchor")
     int64_t n_params = 0;
-    double *d_params = nullptr;
+    vgi::DeviceMem<double> d_params;
     std::vector<vg::PrepDataset> prep;  // one descriptor per non-empty dataset (vg_chain_prep_multi_kernel takes them by value)
-    vg::PrepDataset *d_prep = nullptr;  // the same as a table in global memory, only for problems of more than kPrepMax datasets
+    vgi::DeviceMem<vg::PrepDataset> d_prep;  // the same as a table in global memory, only for problems of more than kPrepMax datasets
     int64_t prep_blocks = 0;
     // vg_problem_prepare marks the frames stale; they are rebuilt on demand (chain-prep kernel) by whoever reads
     // them from HBM -- or never, when every consumer derives them in-kernel (single-member DIRECT chains)
@@ -162,10 +246,11 @@ struct vg_block {
     std::vector<double> h_grid, h_obs;  // kept for the private problem / the group's resident problem
     // one device allocation [res | jac_intr | jac_member 0 | ...] and one pinned host mirror of it: a call is one
     // H2D of the parameters, two launches, ONE D2H and one synchronisation
-    double *d_out = nullptr, *h_out = nullptr;
+    vgi::DeviceMem<double> d_out;
+    vgi::PinnedMem<double> h_out;
     double *d_res = nullptr, *d_jintr = nullptr;
     double *d_jm[vg::kMaxChain] = {nullptr};
-    double *h_params = nullptr;  // pinned, K + 6L doubles
+    vgi::PinnedMem<double> h_params;  // K + 6L doubles
     // ---- membership in a vg_block_group (vg_block_group.hpp)
     vg_block_group *group = nullptr;
     int g_ds = -1, g_idx = -1;

@@ -45,11 +45,7 @@ struct LmSolve::DeviceLoop {
         vg::LmState *p = nullptr;
         volatile unsigned long long *seq = nullptr;   // pinned, behind the states: what the accept kernel of a slot wrote last
         unsigned long long expect[kSlots] = {};
-        bool owned = false;
-        ~Slots()
-        {
-            if (p && owned) (void)hipHostFree(p);
-        }
+        vgi::PinnedMem<vg::LmState> own;   // when the solve's arena had no room
     } slots;
     unsigned long long seq_counter = 0ull;
     int n_queued = 0;
@@ -159,8 +155,8 @@ struct LmSolve::DeviceLoop {
         const size_t slots_bytes = sizeof(vg::LmState) * kSlots + sizeof(unsigned long long) * kSlots;
         if (t_arena) slots.p = static_cast<vg::LmState *>(t_arena->pin_alloc(slots_bytes));
         if (!slots.p) {
-            VG_HIP(hipHostMalloc(reinterpret_cast<void **>(&slots.p), slots_bytes, hipHostMallocCoherent));
-            slots.owned = true;
+            VG_HIP(slots.own.alloc(slots_bytes, hipHostMallocCoherent));
+            slots.p = slots.own;
         }
         slots.seq = reinterpret_cast<volatile unsigned long long *>(slots.p + kSlots);
         for (int k = 0; k < kSlots; k++) slots.seq[k] = 0ull;

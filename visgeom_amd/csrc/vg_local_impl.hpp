@@ -1,6 +1,7 @@
 // vg_local_impl.hpp -- host side of the localization reprojection costs (vg_local.hpp): resident sets of blocks, the
 // batched device entries and the per-block host entries that mirror Ceres' Evaluate contract.  Included at the end of
 // vg_capi.hip (the library is one translation unit).
+#include <memory>
 #include <new>
 
 #include "vg_internal.hpp"
@@ -12,14 +13,15 @@ struct vg_reproject_set {
     hipStream_t stream = nullptr;
     int64_t n_blocks = 0, total = 0;       // total = number of points over all blocks
     std::vector<int64_t> offsets;          // [n_blocks + 1] first point of every block
-    double *d_const = nullptr;             // one allocation: intrinsics | xiBaseCam | x1 | x2 | p2 | size
+    vgi::DeviceMem<double> d_const;        // one allocation: intrinsics | xiBaseCam | x1 | x2 | p2 | size
     double *d_intr = nullptr, *d_xb = nullptr, *d_x1 = nullptr, *d_x2 = nullptr, *d_p2 = nullptr, *d_size = nullptr;
     double *d_base = nullptr;              // [kBaseConst] what the frames need of xiBaseCam alone, computed once on the device
-    int *d_point_block = nullptr;
-    double *d_frames = nullptr;
+    vgi::DeviceMem<int> d_point_block;
+    vgi::DeviceMem<double> d_frames;
     // per-block host entry: parameters in, rows out, through one pinned block and one device block
     int64_t max_points = 0;
-    double *h_pin = nullptr, *d_io = nullptr;
+    vgi::PinnedMem<double> h_pin;
+    vgi::DeviceMem<double> d_io;
     // sparse: the most blocks any aligned run of kEmitThreads points of the set touches (counting empty blocks in between)
     int64_t max_wg_span = 0;
 };
@@ -32,11 +34,6 @@ inline void destroy(vg_reproject_set *s)
 {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    if (s->d_const) (void)hipFree(s->d_const);
-    if (s->d_point_block) (void)hipFree(s->d_point_block);
-    if (s->d_frames) (void)hipFree(s->d_frames);
-    if (s->d_io) (void)hipFree(s->d_io);
-    if (s->h_pin) (void)hipHostFree(s->h_pin);
     delete s;
 }
 
@@ -47,10 +44,10 @@ inline size_t io_doubles(const vg_reproject_set *s)
     return 12 + 2 * n + 12 * n + (s->sparse ? 0 : 10 * n);
 }
 
-inline int create_unguarded(vg_reproject_set **out, int device, void *hip_stream, int model, const double *intr, const double *xb, bool sparse,
-                            int64_t n_blocks, const int64_t *offsets, const double *x1, const double *x2, const double *p2, const double *size,
-                            vg_reproject_set *&live)
-{
+// std::vector growth inside the set-up may throw; nothing may cross the extern "C" boundary
+inline int create(vg_reproject_set **out, int device, void *hip_stream, int model, const double *intr, const double *xb, bool sparse,
+                  int64_t n_blocks, const int64_t *offsets, const double *x1, const double *x2, const double *p2, const double *size)
+try {
     if (!out) return fail(VG_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
     const int K = vg::num_intrinsics(model);
@@ -58,15 +55,9 @@ inline int create_unguarded(vg_reproject_set **out, int device, void *hip_stream
     if (!intr || !xb || n_blocks < 0 || (n_blocks > 0 && (!x1 || !p2))) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (sparse && n_blocks > 0 && (!offsets || !x2 || !size)) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (n_blocks >= (1ll << 31) / 8) return fail(VG_ERR_INVALID_ARGUMENT, "too many blocks");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        (void)hipGetLastError();
-        return fail(VG_ERR_NO_DEVICE, "no HIP device: the reprojection costs have no CPU fallback");
-    }
-    if (device < 0 || device >= n_dev) return fail(VG_ERR_INVALID_ARGUMENT, "device index out of range");
-    vg_reproject_set *s = new (std::nothrow) vg_reproject_set();
+    if (const int rc = vgi::check_device(device, "the reprojection costs")) return rc;
+    std::unique_ptr<vg_reproject_set> s(new (std::nothrow) vg_reproject_set());
     if (!s) return fail(VG_ERR_ALLOC, "out of host memory");
-    live = s;   // what create() releases if a container below throws
     s->device = device;
     s->model = model;
     s->K = K;
@@ -78,25 +69,13 @@ inline int create_unguarded(vg_reproject_set **out, int device, void *hip_stream
         s->offsets[(size_t)b] = (sparse && n_blocks > 0) ? offsets[b] : b * vg::kMonoPoints;   // an empty sparse set may pass offsets = NULL
         if (b > 0) {
             const int64_t n = s->offsets[(size_t)b] - s->offsets[(size_t)b - 1];
-            if (n < 0) {
-                delete s;
-                live = nullptr;
-                return fail(VG_ERR_INVALID_ARGUMENT, "offsets must not decrease");
-            }
+            if (n < 0) return fail(VG_ERR_INVALID_ARGUMENT, "offsets must not decrease");
             s->max_points = n > s->max_points ? n : s->max_points;
         }
     }
-    if (n_blocks > 0 && s->offsets[0] != 0) {
-        delete s;
-        live = nullptr;
-        return fail(VG_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
-    }
+    if (n_blocks > 0 && s->offsets[0] != 0) return fail(VG_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
     s->total = s->offsets[(size_t)n_blocks];
-    if (s->total >= (1ll << 31)) {
-        delete s;
-        live = nullptr;
-        return fail(VG_ERR_INVALID_ARGUMENT, "too many points");
-    }
+    if (s->total >= (1ll << 31)) return fail(VG_ERR_INVALID_ARGUMENT, "too many points");
     const size_t T = (size_t)s->total;
     // layout of the constant block (every piece 16-byte aligned)
     const size_t o_intr = 0, o_xb = 10, o_x1 = 16, o_x2 = o_x1 + 3 * T + (T & 1), o_p2 = o_x2 + (sparse ? 3 * T + (T & 1) : 0),
@@ -111,15 +90,13 @@ inline int create_unguarded(vg_reproject_set **out, int device, void *hip_stream
         std::memcpy(h.data() + o_p2, p2, sizeof(double) * 2 * T);
         if (sparse) std::memcpy(h.data() + o_size, size, sizeof(double) * T);
     }
-    int rc = VG_OK;
-    auto hip_fail = [&](hipError_t e, const char *what) {
-        rc = fail(e == hipErrorNoDevice || e == hipErrorInvalidDevice ? VG_ERR_NO_DEVICE : VG_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-        return rc;
+    auto hip_fail = [](hipError_t e, const char *what) {
+        return fail(e == hipErrorNoDevice || e == hipErrorInvalidDevice ? VG_ERR_NO_DEVICE : VG_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
     };
     hipError_t e;
-    if ((e = hipSetDevice(device)) != hipSuccess) { hip_fail(e, "hipSetDevice"); destroy(s); live = nullptr; return rc; }
-    if ((e = hipMalloc(reinterpret_cast<void **>(&s->d_const), sizeof(double) * n_const)) != hipSuccess) { hip_fail(e, "hipMalloc"); destroy(s); live = nullptr; return rc; }
-    if ((e = hipMemcpy(s->d_const, h.data(), sizeof(double) * n_const, hipMemcpyHostToDevice)) != hipSuccess) { hip_fail(e, "hipMemcpy"); destroy(s); live = nullptr; return rc; }
+    if ((e = hipSetDevice(device)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if ((e = s->d_const.alloc(sizeof(double) * n_const)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    if ((e = hipMemcpy(s->d_const, h.data(), sizeof(double) * n_const, hipMemcpyHostToDevice)) != hipSuccess) return hip_fail(e, "hipMemcpy");
     s->d_intr = s->d_const + o_intr;
     s->d_xb = s->d_const + o_xb;
     s->d_x1 = s->d_const + o_x1;
@@ -128,7 +105,7 @@ inline int create_unguarded(vg_reproject_set **out, int device, void *hip_stream
     s->d_size = s->d_const + o_size;
     s->d_base = s->d_const + o_base;
     hipLaunchKernelGGL(vg::vg_local_base_kernel, dim3(1), dim3(64), 0, s->stream, (const double *)s->d_xb, s->d_base);
-    if ((e = hipGetLastError()) != hipSuccess) { hip_fail(e, "vg_local_base_kernel"); destroy(s); live = nullptr; return rc; }
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "vg_local_base_kernel");
     if (sparse) {
         std::vector<int> pb(T ? T : 1, 0);
         for (int64_t b = 0; b < n_blocks; b++)
@@ -139,31 +116,19 @@ inline int create_unguarded(vg_reproject_set **out, int device, void *hip_stream
             const int64_t span = (int64_t)pb[j] - pb[i] + 1;
             s->max_wg_span = span > s->max_wg_span ? span : s->max_wg_span;
         }
-        if ((e = hipMalloc(reinterpret_cast<void **>(&s->d_point_block), sizeof(int) * pb.size())) != hipSuccess) { hip_fail(e, "hipMalloc"); destroy(s); live = nullptr; return rc; }
-        if ((e = hipMemcpy(s->d_point_block, pb.data(), sizeof(int) * pb.size(), hipMemcpyHostToDevice)) != hipSuccess) { hip_fail(e, "hipMemcpy"); destroy(s); live = nullptr; return rc; }
+        if ((e = s->d_point_block.alloc(sizeof(int) * pb.size())) != hipSuccess) return hip_fail(e, "hipMalloc");
+        if ((e = hipMemcpy(s->d_point_block, pb.data(), sizeof(int) * pb.size(), hipMemcpyHostToDevice)) != hipSuccess) return hip_fail(e, "hipMemcpy");
     }
     const size_t fr = sparse ? (size_t)(n_blocks ? n_blocks : 1) * vg::kSparseFrame : 2;   // mono frames live in LDS only
-    if ((e = hipMalloc(reinterpret_cast<void **>(&s->d_frames), sizeof(double) * fr)) != hipSuccess) { hip_fail(e, "hipMalloc"); destroy(s); live = nullptr; return rc; }
-    const size_t io = io_doubles(s);
-    if ((e = hipMalloc(reinterpret_cast<void **>(&s->d_io), sizeof(double) * io)) != hipSuccess) { hip_fail(e, "hipMalloc"); destroy(s); live = nullptr; return rc; }
-    if ((e = hipHostMalloc(reinterpret_cast<void **>(&s->h_pin), sizeof(double) * io, hipHostMallocDefault)) != hipSuccess) { hip_fail(e, "hipHostMalloc"); destroy(s); live = nullptr; return rc; }
-    *out = s;
-    live = nullptr;
+    if ((e = s->d_frames.alloc(sizeof(double) * fr)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    const size_t io = io_doubles(s.get());
+    if ((e = s->d_io.alloc(sizeof(double) * io)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    if ((e = s->h_pin.alloc(sizeof(double) * io, hipHostMallocDefault)) != hipSuccess) return hip_fail(e, "hipHostMalloc");
+    *out = s.release();
     return VG_OK;
-}
-
-// std::vector growth inside the set-up may throw; nothing may cross the extern "C" boundary
-inline int create(vg_reproject_set **out, int device, void *hip_stream, int model, const double *intr, const double *xb, bool sparse,
-                  int64_t n_blocks, const int64_t *offsets, const double *x1, const double *x2, const double *p2, const double *size)
-{
-    vg_reproject_set *live = nullptr;
-    try {
-        return create_unguarded(out, device, hip_stream, model, intr, xb, sparse, n_blocks, offsets, x1, x2, p2, size, live);
-    } catch (const std::exception &e) {
-        destroy(live);
-        if (out) *out = nullptr;
-        return fail(VG_ERR_ALLOC, std::string("out of host memory while building the block set: ") + e.what());
-    }
+} catch (const std::exception &e) {
+    if (out) *out = nullptr;
+    return fail(VG_ERR_ALLOC, std::string("out of host memory while building the block set: ") + e.what());
 }
 
 constexpr size_t kLocalLds = sizeof(double) * (vg::kEmitThreads / vg::kWave) * 2 * vg::kWave * 6;
@@ -337,12 +302,7 @@ int vg_camera_jacobian_evaluate(int device, void *hip_stream, int model, const d
     if (!intrinsics || !T12 || n < 0 || (n > 0 && !X2)) return vgi::fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (dfdxi && !grad) return vgi::fail(VG_ERR_INVALID_ARGUMENT, "dfdxi needs the image gradient");
     if (n >= (1ll << 31)) return vgi::fail(VG_ERR_INVALID_ARGUMENT, "too many points");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        (void)hipGetLastError();
-        return vgi::fail(VG_ERR_NO_DEVICE, "no HIP device: CameraJacobian has no CPU fallback");
-    }
-    if (device < 0 || device >= n_dev) return vgi::fail(VG_ERR_INVALID_ARGUMENT, "device index out of range");
+    if (const int rc = vgi::check_device(device, "CameraJacobian")) return rc;
     if (!n || (!dpdxi && !dfdxi)) return VG_OK;
     VG_HIP(hipSetDevice(device));
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);

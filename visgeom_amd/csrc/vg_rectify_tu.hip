@@ -16,17 +16,6 @@ using vgi::fail;
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-int check_device(int device, const char *what)
-{
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        (void)hipGetLastError();
-        return fail(VG_ERR_NO_DEVICE, std::string("no HIP device: ") + what + " has no CPU fallback");
-    }
-    if (device < 0 || device >= n_dev) return fail(VG_ERR_INVALID_ARGUMENT, "device index out of range");
-    return VG_OK;
-}
-
 bool valid_dim(int d) { return d >= 1 && d <= vg::kRectMaxDim; }
 
 template <int MODEL>
@@ -72,7 +61,7 @@ int vg_rectify_map(int device, void *hip_stream, int model, const double *intrin
         return fail(VG_ERR_INVALID_ARGUMENT, "pinhole width / height must be integers in [1, 16384]");
     if (!(std::isfinite(pinhole5[2]) && std::isfinite(pinhole5[3]) && std::isfinite(pinhole5[4]) && pinhole5[4] != 0.))
         return fail(VG_ERR_INVALID_ARGUMENT, "pinhole u0, v0, f must be finite and f non-zero");
-    if (const int rc = check_device(device, "rectification")) return rc;
+    if (const int rc = vgi::check_device(device, "rectification")) return rc;
     vg::RectifyMapArgs a;
     for (int k = 0; k < 10; k++) a.intr[k] = k < K ? intrinsics[k] : 0.;
     const vg::RotTrig g = vg::rot_trig(xi6 + 3, true, false);
@@ -106,7 +95,7 @@ int vg_remap(int device, void *hip_stream, int pixel_type, int channels, int64_t
     if (!valid_dim(src_w) || !valid_dim(src_h) || !valid_dim(map_w) || !valid_dim(map_h))
         return fail(VG_ERR_INVALID_ARGUMENT, "image and map sides must be in [1, 16384]");
     if (!map_x || !map_y || (n_images > 0 && (!src || !dst))) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (const int rc = check_device(device, "remap")) return rc;
+    if (const int rc = vgi::check_device(device, "remap")) return rc;
     if (n_images == 0) return VG_OK;
     vg::RemapArgs a;
     a.src = src;

@@ -17,87 +17,63 @@ namespace {
 // HBM (a vg_problem's dataset, the calibration front end's CornerBlock) there is no observation traffic at all.
 struct RefineScratch {
     int device = -1;
-    char *dev = nullptr, *pin = nullptr, *pin_dev = nullptr;   // pin_dev: the pinned block as the device addresses it
+    vgi::DeviceMem<char> dev;
+    vgi::PinnedMem<char> pin;
+    char *pin_dev = nullptr;   // the pinned block as the device addresses it
     size_t cap = 0, dev_cap = 0;
-    double *d_obs = nullptr;   // the host-pointer entry's observations (grow-only)
+    vgi::DeviceMem<double> d_obs;   // the host-pointer entry's observations (grow-only)
     size_t obs_cap = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    vgi::Event e0, e1;
     // pinned ping-pong staging of vgi::upload_corners
-    char *stage = nullptr;
+    vgi::PinnedMem<char> stage;
     size_t stage_half = 0;
-    hipEvent_t stage_done[2] = {nullptr, nullptr};
-    void drop()
-    {
-        if (dev) (void)hipFree(dev);
-        if (pin) (void)hipHostFree(pin);
-        if (d_obs) (void)hipFree(d_obs);
-        if (stage) (void)hipHostFree(stage);
-        for (hipEvent_t e : {e0, e1, stage_done[0], stage_done[1]})
-            if (e) (void)hipEventDestroy(e);
-        *this = RefineScratch();
-    }
+    vgi::Event stage_done[2];
 };
 std::mutex g_refine_m;
-RefineScratch g_refine;
+RefineScratch &g_refine = *new RefineScratch();   // never destroyed: no HIP call at process exit, when the runtime may be gone
 
 int refine_scratch_for(int device, size_t bytes, size_t obs_bytes, size_t front_bytes = 0)
 {
     RefineScratch &r = g_refine;
-    if (r.device != device) r.drop();
+    if (r.device != device) r = RefineScratch();
     r.device = device;
     if (front_bytes > r.dev_cap) {   // the device block holds the front only: counter, intrinsics, board
-        if (r.dev) (void)hipFree(r.dev);
-        r.dev = nullptr;
         r.dev_cap = 0;
         const size_t want = front_bytes < 64 * 1024 ? (size_t)64 * 1024 : front_bytes * 2;
-        VG_HIP(hipMalloc(&r.dev, want));
+        VG_HIP(r.dev.alloc(want));
         r.dev_cap = want;
     }
     if (bytes > r.cap) {
-        if (r.pin) (void)hipHostFree(r.pin);
-        r.pin = r.pin_dev = nullptr;
+        r.pin_dev = nullptr;
         r.cap = 0;
         const size_t want = bytes + bytes / 4 + 4096;
-        VG_HIP(hipHostMalloc(&r.pin, want, hipHostMallocMapped));
+        VG_HIP(r.pin.alloc(want, hipHostMallocMapped));
         VG_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&r.pin_dev), r.pin, 0));
         r.cap = want;
     }
     if (obs_bytes > r.obs_cap) {
-        if (r.d_obs) (void)hipFree(r.d_obs);
-        r.d_obs = nullptr;
         r.obs_cap = 0;
-        VG_HIP(hipMalloc(&r.d_obs, obs_bytes));
+        VG_HIP(r.d_obs.alloc(obs_bytes));
         r.obs_cap = obs_bytes;
     }
-    if (!r.e0) {
-        VG_HIP(hipEventCreate(&r.e0));
-        VG_HIP(hipEventCreate(&r.e1));
+    if (!r.e0) {   // both events or neither: a failure leaves no half-made pair behind
+        vgi::Event e0, e1;
+        VG_HIP(e0.create());
+        VG_HIP(e1.create());
+        r.e0 = std::move(e0);
+        r.e1 = std::move(e1);
     }
     return VG_OK;
 }
 
 inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
-int check_refine_device(int device)
-{
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
-        return vgi::fail(VG_ERR_NO_DEVICE, "no HIP device available; visgeom_amd has no CPU fallback");
-    if (device < 0 || device >= n_dev) return vgi::fail(VG_ERR_INVALID_ARGUMENT, "device index out of range");
-    return VG_OK;
-}
-
 }  // namespace
 
 void vgi::refine_release_cached()
 {
     std::lock_guard<std::mutex> lk(g_refine_m);
-    g_refine.drop();
-}
-
-vgi::CornerBlock::~CornerBlock()
-{
-    if (d_obs) (void)hipFree(d_obs);
+    g_refine = RefineScratch();
 }
 
 // The corners of a dataset into HBM, ONCE: `gather(first, count, dst)` writes images [first, first + count) as [image][N][2]
@@ -105,7 +81,7 @@ vgi::CornerBlock::~CornerBlock()
 int vgi::upload_corners(int device, void *hip_stream, int64_t n_images, int n_points, const GatherFn &gather, std::shared_ptr<CornerBlock> *out)
 {
     if (!out || n_images < 0 || n_points <= 0) return fail(VG_ERR_INVALID_ARGUMENT, "bad corner block");
-    const int rc0 = check_refine_device(device);
+    const int rc0 = check_device(device, "visgeom_amd");
     if (rc0 != VG_OK) return rc0;
     VG_HIP(hipSetDevice(device));
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
@@ -114,25 +90,27 @@ int vgi::upload_corners(int device, void *hip_stream, int64_t n_images, int n_po
     blk->n_images = n_images;
     blk->N = n_points;
     const size_t per_image = sizeof(double) * 2 * (size_t)n_points;
-    VG_HIP(hipMalloc(&blk->d_obs, per_image * (size_t)(n_images ? n_images : 1)));
+    VG_HIP(blk->d_obs.alloc(per_image * (size_t)(n_images ? n_images : 1)));
     std::lock_guard<std::mutex> lk(g_refine_m);
     RefineScratch &r = g_refine;
-    if (r.device != device) r.drop();
+    if (r.device != device) r = RefineScratch();
     r.device = device;
     const size_t half = (size_t)8 << 20;   // pinning costs ~80 us per MiB once: 16 MiB of staging, two chunks for 10 k images
-    if (!r.stage) {
-        VG_HIP(hipHostMalloc(&r.stage, 2 * half, hipHostMallocDefault));
+    if (!r.stage) {   // published only once the block and both its events exist
+        vgi::PinnedMem<char> stage;
+        vgi::Event done0, done1;
+        VG_HIP(stage.alloc(2 * half, hipHostMallocDefault));
+        VG_HIP(done0.create(hipEventDisableTiming));
+        VG_HIP(done1.create(hipEventDisableTiming));
+        r.stage = std::move(stage);
         r.stage_half = half;
-        VG_HIP(hipEventCreateWithFlags(&r.stage_done[0], hipEventDisableTiming));
-        VG_HIP(hipEventCreateWithFlags(&r.stage_done[1], hipEventDisableTiming));
+        r.stage_done[0] = std::move(done0);
+        r.stage_done[1] = std::move(done1);
     }
     const int64_t per_chunk = (int64_t)(r.stage_half / per_image);
     if (per_chunk < 1) return fail(VG_ERR_INVALID_ARGUMENT, "a single image's corners exceed the staging buffer");
     // whichever way this is left, nothing of the library's staging may still be on the bus when the next caller fills it
-    struct Drain {
-        hipStream_t st;
-        ~Drain() { (void)hipStreamSynchronize(st); }
-    } drain{st};
+    vgi::StreamDrain drain{st};
     bool used[2] = {false, false};
     int k = 0;
     for (int64_t first = 0; first < n_images; first += per_chunk, k ^= 1) {
@@ -191,14 +169,7 @@ int vgi::refine_poses_resident(int device, void *hip_stream, int model, const do
     if (!d_board) std::memcpy(r.pin + o_board, h_board, sizeof(double) * 3 * N);
     std::memcpy(r.pin + o_poses, poses, sizeof(double) * 6 * n);
     // from here on work that reads and writes the library's own blocks is queued: no way out of this function without draining it
-    struct Drain {
-        hipStream_t st;
-        bool armed;
-        ~Drain()
-        {
-            if (armed) (void)hipStreamSynchronize(st);
-        }
-    } drain{st, true};
+    vgi::StreamDrain drain{st};
     VG_HIP(hipMemcpyAsync(r.dev, r.pin, o_poses, hipMemcpyHostToDevice, st));   // counter, intrinsics, board: ONE small copy
     vg::PoseLmArgs a;
     a.board = d_board ? d_board : reinterpret_cast<const double *>(r.dev + o_board);
@@ -280,7 +251,7 @@ int vgi::refine_poses(int device, void *hip_stream, int model, const double *int
     if (!intrinsics || !board || n_points <= 0 || n_images < 0 || (n_images > 0 && (!corners || !poses)))
         return fail(VG_ERR_INVALID_ARGUMENT, "NULL / empty argument");
     if (n_images > 0x3fffffff) return fail(VG_ERR_INVALID_ARGUMENT, "too many images for one launch");
-    const int rc0 = check_refine_device(device);
+    const int rc0 = check_device(device, "visgeom_amd");
     if (rc0 != VG_OK) return rc0;
     if (!n_images) return VG_OK;
     VG_HIP(hipSetDevice(device));

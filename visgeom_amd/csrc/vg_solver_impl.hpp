@@ -101,7 +101,7 @@ void vg_release_cached_memory(void)
 {
     {
         std::lock_guard<std::mutex> lk(g_arena_cache.m);
-        g_arena_cache.drop();
+        g_arena_cache.b = ArenaBlocks();
     }
     vgi::refine_release_cached();
 }

@@ -56,51 +56,43 @@ struct SolveArena {
     }
 };
 
+// a device block and a pinned block of one solve, with their capacities
+struct ArenaBlocks {
+    vgi::DeviceMem<char> dev;
+    vgi::PinnedMem<char> pin;
+    size_t dev_cap = 0, pin_cap = 0;
+};
+
 struct ArenaCache {
     std::mutex m;
-    char *dev = nullptr, *pin = nullptr;
-    size_t dev_cap = 0, pin_cap = 0;
+    ArenaBlocks b;
     int device = -1;
-    void drop()
-    {
-        // (hipFree takes the pointer's own device: the calling thread's current device is not touched -- a torch caller relies
-        //  on its own)
-        if (dev) (void)hipFree(dev);
-        if (pin) (void)hipHostFree(pin);
-        dev = pin = nullptr;
-        dev_cap = pin_cap = 0;
-    }
 };
-ArenaCache g_arena_cache;
+ArenaCache &g_arena_cache = *new ArenaCache();   // never destroyed: no HIP call at process exit, when the runtime may be gone
 thread_local SolveArena *t_arena = nullptr;
 
 // takes the cached blocks when they are large enough, allocates otherwise; the destructor hands the blocks back
 struct ArenaScope {
     SolveArena a;
+    ArenaBlocks own;       // the blocks a points into
     bool discard = false;  // set when the solve's stream could not be drained: the blocks are freed, never cached
     ArenaScope(int device, size_t dev_need, size_t pin_need, size_t up_cap)
     {
         {
             std::lock_guard<std::mutex> lk(g_arena_cache.m);
-            if (g_arena_cache.dev && g_arena_cache.device == device && g_arena_cache.dev_cap >= dev_need && g_arena_cache.pin_cap >= pin_need) {
-                a.dev = g_arena_cache.dev;
-                a.pin = g_arena_cache.pin;
-                a.dev_cap = g_arena_cache.dev_cap;
-                a.pin_cap = g_arena_cache.pin_cap;
-                g_arena_cache.dev = g_arena_cache.pin = nullptr;
-                g_arena_cache.dev_cap = g_arena_cache.pin_cap = 0;
-            }
+            const ArenaBlocks &c = g_arena_cache.b;
+            if (c.dev && g_arena_cache.device == device && c.dev_cap >= dev_need && c.pin_cap >= pin_need) std::swap(own, g_arena_cache.b);
         }
-        if (!a.dev) {
-            if (hipMalloc(reinterpret_cast<void **>(&a.dev), dev_need) != hipSuccess) a.dev = nullptr;
-            if (a.dev && hipHostMalloc(reinterpret_cast<void **>(&a.pin), pin_need, hipHostMallocCoherent) != hipSuccess) {
-                (void)hipFree(a.dev);
-                a.dev = a.pin = nullptr;
-            }
+        if (!own.dev) {
+            if (own.dev.alloc(dev_need) == hipSuccess && own.pin.alloc(pin_need, hipHostMallocCoherent) != hipSuccess) (void)own.dev.release();
             (void)hipGetLastError();  // a failed block only means: every buffer takes its own allocation
-            a.dev_cap = a.dev ? dev_need : 0;
-            a.pin_cap = a.pin ? pin_need : 0;
+            own.dev_cap = own.dev ? dev_need : 0;
+            own.pin_cap = own.pin ? pin_need : 0;
         }
+        a.dev = own.dev;
+        a.pin = own.pin;
+        a.dev_cap = own.dev_cap;
+        a.pin_cap = own.pin_cap;
         a.device = device;
         a.up_cap = up_cap < a.dev_cap && up_cap < a.pin_cap ? up_cap : 0;
         a.dev_used = a.pin_used = a.up_cap;
@@ -113,16 +105,9 @@ struct ArenaScope {
         std::lock_guard<std::mutex> lk(g_arena_cache.m);
         // keep the pair that serves more solves: a hit needs BOTH capacities, so a pair replaces the cached one only when it
         // is at least as large in both (or nothing is cached)
-        if (!discard && a.dev_cap >= g_arena_cache.dev_cap && a.pin_cap >= g_arena_cache.pin_cap) {
-            g_arena_cache.drop();
-            g_arena_cache.dev = a.dev;
-            g_arena_cache.pin = a.pin;
-            g_arena_cache.dev_cap = a.dev_cap;
-            g_arena_cache.pin_cap = a.pin_cap;
+        if (!discard && own.dev_cap >= g_arena_cache.b.dev_cap && own.pin_cap >= g_arena_cache.b.pin_cap) {
+            g_arena_cache.b = std::move(own);
             g_arena_cache.device = a.device;
-        } else {
-            (void)hipFree(a.dev);
-            (void)hipHostFree(a.pin);
         }
     }
     ArenaScope(const ArenaScope &) = delete;
@@ -132,17 +117,13 @@ struct ArenaScope {
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
-    bool owned = false;
-    ~DevBuf()
-    {
-        if (p && owned) (void)hipFree(p);
-    }
+    vgi::DeviceMem<T> own;   // when the solve's arena had no room
     int alloc(size_t n)
     {
         const size_t bytes = sizeof(T) * (n ? n : 1);
         if (t_arena && (p = static_cast<T *>(t_arena->dev_alloc(bytes))) != nullptr) return VG_OK;
-        VG_HIP(hipMalloc(&p, bytes));
-        owned = true;
+        VG_HIP(own.alloc(bytes));
+        p = own;
         return VG_OK;
     }
     int upload(const std::vector<T> &h)
@@ -159,18 +140,14 @@ struct DevBuf {
 struct PinnedBuf {
     double *p = nullptr;
     size_t n = 0;
-    bool owned = false;
-    ~PinnedBuf()
-    {
-        if (p && owned) (void)hipHostFree(p);
-    }
+    vgi::PinnedMem<double> own;   // when the solve's arena had no room
     int alloc(size_t count)
     {
         n = count;
         const size_t bytes = sizeof(double) * (count ? count : 1);
         if (t_arena && (p = static_cast<double *>(t_arena->pin_alloc(bytes))) != nullptr) return VG_OK;
-        VG_HIP(hipHostMalloc(reinterpret_cast<void **>(&p), bytes, hipHostMallocCoherent));   // the host spins on words kernels store here
-        owned = true;
+        VG_HIP(own.alloc(bytes, hipHostMallocCoherent));   // the host spins on words kernels store here
+        p = own;
         return VG_OK;
     }
 };

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -20,17 +21,6 @@ namespace {
 using vgi::fail;
 
 constexpr int64_t kStereoBudget = int64_t(2) << 30;   // device scratch of one chunk, bytes (one pair more if it is larger)
-
-int check_device(int device)
-{
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
-        (void)hipGetLastError();
-        return fail(VG_ERR_NO_DEVICE, "no HIP device: stereo has no CPU fallback");
-    }
-    if (device < 0 || device >= n_dev) return fail(VG_ERR_INVALID_ARGUMENT, "device index out of range");
-    return VG_OK;
-}
 
 void limit_vector(double *x)   // limitVector (epipoles.cpp:27-35)
 {
@@ -86,9 +76,9 @@ struct vg_stereo {
     hipStream_t stream = nullptr;
     vg_stereo_params prm;
     vgs::StereoGeom g;
-    vgs::Poly2 *d_table = nullptr;
-    vgs::GeomEntry *d_geom = nullptr;
-    void *d_scratch = nullptr;
+    vgi::DeviceMem<vgs::Poly2> d_table;
+    vgi::DeviceMem<vgs::GeomEntry> d_geom;
+    vgi::DeviceMem<void> d_scratch;
     int64_t scratch_bytes = 0;
     int64_t P = 0;
 
@@ -251,10 +241,9 @@ struct Bufs {
 int ensure_scratch(vg_stereo *s, int64_t bytes)
 {
     if (bytes <= s->scratch_bytes) return VG_OK;
-    if (s->d_scratch) VG_HIP(hipFree(s->d_scratch));
-    s->d_scratch = nullptr;
     s->scratch_bytes = 0;
-    VG_HIP(hipMalloc(&s->d_scratch, (size_t)bytes));
+    VG_HIP(s->d_scratch.release());
+    VG_HIP(s->d_scratch.alloc((size_t)bytes));
     s->scratch_bytes = bytes;
     return VG_OK;
 }
@@ -264,7 +253,7 @@ int scratch_bufs(vg_stereo *s, int64_t n, Bufs &b)
 {
     const int64_t P = s->P, D = s->prm.disp_max;
     if (const int rc = ensure_scratch(s, n * s->per_pair())) return rc;
-    char *p = static_cast<char *>(s->d_scratch);
+    char *p = static_cast<char *>(s->d_scratch.get());
     b.sum = reinterpret_cast<int32_t *>(p);
     p += n * P * D * 4;
     b.disp = reinterpret_cast<int32_t *>(p);
@@ -379,7 +368,7 @@ int vg_stereo_create(vg_stereo **out, int device, void *hip_stream, const double
     if (eucm1[2] == 0. || eucm1[3] == 0. || eucm2[2] == 0. || eucm2[3] == 0.) return fail(VG_ERR_INVALID_ARGUMENT, "fu, fv must be non-zero");
     if (!(xi12[0] * xi12[0] + xi12[1] * xi12[1] + xi12[2] * xi12[2] > 1e-10))
         return fail(VG_ERR_INVALID_ARGUMENT, "the stereo baseline must not vanish (|t|^2 > 1e-10)");
-    vg_stereo *s = new (std::nothrow) vg_stereo();
+    std::unique_ptr<vg_stereo> s(new (std::nothrow) vg_stereo());
     if (!s) return fail(VG_ERR_ALLOC, "out of host memory");
     s->prm = *params;
     s->prm.x_max = x_max;
@@ -388,31 +377,21 @@ int vg_stereo_create(vg_stereo **out, int device, void *hip_stream, const double
     s->g.y_max = y_max;
     s->P = (int64_t)x_max * y_max;
     std::vector<vgs::Poly2> table;
-    if (const int rc = build_geometry(*s, eucm1, eucm2, xi12, table)) {
-        delete s;
-        return rc;
-    }
-    if (const int rc = check_device(device)) {
-        delete s;
-        return rc;
-    }
+    if (const int rc = build_geometry(*s, eucm1, eucm2, xi12, table)) return rc;
+    if (const int rc = vgi::check_device(device, "stereo")) return rc;
     s->device = device;
     s->stream = reinterpret_cast<hipStream_t>(hip_stream);
-    auto undo = [&](int rc) {
-        vg_stereo_destroy(s);
-        return rc;
-    };
-    if (hipSetDevice(device) != hipSuccess) return undo(fail(VG_ERR_HIP, "hipSetDevice failed"));
-    if (hipMalloc(&s->d_table, table.size() * sizeof(vgs::Poly2)) != hipSuccess ||
-        hipMalloc(&s->d_geom, (size_t)s->P * sizeof(vgs::GeomEntry)) != hipSuccess)
-        return undo(fail(VG_ERR_ALLOC, "device allocation of the stereo geometry failed"));
+    if (hipSetDevice(device) != hipSuccess) return fail(VG_ERR_HIP, "hipSetDevice failed");
+    vgi::StreamDrain drain{s->stream};   // a failure below drains the stream before s is freed
+    if (s->d_table.alloc(table.size() * sizeof(vgs::Poly2)) != hipSuccess || s->d_geom.alloc((size_t)s->P * sizeof(vgs::GeomEntry)) != hipSuccess)
+        return fail(VG_ERR_ALLOC, "device allocation of the stereo geometry failed");
     if (hipMemcpyAsync(s->d_table, table.data(), table.size() * sizeof(vgs::Poly2), hipMemcpyHostToDevice, s->stream) != hipSuccess)
-        return undo(fail(VG_ERR_HIP, "curve table upload failed"));
+        return fail(VG_ERR_HIP, "curve table upload failed");
     s->g.table = s->d_table;
     hipLaunchKernelGGL(vgs::stereo_geometry_kernel, dim3(blocks_of(s->P, 256)), dim3(256), 0, s->stream, s->g, s->d_geom);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess)
-        return undo(fail(VG_ERR_HIP, "stereo geometry kernel failed"));
-    *out = s;
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess) return fail(VG_ERR_HIP, "stereo geometry kernel failed");
+    drain.armed = false;
+    *out = s.release();
     return VG_OK;
 }
 
@@ -421,9 +400,6 @@ void vg_stereo_destroy(vg_stereo *s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->stream);
-    if (s->d_table) (void)hipFree(s->d_table);
-    if (s->d_geom) (void)hipFree(s->d_geom);
-    if (s->d_scratch) (void)hipFree(s->d_scratch);
     delete s;
 }
 
@@ -479,7 +455,7 @@ int vg_stereo_aggregate(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, cons
     const int64_t np = n_pairs * s->P;
     if (const int rc = ensure_scratch(s, np * (s->prm.disp_max + 3) + (disparity ? 0 : np * 4))) return rc;
     Bufs b;
-    b.err = static_cast<uint8_t *>(s->d_scratch);
+    b.err = static_cast<uint8_t *>(s->d_scratch.get());
     b.step = b.err + np * s->prm.disp_max;
     b.sal = b.step + np;
     b.skip = b.sal + np;
