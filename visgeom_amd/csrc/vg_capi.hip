@@ -81,6 +81,15 @@ int64_t emit_nt_min_bytes()
     return h ? (int64_t)h : (int64_t)230000000;
 }
 
+// Store policy of a single-dataset emit launch by its output: non-temporal past the Infinity Cache (emit_nt_min_bytes), write-through
+// inside it.  Write-through (`sc1`) leaves no dirty Jacobian lines in the XCD L2s for the launch's end to wait on
+// (profiles/r10_emit_store_policy.txt).  hook emit_write_through: -1 = plain stores inside the cache (the policy before), 0 = the default.
+int emit_store_policy(int64_t launch_output_bytes)
+{
+    if (launch_output_bytes >= emit_nt_min_bytes()) return vg::kStoreNonTemporal;
+    return vgi::debug_hook(vgi::kHookEmitWriteThrough) < 0 ? vg::kStorePlain : vg::kStoreWriteThrough;
+}
+
 // Tile map of an emit launch by its output: one contiguous eighth per XCD while the launch stays inside or near the Infinity Cache
 // (<= 1.2 GB: same box, alternating, the eighths are level with the windows for EUCM and 2 % ahead for Mei at 10 k images,
 // profiles/r06l_headline_map_ab.txt), windows of 8 x kEmitMapWindow tiles beyond, where the eighths fall into their slow mode on
@@ -169,7 +178,7 @@ void fill_emit_args_at(const vg_problem *p, const Dataset &d, vg::EmitArgs &a, i
     a.chain_stride = d.L ? d.chain.stride[0] : 0;
     a.seq_index = d.seq_identity ? nullptr : d.d_seq + b0;
     a.first_block = b0;
-    a.nt_stores = emit_output_bytes(a, cam.K) >= emit_nt_min_bytes() ? 1 : 0;  // a merged launch decides for all its datasets together
+    a.nt_stores = emit_store_policy(emit_output_bytes(a, cam.K));  // a merged launch decides for all its datasets together (plain or non-temporal)
     a.map_window = emit_map_window(emit_output_bytes(a, cam.K));   // likewise
 }
 
@@ -192,7 +201,8 @@ namespace {
 long long g_debug_hooks[vgi::kHookCount] = {0};
 const char *const kDebugHookNames[vgi::kHookCount] = {"inline_chain_max_bytes", "gram_no_merge", "max_obs_per_launch", "solver_timing",
                                                       "solver_host_loop", "solver_device_loop", "solver_no_fold_frames", "solver_fold_max_groups",
-                                                      "emit_nt_min_bytes", "host_chunk_bytes", "gram_persistent", "emit_map_window"};
+                                                      "emit_nt_min_bytes", "host_chunk_bytes", "gram_persistent", "emit_map_window",
+                                                      "emit_write_through"};
 }  // namespace
 long long vgi::debug_hook(vgi::DebugHook h) { return g_debug_hooks[h]; }
 #endif

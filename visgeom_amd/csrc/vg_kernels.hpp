@@ -159,7 +159,7 @@ struct EmitArgs {
     unsigned int N;
     int L;
     int frame_stride_d;
-    int nt_stores;         // 1: the launch's output streams past the Infinity Cache -> non-temporal stores (stream_store16)
+    int nt_stores;         // store policy of the launch (EmitStorePolicy): 1 = past the Infinity Cache, non-temporal; 2 = inside it, write-through
     unsigned int map_window;  // tile map of the launch: 0 = every XCD one contiguous eighth of the tiles; W > 0 = windows of 8 W tiles,
                               // XCD x the x-th run of W tiles in each window (W = 1: the linear map); xcd_window_block, kEmitMapWindow
 };
@@ -174,11 +174,21 @@ struct EmitArgs {
 // A launch that streams past the cache sets the hint: a line kept behind the write only displaces the next lines of the same
 // stream (same box, alternating builds, profiles/r05c_emit_sweep_ab.txt: EUCM 12.5 k images = 250 MB 57 -> 45 us, 25 k 105 -> 83,
 // 50 k = 1 GB 201 -> 159 us, 0.67 -> 0.84 of the HBM peak; inside the cache the hint costs: 10 k images 36 -> 41 us).
-__device__ __forceinline__ void stream_store16(HIP_vector_type<double, 2> *dst, const HIP_vector_type<double, 2> &v, bool nt)
+// A launch inside the cache can instead write through (kStoreWriteThrough, `sc1`): the lines leave the XCD's L2 as they are
+// written instead of staying dirty behind the write, and the 215 MB headline write ran 31.0 -> 29.9 us that way
+// (tools/exp/store_policy.hip, profiles/r10_emit_store_policy.txt).
+enum EmitStorePolicy { kStorePlain = 0, kStoreNonTemporal = 1, kStoreWriteThrough = 2 };
+
+__device__ __forceinline__ void stream_store16(HIP_vector_type<double, 2> *dst, const HIP_vector_type<double, 2> &v, int policy)
 {
-    if (nt) {
+    if (policy == kStoreNonTemporal) {
         __builtin_nontemporal_store(v.x, &dst->x);
         __builtin_nontemporal_store(v.y, &dst->y);
+    } else if (policy == kStoreWriteThrough) {
+        // hipcc has no builtin for a flat-address `sc1` store; the trailing nop keeps the data registers intact until the store
+        // has read them (the compiler does not pad an asm statement's hazards)
+        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(__builtin_bit_cast(u4, v)) : "memory");
     } else {
         *dst = v;
     }
@@ -186,7 +196,7 @@ __device__ __forceinline__ void stream_store16(HIP_vector_type<double, 2> *dst, 
 
 template <int S>
 __device__ __forceinline__ void wave_store_rows(double *__restrict__ stage, const double *vals,
-                                                double *__restrict__ out_tile, int n_valid_obs, int lane, bool nt = false)
+                                                double *__restrict__ out_tile, int n_valid_obs, int lane, int nt = kStorePlain)
 {
     using d2 = HIP_vector_type<double, 2>;
     d2 *st = reinterpret_cast<d2 *>(stage);
@@ -228,7 +238,7 @@ constexpr int emit_stage_doubles_per_wave()
 // 32 * 16 * S contiguous bytes out, h = 0, 1.
 template <int S>
 __device__ __forceinline__ void wave_store_rows_halves(double *__restrict__ stage, const double *vals,
-                                                       double *__restrict__ out_tile, int n_valid_obs, int lane, bool nt = false)
+                                                       double *__restrict__ out_tile, int n_valid_obs, int lane, int nt = kStorePlain)
 {
     static_assert(S <= 2 * kStageRowDoubles, "half a wave of rows must fit the tile");
     using d2 = HIP_vector_type<double, 2>;
@@ -364,7 +374,7 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
     d2 r;
     r.x = e.ok ? e.u - ob.x : kDoubleBig;
     r.y = e.ok ? e.v - ob.y : kDoubleBig;
-    if (active) stream_store16(reinterpret_cast<d2 *>(a.res) + o, r, a.nt_stores != 0);
+    if (active) stream_store16(reinterpret_cast<d2 *>(a.res) + o, r, a.nt_stores);
 
     if (a.failed) {
         // Failures are rare: the counter is never zeroed (an 8-byte hipMemsetAsync is a whole 5 us fill
@@ -396,8 +406,8 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
                 rows[i] = e.Ju[i];
                 rows[K + i] = e.Jv[i];
             }
-            if (K > kStageRowDoubles) wave_store_rows_halves<K>(stage, rows, a.jac_intr + (size_t)ow * (2 * K), n_valid, lane, a.nt_stores != 0);
-            else wave_store_rows<(K > kStageRowDoubles ? 1 : K)>(stage, rows, a.jac_intr + (size_t)ow * (2 * K), n_valid, lane, a.nt_stores != 0);
+            if (K > kStageRowDoubles) wave_store_rows_halves<K>(stage, rows, a.jac_intr + (size_t)ow * (2 * K), n_valid, lane, a.nt_stores);
+            else wave_store_rows<(K > kStageRowDoubles ? 1 : K)>(stage, rows, a.jac_intr + (size_t)ow * (2 * K), n_valid, lane, a.nt_stores);
         }
         // pose blocks, u-row at +12i, v-row at +12i+6       calib_cost_functions.cpp:93-101
         for (int l = 0; l < a.L; l++) {
@@ -405,7 +415,7 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
             if (!Jm) continue;
             double rows[12];
             pose_rows(e.P, X0, X1, X2, fr + 12 + 21 * l, rows);
-            wave_store_rows<6>(stage, rows, Jm + (size_t)ow * 12, n_valid, lane, a.nt_stores != 0);
+            wave_store_rows<6>(stage, rows, Jm + (size_t)ow * 12, n_valid, lane, a.nt_stores);
         }
     }
 }
