@@ -116,6 +116,24 @@ bool emit_frames_in_lds(int N, int frame_stride)
     return (size_t)max_frames * frame_stride * sizeof(double) <= 32 * 1024;
 }
 
+// the store policy is a template argument of the emit kernels (one straight-line store sequence per tile): a.nt_stores picks the
+// instantiation
+template <int MODEL, bool WANT_JAC, bool FRAMES_LDS, bool INLINE_CHAIN>
+void launch_emit_policy(hipStream_t stream, const vg::EmitArgs &a, unsigned int grid, size_t lds)
+{
+    switch (a.nt_stores) {
+    case vg::kStoreNonTemporal:
+        hipLaunchKernelGGL((vg::vg_emit_kernel<MODEL, WANT_JAC, FRAMES_LDS, INLINE_CHAIN, vg::kStoreNonTemporal>), dim3(grid), dim3(vg::kEmitThreads), lds, stream, a);
+        break;
+    case vg::kStoreWriteThrough:
+        hipLaunchKernelGGL((vg::vg_emit_kernel<MODEL, WANT_JAC, FRAMES_LDS, INLINE_CHAIN, vg::kStoreWriteThrough>), dim3(grid), dim3(vg::kEmitThreads), lds, stream, a);
+        break;
+    default:
+        hipLaunchKernelGGL((vg::vg_emit_kernel<MODEL, WANT_JAC, FRAMES_LDS, INLINE_CHAIN, vg::kStorePlain>), dim3(grid), dim3(vg::kEmitThreads), lds, stream, a);
+        break;
+    }
+}
+
 template <int MODEL>
 int launch_emit(hipStream_t stream, const vg::EmitArgs &a, bool want_jac, bool inline_chain)
 {
@@ -123,21 +141,21 @@ int launch_emit(hipStream_t stream, const vg::EmitArgs &a, bool want_jac, bool i
     const size_t lds = emit_lds_bytes<MODEL>(want_jac, frames_lds, (int)a.N, a.frame_stride_d);
     const unsigned int grid = (a.n_obs + vg::kEmitThreads - 1) / vg::kEmitThreads;
     if (inline_chain) {  // the caller checked: one DIRECT member, frames fit the LDS
-        if (want_jac) hipLaunchKernelGGL((vg::vg_emit_kernel<MODEL, true, true, true>), dim3(grid), dim3(vg::kEmitThreads), lds, stream, a);
-        else hipLaunchKernelGGL((vg::vg_emit_kernel<MODEL, false, true, true>), dim3(grid), dim3(vg::kEmitThreads), lds, stream, a);
+        if (want_jac) launch_emit_policy<MODEL, true, true, true>(stream, a, grid, lds);
+        else launch_emit_policy<MODEL, false, true, true>(stream, a, grid, lds);
         VG_HIP(hipGetLastError());
         return VG_OK;
     }
     if (want_jac) {
         if (frames_lds)
-            hipLaunchKernelGGL((vg::vg_emit_kernel<MODEL, true, true>), dim3(grid), dim3(vg::kEmitThreads), lds, stream, a);
+            launch_emit_policy<MODEL, true, true, false>(stream, a, grid, lds);
         else
-            hipLaunchKernelGGL((vg::vg_emit_kernel<MODEL, true, false>), dim3(grid), dim3(vg::kEmitThreads), lds, stream, a);
+            launch_emit_policy<MODEL, true, false, false>(stream, a, grid, lds);
     } else {
         if (frames_lds)
-            hipLaunchKernelGGL((vg::vg_emit_kernel<MODEL, false, true>), dim3(grid), dim3(vg::kEmitThreads), lds, stream, a);
+            launch_emit_policy<MODEL, false, true, false>(stream, a, grid, lds);
         else
-            hipLaunchKernelGGL((vg::vg_emit_kernel<MODEL, false, false>), dim3(grid), dim3(vg::kEmitThreads), lds, stream, a);
+            launch_emit_policy<MODEL, false, false, false>(stream, a, grid, lds);
     }
     VG_HIP(hipGetLastError());
     return VG_OK;
@@ -794,7 +812,7 @@ int vg_problem_evaluate(vg_problem *p, const vg_dataset_outputs *outs)
             int64_t launch_bytes = 0;
             for (int k = 0; k < m.n; k++) launch_bytes += emit_output_bytes(m.ds[k], p->cams[p->dss[shared[g0 + k]].camera].K);
             for (int k = 0; k < m.n; k++) {
-                m.ds[k].nt_stores = launch_bytes >= emit_nt_min_bytes() ? 1 : 0;
+                m.ds[k].nt_stores = launch_bytes >= emit_nt_min_bytes() ? vg::kStoreNonTemporal : vg::kStorePlain;
                 m.ds[k].map_window = emit_map_window(launch_bytes);
             }
         }
@@ -803,7 +821,10 @@ int vg_problem_evaluate(vg_problem *p, const vg_dataset_outputs *outs)
         // stereo 21.1 -> 19.6 us, rig 116 (one contiguous piece of equal tile counts per die) / 108.5 (equal bytes) / 109.4 us)
         unsigned int longest = 0;
         for (int k = 0; k < m.n; k++) longest += (m.first_tile[k + 1] - m.first_tile[k] + 7) / 8;
-        hipLaunchKernelGGL(vg::vg_emit_multi_kernel, dim3(8 * longest), dim3(vg::kEmitThreads), lds, p->stream, m);
+        if (m.ds[0].nt_stores == vg::kStoreNonTemporal)
+            hipLaunchKernelGGL(vg::vg_emit_multi_kernel<vg::kStoreNonTemporal>, dim3(8 * longest), dim3(vg::kEmitThreads), lds, p->stream, m);
+        else
+            hipLaunchKernelGGL(vg::vg_emit_multi_kernel<vg::kStorePlain>, dim3(8 * longest), dim3(vg::kEmitThreads), lds, p->stream, m);
         VG_HIP(hipGetLastError());
     }
     for (int i : alone)

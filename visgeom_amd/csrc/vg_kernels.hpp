@@ -169,7 +169,7 @@ struct EmitArgs {
 // (16 B stores at a 16*S-byte lane stride) and the tile is then streamed out linearly, 16 B per lane
 // per store -> every global store instruction writes 1 KiB of consecutive bytes.
 // The 16-byte store of the output stream, plain or with the non-temporal hint (`global_store_dwordx4 ... nt`), chosen per LAUNCH by
-// the host (EmitArgs::nt_stores, a wave-uniform branch).  A launch whose output fits the 256 MiB Infinity Cache keeps plain
+// the host (EmitArgs::nt_stores, which selects the kernel instantiation).  A launch whose output fits the 256 MiB Infinity Cache keeps plain
 // stores: the consumer (second-pass Gram, a copy engine, the next evaluation overwriting the same rows) finds the lines there.
 // A launch that streams past the cache sets the hint: a line kept behind the write only displaces the next lines of the same
 // stream (same box, alternating builds, profiles/r05c_emit_sweep_ab.txt: EUCM 12.5 k images = 250 MB 57 -> 45 us, 25 k 105 -> 83,
@@ -179,12 +179,15 @@ struct EmitArgs {
 // (tools/exp/store_policy.hip, profiles/r10_emit_store_policy.txt).
 enum EmitStorePolicy { kStorePlain = 0, kStoreNonTemporal = 1, kStoreWriteThrough = 2 };
 
-__device__ __forceinline__ void stream_store16(HIP_vector_type<double, 2> *dst, const HIP_vector_type<double, 2> &v, int policy)
+// The policy is a template parameter (of the emit kernels, per launch): a tile's store sequence is straight-line code, not a
+// three-way dispatch per 16-byte store.
+template <int POLICY>
+__device__ __forceinline__ void stream_store16(HIP_vector_type<double, 2> *dst, const HIP_vector_type<double, 2> &v)
 {
-    if (policy == kStoreNonTemporal) {
+    if constexpr (POLICY == kStoreNonTemporal) {
         __builtin_nontemporal_store(v.x, &dst->x);
         __builtin_nontemporal_store(v.y, &dst->y);
-    } else if (policy == kStoreWriteThrough) {
+    } else if constexpr (POLICY == kStoreWriteThrough) {
         // hipcc has no builtin for a flat-address `sc1` store; the trailing nop keeps the data registers intact until the store
         // has read them (the compiler does not pad an asm statement's hazards)
         typedef unsigned int u4 __attribute__((ext_vector_type(4)));
@@ -194,9 +197,43 @@ __device__ __forceinline__ void stream_store16(HIP_vector_type<double, 2> *dst, 
     }
 }
 
-template <int S>
+// Streams the n16 16-byte words of a staged row block out, word idx = k * 64 + lane by store k.  Inside the Infinity Cache
+// (plain or write-through stores) the block's LDS reads are issued together ahead of its stores, which then wait on counted
+// lgkmcnt instead of one ds_read round trip each.  Reading the tile past n16 only reads stale LDS of the wave's own tile;
+// those words are not stored.  A full block (every wave of a launch but its last) stores unpredicated: with a per-lane
+// branch around each store the compiler would sink the first read into its branch, behind the others.
+// Non-temporal launches stream to DRAM and keep one LDS read per store: with the reads ahead the 2 GB launch (EUCM 100 k
+// images) ran 329 us against 290 us this way and 313 us before either (same box, alternating; profiles/r11_emit_waits.md).
+template <int NK, int POLICY>
+__device__ __forceinline__ void stream_tile_out(const HIP_vector_type<double, 2> *st, HIP_vector_type<double, 2> *dst, int n16, int lane)
+{
+    using d2 = HIP_vector_type<double, 2>;
+    if constexpr (POLICY == kStoreNonTemporal) {
+#pragma unroll
+        for (int k = 0; k < NK; k++) {
+            const int idx = k * kWave + lane;
+            if (idx < n16) stream_store16<POLICY>(dst + idx, st[idx]);
+        }
+        return;
+    }
+    d2 v[NK];
+#pragma unroll
+    for (int k = 0; k < NK; k++) v[k] = st[k * kWave + lane];
+    if (n16 >= NK * kWave) {
+#pragma unroll
+        for (int k = 0; k < NK; k++) stream_store16<POLICY>(dst + k * kWave + lane, v[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < NK; k++) {
+            const int idx = k * kWave + lane;
+            if (idx < n16) stream_store16<POLICY>(dst + idx, v[k]);
+        }
+    }
+}
+
+template <int S, int POLICY = kStorePlain>
 __device__ __forceinline__ void wave_store_rows(double *__restrict__ stage, const double *vals,
-                                                double *__restrict__ out_tile, int n_valid_obs, int lane, int nt = kStorePlain)
+                                                double *__restrict__ out_tile, int n_valid_obs, int lane)
 {
     using d2 = HIP_vector_type<double, 2>;
     d2 *st = reinterpret_cast<d2 *>(stage);
@@ -211,13 +248,7 @@ __device__ __forceinline__ void wave_store_rows(double *__restrict__ stage, cons
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const int n16 = n_valid_obs * S;
-    d2 *dst = reinterpret_cast<d2 *>(out_tile);
-#pragma unroll
-    for (int k = 0; k < S; k++) {
-        const int idx = k * kWave + lane;
-        if (idx < n16) stream_store16(dst + idx, st[idx], nt);
-    }
+    stream_tile_out<S, POLICY>(st, reinterpret_cast<d2 *>(out_tile), n_valid_obs * S, lane);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -236,9 +267,9 @@ constexpr int emit_stage_doubles_per_wave()
 
 // wave_store_rows for S > kStageRowDoubles: lanes [32h, 32h + 32) stage their rows, the whole wave streams the
 // 32 * 16 * S contiguous bytes out, h = 0, 1.
-template <int S>
+template <int S, int POLICY>
 __device__ __forceinline__ void wave_store_rows_halves(double *__restrict__ stage, const double *vals,
-                                                       double *__restrict__ out_tile, int n_valid_obs, int lane, int nt = kStorePlain)
+                                                       double *__restrict__ out_tile, int n_valid_obs, int lane)
 {
     static_assert(S <= 2 * kStageRowDoubles, "half a wave of rows must fit the tile");
     using d2 = HIP_vector_type<double, 2>;
@@ -260,13 +291,7 @@ __device__ __forceinline__ void wave_store_rows_halves(double *__restrict__ stag
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         int nv = n_valid_obs - h * kHalf;
         nv = nv < 0 ? 0 : (nv > kHalf ? kHalf : nv);
-        const int n16 = nv * S;
-        d2 *dst = reinterpret_cast<d2 *>(out_tile) + h * kHalf * S;
-#pragma unroll
-        for (int k = 0; k < (kHalf * S + kWave - 1) / kWave; k++) {
-            const int idx = k * kWave + lane;
-            if (idx < n16) stream_store16(dst + idx, st[idx], nt);
-        }
+        stream_tile_out<(kHalf * S + kWave - 1) / kWave, POLICY>(st, reinterpret_cast<d2 *>(out_tile) + h * kHalf * S, nv * S, lane);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -301,12 +326,51 @@ __device__ __forceinline__ unsigned int xcd_window_block(unsigned int b, unsigne
     return base + x * q + (x < r ? x : r) + i;
 }
 
+// The store sequence of one tile: its residual pair, then (WANT_JAC) the intrinsic and pose row blocks through the wave's LDS tile.
+// With the frames in LDS nothing in it waits on vmcnt from its first store on: every global load of the tile was consumed before it.
+template <int MODEL, bool WANT_JAC, int POLICY>
+__device__ __forceinline__ void emit_tile_stores(const EmitArgs &a, const unsigned int o0, bool active, const HIP_vector_type<double, 2> &r,
+                                                 const CornerEval<CameraTraits<MODEL>::K> &e, double X0, double X1, double X2,
+                                                 const double *fr, double *stage)
+{
+    constexpr int K = CameraTraits<MODEL>::K;
+    using d2 = HIP_vector_type<double, 2>;
+    const int lane = threadIdx.x & (kWave - 1);
+    if (active) stream_store16<POLICY>(reinterpret_cast<d2 *>(a.res) + o0 + threadIdx.x, r);
+
+    if (WANT_JAC) {
+        const unsigned int ow = o0 + (threadIdx.x & ~(kWave - 1));  // first observation of this wave
+        int n_valid = 0;
+        if (ow < a.n_obs) n_valid = (a.n_obs - ow < (unsigned)kWave) ? (int)(a.n_obs - ow) : kWave;
+
+        // intrinsic block, rows 2i / 2i+1 of [2N x K]       calib_cost_functions.cpp:105-114
+        if (a.jac_intr) {
+            double rows[2 * K];
+#pragma unroll
+            for (int i = 0; i < K; i++) {
+                rows[i] = e.Ju[i];
+                rows[K + i] = e.Jv[i];
+            }
+            if (K > kStageRowDoubles) wave_store_rows_halves<K, POLICY>(stage, rows, a.jac_intr + (size_t)ow * (2 * K), n_valid, lane);
+            else wave_store_rows<(K > kStageRowDoubles ? 1 : K), POLICY>(stage, rows, a.jac_intr + (size_t)ow * (2 * K), n_valid, lane);
+        }
+        // pose blocks, u-row at +12i, v-row at +12i+6       calib_cost_functions.cpp:93-101
+        for (int l = 0; l < a.L; l++) {
+            double *Jm = a.jac_member[l];
+            if (!Jm) continue;
+            double rows[12];
+            pose_rows(e.P, X0, X1, X2, fr + 12 + 21 * l, rows);
+            wave_store_rows<6, POLICY>(stage, rows, Jm + (size_t)ow * 12, n_valid, lane);
+        }
+    }
+}
+
 // dynamic LDS: 4 wave tiles, then (FRAMES_LDS) the frames of the images this workgroup touches
 // INLINE_CHAIN (with FRAMES_LDS, chain = one DIRECT member): the workgroup derives the <= 4 frames it needs itself
 // (thread f walks image b_first + f with build_frame_single_direct) instead of reading them from the chain-prep
 // kernel's output -- a full evaluation is then ONE launch.
-// One 256-observation tile of one dataset (o0 = first observation of the tile).
-template <int MODEL, bool WANT_JAC, bool FRAMES_LDS, bool INLINE_CHAIN>
+// One 256-observation tile of one dataset (o0 = first observation of the tile), its stores of policy POLICY (EmitStorePolicy).
+template <int MODEL, bool WANT_JAC, bool FRAMES_LDS, bool INLINE_CHAIN, int POLICY>
 __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int o0)
 {
     static_assert(!INLINE_CHAIN || FRAMES_LDS, "the inline chain writes its frames to LDS");
@@ -374,7 +438,11 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
     d2 r;
     r.x = e.ok ? e.u - ob.x : kDoubleBig;
     r.y = e.ok ? e.v - ob.y : kDoubleBig;
-    if (active) stream_store16(reinterpret_cast<d2 *>(a.res) + o, r, a.nt_stores);
+    // Pins the residual pair (and with it the observation load) here, ahead of every store.  Left alone, the compiler sinks
+    // the two subtractions into the `if (active)` below; the load's vmcnt wait then sits on one path only, and at the join the
+    // waitcnt pass still counts the load as pending and waits vmcnt(0) -- for the wave's own stores -- before it reuses the
+    // load's registers.  With the load consumed before the first store, no vmcnt wait follows it (tests/test_emit_isa_cpu.py).
+    asm volatile("" ::"v"(r.x), "v"(r.y));
 
     if (a.failed) {
         // Failures are rare: the counter is never zeroed (an 8-byte hipMemsetAsync is a whole 5 us fill
@@ -392,35 +460,11 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
         }
     }
 
-    if (WANT_JAC) {
-        double *stage = smem + wave * emit_stage_doubles_per_wave<MODEL>();
-        const unsigned int ow = o0 + wave * kWave;  // first observation of this wave
-        int n_valid = 0;
-        if (ow < a.n_obs) n_valid = (a.n_obs - ow < (unsigned)kWave) ? (int)(a.n_obs - ow) : kWave;
-
-        // intrinsic block, rows 2i / 2i+1 of [2N x K]       calib_cost_functions.cpp:105-114
-        if (a.jac_intr) {
-            double rows[2 * K];
-#pragma unroll
-            for (int i = 0; i < K; i++) {
-                rows[i] = e.Ju[i];
-                rows[K + i] = e.Jv[i];
-            }
-            if (K > kStageRowDoubles) wave_store_rows_halves<K>(stage, rows, a.jac_intr + (size_t)ow * (2 * K), n_valid, lane, a.nt_stores);
-            else wave_store_rows<(K > kStageRowDoubles ? 1 : K)>(stage, rows, a.jac_intr + (size_t)ow * (2 * K), n_valid, lane, a.nt_stores);
-        }
-        // pose blocks, u-row at +12i, v-row at +12i+6       calib_cost_functions.cpp:93-101
-        for (int l = 0; l < a.L; l++) {
-            double *Jm = a.jac_member[l];
-            if (!Jm) continue;
-            double rows[12];
-            pose_rows(e.P, X0, X1, X2, fr + 12 + 21 * l, rows);
-            wave_store_rows<6>(stage, rows, Jm + (size_t)ow * 12, n_valid, lane, a.nt_stores);
-        }
-    }
+    emit_tile_stores<MODEL, WANT_JAC, POLICY>(a, o0, active, r, e, X0, X1, X2, fr, smem + wave * emit_stage_doubles_per_wave<MODEL>());
 }
 
-template <int MODEL, bool WANT_JAC, bool FRAMES_LDS, bool INLINE_CHAIN = false>
+// POLICY: the launch's store policy (EmitArgs::nt_stores), a template argument so that the tile's stores are straight-line code
+template <int MODEL, bool WANT_JAC, bool FRAMES_LDS, bool INLINE_CHAIN, int POLICY>
 #ifndef VG_EMIT_WAVES
 #define VG_EMIT_WAVES 4    // waves per SIMD the register allocation of the emit kernels aims at (experiment switch, profiles/NOTES.md)
 #endif
@@ -430,7 +474,7 @@ template <int MODEL, bool WANT_JAC, bool FRAMES_LDS, bool INLINE_CHAIN = false>
 __global__ __launch_bounds__(kEmitThreads) __attribute__((amdgpu_waves_per_eu(VG_EMIT_WAVES, 8))) void vg_emit_kernel(EmitArgs a)
 {
     const unsigned int t = a.map_window ? xcd_window_block(blockIdx.x, gridDim.x, a.map_window) : xcd_contiguous_block(blockIdx.x, gridDim.x);
-    emit_tile<MODEL, WANT_JAC, FRAMES_LDS, INLINE_CHAIN>(a, t * (unsigned)kEmitThreads);
+    emit_tile<MODEL, WANT_JAC, FRAMES_LDS, INLINE_CHAIN, POLICY>(a, t * (unsigned)kEmitThreads);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -455,14 +499,16 @@ struct EmitMultiArgs {
     int n;
 };
 
-template <int MODEL>
+template <int MODEL, int POLICY>
 __device__ __forceinline__ void emit_tile_route(const EmitArgs &a, unsigned int o0, bool inline_chain)
 {
-    if (inline_chain) emit_tile<MODEL, true, true, true>(a, o0);
-    else emit_tile<MODEL, true, true, false>(a, o0);
+    if (inline_chain) emit_tile<MODEL, true, true, true, POLICY>(a, o0);
+    else emit_tile<MODEL, true, true, false, POLICY>(a, o0);
 }
 
 #ifdef VG_TU_CORE  // this kernel is launched by one translation unit only; the others see the header without it
+// POLICY: the store policy of the launch, shared by all its datasets (plain or non-temporal)
+template <int POLICY>
 __global__ __launch_bounds__(kEmitThreads) __attribute__((amdgpu_waves_per_eu(VG_EMIT_MULTI_WAVES, 8))) void vg_emit_multi_kernel(EmitMultiArgs m)
 {
     const unsigned int x = blockIdx.x & 7u;   // workgroup b runs on XCD b % 8 (observed dispatch order)
@@ -481,9 +527,9 @@ __global__ __launch_bounds__(kEmitThreads) __attribute__((amdgpu_waves_per_eu(VG
     const unsigned int o0 = (t - m.first_tile[d]) * (unsigned)kEmitThreads;
     const bool inl = m.inline_chain[d] != 0;
     switch (m.model[d]) {
-    case kEUCM: emit_tile_route<kEUCM>(m.ds[d], o0, inl); break;
-    case kUCM: emit_tile_route<kUCM>(m.ds[d], o0, inl); break;
-    default: emit_tile_route<kMEI>(m.ds[d], o0, inl); break;
+    case kEUCM: emit_tile_route<kEUCM, POLICY>(m.ds[d], o0, inl); break;
+    case kUCM: emit_tile_route<kUCM, POLICY>(m.ds[d], o0, inl); break;
+    default: emit_tile_route<kMEI, POLICY>(m.ds[d], o0, inl); break;
     }
 }
 #endif
