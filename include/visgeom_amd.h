@@ -662,6 +662,54 @@ int vg_stereo_aggregate(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, cons
  * unsteps), one at a time, |steps| <= 1000: uv [|steps| + 1][2] receives the start and every position. */
 int vg_stereo_curve_walk(const double *poly6, int u, int v, int eu, int ev, int step_mult, int steps, int32_t *uv);
 
+/* =====================================================================================
+ * 10. Motion stereo: the reference's MotionStereo (src/reconstruction/eucm_motion_stereo.cpp): a key frame's depth map is
+ *     computed or refined from a further image of a moving camera.  Each salient pixel of the key frame is searched along
+ *     its epipolar curve in the new image (the whole curve without a prior, the +-3 sigma segment with one), triangulated
+ *     and fused into the map.  Images are DEVICE u8 [n][v_max][u_max], depth maps DEVICE FP64 [n][y_max][x_max].  The calls
+ *     are synchronous on the handle's stream.  Deviations: DESIGN.md section 9, "Motion stereo".
+ * ===================================================================================== */
+typedef struct vg_motion_stereo vg_motion_stereo;
+/* MotionStereoParameters (eucm_motion_stereo.h:37-53): StereoParameters + gradientThresh.  The SGM-only fields of `stereo`
+ * (step_cost, jump_cost, image_based_cost, salient_points_only, use_uv_cache) are ignored; hypotheses must be 1. */
+typedef struct vg_motion_stereo_params {
+    vg_stereo_params stereo;
+    int gradient_thresh;
+} vg_motion_stereo_params;
+/* vg_stereo_params_default + gradient_thresh 2 */
+void vg_motion_stereo_params_default(vg_motion_stereo_params *p);
+/* A handle for one pair of EUCM cameras (eucm1: the key frames' camera, eucm2: the camera of the further images; the
+ * reference passes the same camera twice), HOST 6 intrinsics each.  The arguments are checked before HIP is touched, as
+ * vg_stereo_create checks them, and gradient_thresh must be in [0, 255].  There is no transformation at creation: every
+ * compute call brings its own. */
+int vg_motion_stereo_create(vg_motion_stereo **out, int device, void *hip_stream, const double *eucm1, const double *eucm2,
+                            const vg_motion_stereo_params *params);
+void vg_motion_stereo_destroy(vg_motion_stereo *s);
+int vg_motion_stereo_size(const vg_motion_stereo *s, int *x_max, int *y_max);
+/* setBaseImage of n key frames (n in [1, 65535]): img1 DEVICE u8 [n][v_max][u_max] is copied into the handle and computeMask runs
+ * on the GPU; image and mask stay resident until the next set_base.  Allocates only when n exceeds every earlier n. */
+int vg_motion_stereo_set_base(vg_motion_stereo *s, int64_t n, const uint8_t *img1);
+/* Both overloads of MotionStereo::compute for n independent items, n at most the n of set_base: item k pairs key frame k with
+ * img2[k] (DEVICE) under the pose xi12[k] (HOST [n][6], [t, rotvec] of the new camera in the key frame; |t|^2 > 1e-10).
+ * depth_in == NULL is the overload without a prior: the outputs start at 0 / 0 / error_max.  Otherwise depth_in, sigma_in and
+ * cost_in are the prior map and the outputs start as its copy; an output may be the same array as its input.  depth,
+ * sigma, cost: DEVICE outputs, none NULL.  counts (HOST int64 [n][6], may be NULL): the pixels rejected by selectPoint, by
+ * computeUncertainty, as too certain (gdispMax / gstep < 2 with a prior; an empty search without one), by sampleImage, the
+ * pixels that reached reconstruct, and the pixels it updated.  The curve tables of the n poses are built on the host and go
+ * up through pinned staging; a second call with the same n allocates nothing. */
+int vg_motion_stereo_compute(vg_motion_stereo *s, int64_t n, const double *xi12, const uint8_t *img2, const double *depth_in,
+                             const double *sigma_in, const double *cost_in, double *depth, double *sigma, double *cost,
+                             int64_t *counts);
+/* Stage entry: the mask of the key frames, DEVICE u8 [n of set_base][v_max][u_max] (0 / 128). */
+int vg_motion_stereo_mask(vg_motion_stereo *s, uint8_t *mask);
+/* Stage entry: what compute decides per depth pixel, without writing a map.  Arguments as vg_motion_stereo_compute (depth_in
+ * NULL: no prior).  record: DEVICE int32 [n][y_max][x_max][16]: [0] status (1 rejected by selectPoint, 2 by computeUncertainty,
+ * 3 too certain, 4 rejected by sampleImage, 5 reached reconstruct and was left as it was, 6 updated), [1] gstep, [2] gu2,
+ * [3] gv2, [4] [5] the rounded start point, [6] [7] the rounded end point, [8] gdispMax, [9] the inverted-sampling flag,
+ * [10] the best sample index, [11] its cost, [12] the curve index of camera 2, [13..15] 0.  A field a pixel never reached is 0. */
+int vg_motion_stereo_select(vg_motion_stereo *s, int64_t n, const double *xi12, const uint8_t *img2, const double *depth_in,
+                            const double *sigma_in, const double *cost_in, int32_t *record);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",
  * "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop", "solver_no_fold_frames",

@@ -33,7 +33,8 @@ def sources():
 
 
 # the host programs build_cli() makes: name -> source in csrc/
-CLI_SOURCES = {"calib": "calib_main.cpp", "rectify": "rectify_main.cpp", "stereo": "stereo_main.cpp"}
+CLI_SOURCES = {"calib": "calib_main.cpp", "rectify": "rectify_main.cpp", "stereo": "stereo_main.cpp",
+               "motion_stereo": "motion_stereo_main.cpp"}
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 STAMP = os.path.join(LIB_DIR, "libvisgeom_amd.sources.sha256")
 _INCLUDE = None
@@ -185,19 +186,22 @@ BIN_DIR = os.path.join(PKG, "bin")
 CLI = os.path.join(BIN_DIR, "calib")
 RECTIFY_CLI = os.path.join(BIN_DIR, "rectify")
 STEREO_CLI = os.path.join(BIN_DIR, "stereo")
+MOTION_STEREO_CLI = os.path.join(BIN_DIR, "motion_stereo")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 
 def build_cli(verbose=False):
     """the reference's programs, host-only C++ on the C ABI: `calib file1.json [file2.json ...]`, `rectify file.json` and
-    `stereo file.json` (the last two also call the HIP runtime for their device buffers)"""
+    `stereo file.json` and `motion_stereo sequence.json` (all but the first also call the HIP runtime for their device buffers)"""
     os.makedirs(BIN_DIR, exist_ok=True)
     common = ["-L" + LIB_DIR, "-lvisgeom_amd", "-Wl,-rpath," + LIB_DIR, "-Wl,-rpath," + os.path.join(ROCM, "lib")]
     cmds = [["g++", "-O2", "-std=c++17", "-Wall", os.path.join(CSRC, CLI_SOURCES["calib"]), "-o", CLI] + common,
             ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROCM, "include"),
              os.path.join(CSRC, CLI_SOURCES["rectify"]), "-o", RECTIFY_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"],
             ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROCM, "include"),
-             os.path.join(CSRC, CLI_SOURCES["stereo"]), "-o", STEREO_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"]]
+             os.path.join(CSRC, CLI_SOURCES["stereo"]), "-o", STEREO_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"],
+            ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROCM, "include"),
+             os.path.join(CSRC, CLI_SOURCES["motion_stereo"]), "-o", MOTION_STEREO_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"]]
     for cmd in cmds:
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

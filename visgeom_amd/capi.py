@@ -202,6 +202,14 @@ SIGNATURES = {
     "vg_stereo_aggregate": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     "vg_stereo_curve_walk": (ctypes.c_int, [_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             _i32p]),
+    "vg_motion_stereo_params_default": (None, [_vp]),
+    "vg_motion_stereo_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, _dp, _dp, _vp]),
+    "vg_motion_stereo_destroy": (None, [_vp]),
+    "vg_motion_stereo_size": (ctypes.c_int, [_vp, _ip, _ip]),
+    "vg_motion_stereo_set_base": (ctypes.c_int, [_vp, ctypes.c_int64, _vp]),
+    "vg_motion_stereo_compute": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64p]),
+    "vg_motion_stereo_mask": (ctypes.c_int, [_vp, _vp]),
+    "vg_motion_stereo_select": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _vp, _vp, _vp, _vp, _vp]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),
@@ -218,6 +226,11 @@ class StereoParams(ctypes.Structure):
                                             "n_scales")] + \
                [("scales", ctypes.c_int * 8)] + \
                [(n, ctypes.c_int) for n in ("step_cost", "jump_cost", "image_based_cost", "salient_points_only", "use_uv_cache")]
+
+
+class MotionStereoParams(ctypes.Structure):
+    """struct vg_motion_stereo_params"""
+    _fields_ = [("stereo", StereoParams), ("gradient_thresh", ctypes.c_int)]
 
 
 class VisgeomError(RuntimeError):
