@@ -5,37 +5,24 @@ first global store holds the wave until its own stores are acknowledged, with no
 instantiation of vg_emit_kernel (each model, with and without Jacobians, each store policy) must therefore run no vmcnt
 wait from its first store to s_endpgm, outside the failed-projection CAS block (the only block with a global atomic).
 The headline instantiation must also keep 4 waves per SIMD (<= 128 VGPRs) and use no scratch."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-from visgeom_amd import _build
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import isa
+from tests.isa import kernel_metadata
 
 # vg_emit_kernel<MODEL, WANT_JAC, FRAMES_LDS = true, INLINE_CHAIN[, POLICY]>
 EMIT_LDS = re.compile(r"^_ZN2vg14vg_emit_kernelILi(\d)ELb([01])ELb1ELb([01])(?:ELi(\d))?EEEvNS_8EmitArgsE$")
 HEADLINE = re.compile(r"^_ZN2vg14vg_emit_kernelILi0ELb1ELb1ELb1E")  # EUCM, Jacobians, frames in LDS, inline chain
 
 
-def _hipcc():
-    return shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-
-
 @pytest.fixture(scope="module")
 def asm(tmp_path_factory):
-    hipcc = _hipcc()
+    hipcc = isa.hipcc()
     if hipcc is None:
         pytest.skip("hipcc not found")
-    out = str(tmp_path_factory.mktemp("isa") / "vg_capi.s")
-    flags = [f for f in _build.HIPCC_FLAGS if f != "-shared"]
-    cmd = [hipcc] + flags + ["--cuda-device-only", "-S", "-I", os.path.join(ROOT, "include"),
-                             os.path.join(_build.CSRC, "vg_capi.hip"), "-o", out]
-    subprocess.run(cmd, check=True, capture_output=True)
-    return open(out).read()
+    return isa.device_asm(hipcc, "vg_capi.hip", str(tmp_path_factory.mktemp("isa") / "vg_capi.s"))
 
 
 def kernel_bodies(text):
@@ -44,17 +31,6 @@ def kernel_bodies(text):
     for m in re.finditer(r"^(_Z\w+):", text, flags=re.M):
         end = text.find(".Lfunc_end", m.end())
         out[m.group(1)] = text[m.end():end].split("\n")
-    return out
-
-
-def kernel_metadata(text):
-    """kernel name -> {field: value} of the code object metadata (.vgpr_count, .private_segment_fixed_size, ...)"""
-    meta = text[text.find("amdhsa.kernels:"):]
-    out = {}
-    for entry in re.split(r"\n  - (?=\.)", meta)[1:]:
-        fields = dict(re.findall(r"^\s*-?\s*(\.[a-z_]+):\s+(\S+)$", "    " + entry, flags=re.M))
-        if ".name" in fields:
-            out[fields[".name"]] = fields
     return out
 
 

@@ -1,5 +1,6 @@
 // vg_motion.hpp -- motion stereo: the reference's MotionStereo (src/reconstruction/eucm_motion_stereo.cpp) on the device
-// functions of vg_stereo.hpp (Poly2, Raster, EUCM reconstruct / project, curve index, epipole choice, regular triangulation).
+// functions of vg_stereo_device.hpp (Poly2, Raster, EUCM reconstruct / project, curve index, epipole choice, the four-point
+// triangulation, the descriptor and its matching).
 // Two kernels: the gradient mask of the key frames (computeMask) and one lane per (item, depth pixel) through selectPoint,
 // computeUncertainty, sampleImage and reconstruct.  Every item has its own StereoGeom in device memory (the pose changes with
 // every call).  Evaluated in the order written (-ffp-contract=off), so tests/motion_ref.py agrees bit for bit.
@@ -81,8 +82,6 @@ struct MotionArgs {
     int gradient_thresh;
 };
 
-constexpr int kMotionLanes = 256;
-
 VGS_HD double dmax(double a, double b) { return a < b ? b : a; }   // std::max
 
 VGS_HD bool coord_ok(const double *pt) { return fabs(pt[0]) <= kCoordLimit && fabs(pt[1]) <= kCoordLimit; }   // false for NaN
@@ -95,15 +94,13 @@ VGS_HD void fuse(double &v1, double &s1, double v2, double s2)
     s1 = dmax(s1 * s2 * K, 0.05 * v1);
 }
 
-// MotionStereo::compute (eucm_motion_stereo.cpp:258-358) for one depth pixel per lane.  compareDescriptor runs as the one
-// stream over the samples that stereo_curve_cost_kernel uses (first half: two columns of history per row; second half: row k
-// lagged by 2 k columns; samples and first-half results of the last 32 columns in an LDS ring), at step 1 and with the running
-// minimum instead of an error volume.  The positions of the best sample and its successor come from a second walk.
-__global__ __launch_bounds__(kMotionLanes) void motion_stereo_kernel(MotionArgs a)
+// MotionStereo::compute (eucm_motion_stereo.cpp:258-358) for one depth pixel per lane.  The descriptor, its thresholds and
+// compareDescriptor's DP are vg_stereo_device.hpp's, as in stereo_curve_cost_kernel; here the samples are the prior's segment
+// at step 1, leaving the image rejects the pixel, and a final column goes into the running first minimum.  The positions of
+// the best sample and its successor come from a second walk.
+__global__ __launch_bounds__(kMatchLanes) void motion_stereo_kernel(MotionArgs a)
 {
-    __shared__ int ring[kRing][kMotionLanes];
-    __shared__ uint16_t thr[kMaxDesc][kMotionLanes];
-    __shared__ uint8_t desc[kMaxDesc][kMotionLanes];
+    __shared__ MatchLds lds;
     const int lane = threadIdx.x;
     const int64_t item = blockIdx.y;
     const int64_t pix = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -136,38 +133,14 @@ __global__ __launch_bounds__(kMotionLanes) void motion_stereo_kernel(MotionArgs 
             if (flags1 & kEpipoleTooClose) break;
             Raster ref;
             make_raster(g, 0, gu, gv, curve_index(g, X), flags1, ref);
-            const uint8_t *im1 = a.img1 + item * img;
-            int step = -1, resp = 0;
-            const int wave_thresh = g.desc_resp_thresh * L;
-            for (int si = 0; si < g.n_scales; si++) {   // EpipolarDescriptor::compute
-                const int sc = g.scales[si];
-                Raster rr = ref;
-                rr.eps *= -sc;
-                rr.steps(-H);
-                bool border = false;
-                for (int i = 0; i < L; i++, rr.step()) {
-                    if (!inside(g, rr.u, rr.v)) {
-                        border = true;
-                        break;
-                    }
-                    desc[i][lane] = im1[(int64_t)rr.v * g.u_max + rr.u];
-                }
-                if (border) {
-                    step = -1;
-                    break;
-                }
-                int tv = 0;
-                for (int i = 1; i < L; i++) tv += abs((int)desc[i - 1][lane] - (int)desc[i][lane]);
-                resp = (tv * 100) / ((int)desc[H][lane] + 30);
-                step = sc;
-                if (abs(resp) > wave_thresh) break;
-            }
+            int resp;
+            const int step = compute_descriptor(g, ref, a.img1 + item * img, lds, lane, resp);
             r.gstep = step;
             ref.eps *= step;   // descRasterUncert
             ref.step();
             r.gu2 = ref.u;
             r.gv2 = ref.v;
-            if (step != 1 || !(abs(resp) > wave_thresh)) break;
+            if (step != 1 || !(abs(resp) > g.desc_resp_thresh * L)) break;
             status = 0;
         } while (false);
     }
@@ -222,26 +195,7 @@ __global__ __launch_bounds__(kMotionLanes) void motion_stereo_kernel(MotionArgs 
 
     // ---- sampleImage + compareDescriptor + the minimum over [HALF_LENGTH, size - HALF_LENGTH)
     if (live && status == 0) {
-        for (int i = 0; i < L; i++) {   // thresholds (compareDescriptor, eucm_stereo.cpp:81-113)
-            const int di = desc[i][lane];
-            int lo, hi;
-            if (i == 0 || i == L - 1) {
-                const int dn = desc[i == 0 ? 1 : L - 2][lane];
-                const int m = (di + dn) / 2;
-                if (di > dn) {
-                    lo = m;
-                    hi = di;
-                } else {
-                    hi = m;
-                    lo = di;
-                }
-            } else {
-                const int d1 = (di + desc[i - 1][lane]) / 2, d2 = (di + desc[i + 1][lane]) / 2;
-                lo = imin(di, imin(d1, d2));
-                hi = di > d1 ? (di > d2 ? di : d2) : (d1 > d2 ? d1 : d2);
-            }
-            thr[i][lane] = (uint16_t)(lo | hi << 8);
-        }
+        descriptor_thresholds(lds, L, lane);
         const uint8_t *im2 = a.img2 + item * img;
         const Poly2 &curve = g.table[(int64_t)(g.n_planes + 1) + r.index2];
         const int nSteps = r.disp_max, N = nSteps + L - 1;
@@ -249,15 +203,10 @@ __global__ __launch_bounds__(kMotionLanes) void motion_stereo_kernel(MotionArgs 
         r2.init(r.su, r.sv, r.fu, r.fv, curve);
         if (r.inverted) r2.eps *= -1;
         r2.steps(-H);
-        int v1[kMaxHalf], v2[kMaxHalf];
-        int w0[kMaxHalf], w1[kMaxHalf], w2[kMaxHalf];
-#pragma unroll
-        for (int i = 0; i < kMaxHalf; i++) {
-            v1[i] = v2[i] = kInf;
-            w0[i] = w1[i] = w2[i] = kInf;
-        }
+        MatchDp dp;
+        dp.init();
         int best = -1, best_cost = 0x7fffffff;
-        const int t_end = nSteps + 3 * H;
+        const int t_end = nSteps + 3 * H;   // column j = t - 2H is final at time t
         for (int t = 0; t < t_end; t++) {
             if (t < N) {
                 if (t > 0) r2.step();
@@ -265,50 +214,12 @@ __global__ __launch_bounds__(kMotionLanes) void motion_stereo_kernel(MotionArgs 
                     status = kRejSample;
                     break;
                 }
-                const int s = im2[(int64_t)r2.v * g.u_max + r2.u];
-                int cur = compute_error(s, thr[0][lane]);
-#pragma unroll
-                for (int i = 1; i <= kMaxHalf; i++) {
-                    if (i <= H) {
-                        const int nv = imin(cur + f, imin(v1[i - 1], v2[i - 1] + f)) + compute_error(s, thr[i][lane]);
-                        v2[i - 1] = v1[i - 1];
-                        v1[i - 1] = cur;
-                        cur = nv;
-                    }
-                }
-                ring[t % kRing][lane] = cur << 8 | s;
+                dp.push(lds, lane, H, f, t, im2[(int64_t)r2.v * g.u_max + r2.u]);
             }
-#pragma unroll
-            for (int k = 0; k < kMaxHalf; k++) {
-                if (k < H) {
-                    const int c = t - 2 * k;
-                    int val = kInf;
-                    if (c >= 0 && c < N) {
-                        const int sc = ring[c % kRing][lane] & 255;
-                        const int ev = compute_error(sc, thr[L - 1 - k][lane]);
-                        if (k == 0) val = ev;
-                        else val = imin(w2[k - 1] + f, imin(w1[k - 1], w0[k - 1] + f)) + ev;
-                    }
-                    w2[k] = w1[k];
-                    w1[k] = w0[k];
-                    w0[k] = val;
-                }
-            }
-            const int j = t - 2 * H;
-            if (j >= H) {
-                int fw2 = kInf, fw1 = kInf, fw0 = kInf;
-#pragma unroll
-                for (int k = 0; k < kMaxHalf; k++)
-                    if (k == H - 1) {
-                        fw2 = w2[k];
-                        fw1 = w1[k];
-                        fw0 = w0[k];
-                    }
-                const int total = (ring[j % kRing][lane] >> 8) + imin(fw2 + f, imin(fw1, fw0 + f));
-                if (total < best_cost) {   // min_element: the first minimum
-                    best_cost = total;
-                    best = j;
-                }
+            int total;
+            if (dp.advance(lds, lane, L, f, t, N, total) && total < best_cost) {   // min_element: the first minimum
+                best_cost = total;
+                best = t - 2 * H;
             }
         }
         if (status == 0) {
@@ -324,13 +235,8 @@ __global__ __launch_bounds__(kMotionLanes) void motion_stereo_kernel(MotionArgs 
                 r3.steps(best);
                 const int u21 = r3.u, v21 = r3.v;
                 r3.step();
-                double p1[3], p2[3], q1[3], q2[3];
-                if (eucm_reconstruct(g.c1, (double)gu, (double)gv, p1) && eucm_reconstruct(g.c1, (double)r.gu2, (double)r.gv2, p2) &&
-                    eucm_reconstruct(g.c2, (double)u21, (double)v21, q1) && eucm_reconstruct(g.c2, (double)r3.u, (double)r3.v, q2)) {
-                    const double pn = sqrt(dot3(p1, p1));
-                    const double l1 = triangulate_lambda(g.R, g.t, p1, q1) * pn;
-                    const double l2 = triangulate_lambda(g.R, g.t, p2, q2) * pn;
-                    const double sigma_new = fabs(l2 - l1);
+                double l1, sigma_new;
+                if (triangulate_pairs(g, gu, gv, r.gu2, r.gv2, u21, v21, r3.u, r3.v, l1, sigma_new)) {
                     if (dist != 0.) {
                         fuse(dist, sig, l1, sigma_new);
                         cst = cst * 0.7 + best_cost * 0.3;

@@ -38,7 +38,7 @@ namespace {
 using vgi::fail;
 constexpr int64_t kMaxItems = 65535;   // items ride on gridDim.y / gridDim.z
 
-unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+using vgsh::blocks_of;
 
 int ensure_items(vg_motion_stereo *s, int64_t n)
 {
@@ -69,8 +69,7 @@ int run(vg_motion_stereo *s, int64_t n, const double *xi12, const uint8_t *img2,
     for (int64_t k = 0; k < n; k++) {
         const double *xi = xi12 + 6 * k;
         if (!vgsh::finite_n(xi, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "the transformations must be finite");
-        if (!(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2] > 1e-10))
-            return fail(VG_ERR_INVALID_ARGUMENT, "the baseline of an item must not vanish (|t|^2 > 1e-10)");
+        if (!vgsh::has_baseline(xi)) return fail(VG_ERR_INVALID_ARGUMENT, "the baseline of an item must not vanish (|t|^2 > 1e-10)");
     }
     VG_HIP(hipSetDevice(s->device));
     if (const int rc = ensure_items(s, n)) return rc;
@@ -101,7 +100,7 @@ int run(vg_motion_stereo *s, int64_t n, const double *xi12, const uint8_t *img2,
     a.counts = counts ? s->d_counts.get() : nullptr;
     a.P = s->P;
     a.gradient_thresh = s->prm.gradient_thresh;
-    hipLaunchKernelGGL(vgm::motion_stereo_kernel, dim3(blocks_of(s->P, vgm::kMotionLanes), (unsigned)n), dim3(vgm::kMotionLanes), 0, s->stream, a);
+    hipLaunchKernelGGL(vgm::motion_stereo_kernel, dim3(blocks_of(s->P, vgs::kMatchLanes), (unsigned)n), dim3(vgs::kMatchLanes), 0, s->stream, a);
     VG_HIP(hipGetLastError());
     if (counts)
         VG_HIP(hipMemcpyAsync(s->h_counts, s->d_counts, (size_t)n * 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
@@ -133,7 +132,7 @@ int vg_motion_stereo_create(vg_motion_stereo **out, int device, void *hip_stream
     if (const int rc = vgsh::check_params(params->stereo, x_max, y_max)) return rc;
     if (params->gradient_thresh < 0 || params->gradient_thresh > 255) return fail(VG_ERR_INVALID_ARGUMENT, "gradient_thresh must be in [0, 255]");
     if (!vgsh::finite_n(eucm1, 6) || !vgsh::finite_n(eucm2, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "camera parameters must be finite");
-    if (eucm1[2] == 0. || eucm1[3] == 0. || eucm2[2] == 0. || eucm2[3] == 0.) return fail(VG_ERR_INVALID_ARGUMENT, "fu, fv must be non-zero");
+    if (!vgsh::focal_nonzero(eucm1, eucm2)) return fail(VG_ERR_INVALID_ARGUMENT, "fu, fv must be non-zero");
     std::unique_ptr<vg_motion_stereo> s(new (std::nothrow) vg_motion_stereo());
     if (!s) return fail(VG_ERR_ALLOC, "out of host memory");
     s->prm = *params;

@@ -1,6 +1,7 @@
 // vg_stereo.hpp -- dense fisheye stereo: the reference's EnhancedSgm (src/reconstruction/eucm_sgm.cpp), semi-global
 // matching along the epipolar curves of two unrectified EUCM images.  The four kernels: per-pixel geometry, curve cost,
-// directional aggregation (left+right, top+bottom with the winner) and depth, on the shared pieces of vg_stereo_device.hpp.
+// directional aggregation (left+right, top+bottom with the winner) and depth, on the shared pieces of vg_stereo_device.hpp
+// (among them the descriptor and its matching, which motion stereo runs too).
 // The entries are in vg_stereo_tu.hip.
 #pragma once
 
@@ -62,8 +63,6 @@ struct CurveCostArgs {
     int64_t n_pairs;
 };
 
-constexpr int kCostLanes = 256;
-
 // writes the skipPixel pattern (eucm_sgm.cpp:220-226)
 __device__ __forceinline__ void skip_pixel(uint8_t *e, int D, uint8_t *skip)
 {
@@ -73,15 +72,11 @@ __device__ __forceinline__ void skip_pixel(uint8_t *e, int D, uint8_t *skip)
 }
 
 // computeCurveCost (eucm_sgm.cpp:228-393) with EpipolarDescriptor::compute, compareDescriptor and fillGaps: one lane per
-// (pair, depth pixel).  compareDescriptor's two row DPs run as one stream over the samples: the first half (descriptor rows 0
-// .. H, columns left to right) keeps two columns of history per row; the second half (rows L-1 .. H+1, whose recurrence looks
-// two columns to the right) runs row k lagged by 2k columns, so after 2H columns the final cost of column j is known.  The
-// samples and the first-half results of the last 32 columns live in an LDS ring; the thresholds of the descriptor in LDS.
-__global__ __launch_bounds__(kCostLanes) void stereo_curve_cost_kernel(StereoGeom g, CurveCostArgs a)
+// (pair, depth pixel).  The descriptor, its thresholds and the DP are vg_stereo_device.hpp's; here are the sample walk of
+// camera 2 (uv-cache walk or stepped rasteriser), skipPixel where it leaves the image, and the error volume with fillGaps.
+__global__ __launch_bounds__(kMatchLanes) void stereo_curve_cost_kernel(StereoGeom g, CurveCostArgs a)
 {
-    __shared__ int ring[kRing][kCostLanes];         // (V_H[j] << 8) | sample[j] at slot j % 32
-    __shared__ uint16_t thr[kMaxDesc][kCostLanes];   // thMin | thMax << 8
-    __shared__ uint8_t desc[kMaxDesc][kCostLanes];
+    __shared__ MatchLds lds;
     const int lane = threadIdx.x;
     const int64_t P = (int64_t)g.x_max * g.y_max;
     const int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -102,62 +97,17 @@ __global__ __launch_bounds__(kCostLanes) void stereo_curve_cost_kernel(StereoGeo
     const uint8_t *im1 = a.img1 + pair * (int64_t)g.u_max * g.v_max;
     const uint8_t *im2 = a.img2 + pair * (int64_t)g.u_max * g.v_max;
 
-    // EpipolarDescriptor::compute
     Raster ref;
     make_raster(g, 0, x * g.scale + g.u0, y * g.scale + g.v0, ge.index, ge.flags1, ref);
-    int step = -1, resp = 0;
-    const int wave_thresh = g.desc_resp_thresh * L;
-    for (int si = 0; si < g.n_scales; si++) {
-        const int sc = g.scales[si];
-        Raster r = ref;
-        r.eps *= -sc;
-        r.steps(-H);
-        bool border = false;
-        for (int i = 0; i < L; i++, r.step()) {
-            if (!inside(g, r.u, r.v)) {
-                border = true;
-                break;
-            }
-            desc[i][lane] = im1[(int64_t)r.v * g.u_max + r.u];
-        }
-        if (border) {
-            step = -1;
-            break;
-        }
-        int tv = 0;
-        for (int i = 1; i < L; i++) tv += abs((int)desc[i - 1][lane] - (int)desc[i][lane]);
-        resp = (tv * 100) / ((int)desc[H][lane] + 30);
-        step = sc;
-        if (abs(resp) > wave_thresh) break;
-    }
+    int resp;
+    const int step = compute_descriptor(g, ref, im1, lds, lane, resp);
     if (step < 1) {
         skip_pixel(e, D, skipp);
         return;
     }
     a.step[gi] = (uint8_t)step;
-    if (g.salient_points_only && step < 2 && abs(resp) > wave_thresh) a.salient[gi] = 1;
-
-    // thresholds (compareDescriptor, eucm_stereo.cpp:81-113)
-    for (int i = 0; i < L; i++) {
-        const int di = desc[i][lane];
-        int lo, hi;
-        if (i == 0 || i == L - 1) {
-            const int dn = desc[i == 0 ? 1 : L - 2][lane];
-            const int m = (di + dn) / 2;
-            if (di > dn) {
-                lo = m;
-                hi = di;
-            } else {
-                hi = m;
-                lo = di;
-            }
-        } else {
-            const int d1 = (di + desc[i - 1][lane]) / 2, d2 = (di + desc[i + 1][lane]) / 2;
-            lo = imin(di, imin(d1, d2));
-            hi = di > d1 ? (di > d2 ? di : d2) : (d1 > d2 ? d1 : d2);
-        }
-        thr[i][lane] = (uint16_t)(lo | hi << 8);
-    }
+    if (g.salient_points_only && step < 2 && abs(resp) > g.desc_resp_thresh * L) a.salient[gi] = 1;
+    descriptor_thresholds(lds, L, lane);
 
     // the sample walk of camera 2
     const int nSteps = (D + step - 1) / step;
@@ -173,17 +123,11 @@ __global__ __launch_bounds__(kCostLanes) void stereo_curve_cost_kernel(StereoGeo
         r2.steps(-H);
     }
 
-    int v1[kMaxHalf], v2[kMaxHalf];           // first half: rows 0 .. H-1, columns t-1 and t-2
-    int w0[kMaxHalf], w1[kMaxHalf], w2[kMaxHalf];   // second half, level k = row L-1-k: its last three columns
-#pragma unroll
-    for (int i = 0; i < kMaxHalf; i++) {
-        v1[i] = v2[i] = kInf;
-        w0[i] = w1[i] = w2[i] = kInf;
-    }
+    MatchDp dp;
+    dp.init();
     int prev = 0;
     const int t_end = nSteps + 3 * H;   // column j = t - 2H is final at time t; j runs to H + nSteps - 1
     for (int t = 0; t < t_end; t++) {
-        int s = 0;
         if (t < N) {
             int su, sv;
             if (g.use_uv_cache) {
@@ -199,49 +143,11 @@ __global__ __launch_bounds__(kCostLanes) void stereo_curve_cost_kernel(StereoGeo
                 skip_pixel(e, D, skipp);
                 return;
             }
-            s = im2[(int64_t)sv * g.u_max + su];
-            // first half, column t
-            int cur = compute_error(s, thr[0][lane]);
-#pragma unroll
-            for (int i = 1; i <= kMaxHalf; i++) {
-                if (i <= H) {
-                    const int nv = imin(cur + f, imin(v1[i - 1], v2[i - 1] + f)) + compute_error(s, thr[i][lane]);
-                    v2[i - 1] = v1[i - 1];
-                    v1[i - 1] = cur;
-                    cur = nv;
-                }
-            }
-            ring[t % kRing][lane] = cur << 8 | s;
+            dp.push(lds, lane, H, f, t, im2[(int64_t)sv * g.u_max + su]);
         }
-        // second half: level k at column t - 2k
-#pragma unroll
-        for (int k = 0; k < kMaxHalf; k++) {
-            if (k < H) {
-                const int c = t - 2 * k;
-                int val = kInf;
-                if (c >= 0 && c < N) {
-                    const int sc = ring[c % kRing][lane] & 255;
-                    const int ev = compute_error(sc, thr[L - 1 - k][lane]);
-                    if (k == 0) val = ev;
-                    else val = imin(w2[k - 1] + f, imin(w1[k - 1], w0[k - 1] + f)) + ev;
-                }
-                w2[k] = w1[k];
-                w1[k] = w0[k];
-                w0[k] = val;
-            }
-        }
-        const int j = t - 2 * H;
-        if (j >= H) {
-            int fw2 = kInf, fw1 = kInf, fw0 = kInf;
-#pragma unroll
-            for (int k = 0; k < kMaxHalf; k++)
-                if (k == H - 1) {
-                    fw2 = w2[k];
-                    fw1 = w1[k];
-                    fw0 = w0[k];
-                }
-            const int total = (ring[j % kRing][lane] >> 8) + imin(fw2 + f, imin(fw1, fw0 + f));
-            const int d = j - H;
+        int total;
+        if (dp.advance(lds, lane, L, f, t, N, total)) {
+            const int d = t - 3 * H;   // column H + d
             const int val = imin(total, 255);
             if (step == 1) {
                 e[d] = (uint8_t)val;
@@ -458,16 +364,11 @@ __global__ __launch_bounds__(256) void stereo_depth_kernel(StereoGeom g, DepthAr
             u22 = r.u;
             v22 = r.v;
         }
-        double p[3], q1[3], q2[3];
-        if (eucm_reconstruct(g.c1, (double)(x * g.scale + g.u0), (double)(y * g.scale + g.v0), p) &&
-            eucm_reconstruct(g.c2, (double)u21, (double)v21, q1) && eucm_reconstruct(g.c2, (double)u22, (double)v22, q2)) {
-            const double pn = sqrt(dot3(p, p));
-            const double l1 = triangulate_lambda(g.R, g.t, p, q1) * pn;
-            const double l2 = triangulate_lambda(g.R, g.t, p, q2) * pn;
-            if (l1 < kTriangulateDistMax) {
-                sig = fabs(l2 - l1);
-                dep = l1;
-            }
+        const int gu = x * g.scale + g.u0, gv = y * g.scale + g.v0;
+        double l1, s1;
+        if (triangulate_pairs(g, gu, gv, gu, gv, u21, v21, u22, v22, l1, s1) && l1 < kTriangulateDistMax) {
+            sig = s1;
+            dep = l1;
         }
     }
     if (a.depth) a.depth[gi] = dep;

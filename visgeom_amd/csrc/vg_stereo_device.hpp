@@ -1,8 +1,9 @@
 // vg_stereo_device.hpp -- the FP64 pieces the host and the kernels of both stereo translation units share (vg_stereo_tu.hip:
 // EnhancedSgm, vg_motion_tu.hip: MotionStereo): EUCM reconstruct / project, the epipolar-curve rasteriser, the curve index,
-// the epipole choice, the regular triangulation and the error of one sample against a descriptor threshold.  Everything is
-// evaluated in the order written (the library is built with -ffp-contract=off), so the host walk, the kernels and the
-// restatements in tests/ agree bit for bit.
+// the epipole choice, the regular triangulation of two point pairs; and, for the kernels alone, the descriptor matching of
+// stereo_curve_cost_kernel and motion_stereo_kernel (EpipolarDescriptor::compute, the thresholds and the DP of
+// compareDescriptor, the block's LDS).  Everything is evaluated in the order written (the library is built with
+// -ffp-contract=off), so the host walk, the kernels and the restatements in tests/ agree bit for bit.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -249,6 +250,150 @@ VGS_HD int compute_error(int v, int th)   // computeError (eucm_stereo.cpp:73-76
 
 VGS_HD int imin(int a, int b) { return a < b ? a : b; }
 
-constexpr int kRing = 32;   // > 2 HALF_LENGTH: the lag of the second half of compareDescriptor
+// the four-point triangulate (eucm_stereo.cpp:250-296): a pixel of camera 1 and its successor on the curve, (a, b) against
+// (c, d) in camera 2.  Distance of the first pair, and as its uncertainty the difference to the second pair's (both along
+// the first ray).  False when one of the four does not reconstruct.
+VGS_HD bool triangulate_pairs(const StereoGeom &g, int ua, int va, int ub, int vb, int uc, int vc, int ud, int vd, double &dist, double &sigma)
+{
+    double p1[3], p2[3], q1[3], q2[3];
+    if (!eucm_reconstruct(g.c1, (double)ua, (double)va, p1) || !eucm_reconstruct(g.c1, (double)ub, (double)vb, p2) ||
+        !eucm_reconstruct(g.c2, (double)uc, (double)vc, q1) || !eucm_reconstruct(g.c2, (double)ud, (double)vd, q2))
+        return false;
+    const double pn = sqrt(dot3(p1, p1));
+    dist = triangulate_lambda(g.R, g.t, p1, q1) * pn;
+    sigma = fabs(triangulate_lambda(g.R, g.t, p2, q2) * pn - dist);
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// EpipolarDescriptor::compute and compareDescriptor for one depth pixel per lane: the one implementation behind
+// stereo_curve_cost_kernel and motion_stereo_kernel.  The kernels keep what differs: where a sample comes from, what leaving
+// the image does, and what becomes of a final column.
+
+constexpr int kRing = 32;          // > 2 HALF_LENGTH: the lag of the second half of compareDescriptor
+constexpr int kMatchLanes = 256;   // lanes per block of both kernels
+
+struct MatchLds {   // one block's LDS, 56 576 bytes: two blocks per CU
+    int ring[kRing][kMatchLanes];          // (V_H[j] << 8) | sample[j] at slot j % kRing
+    uint16_t thr[kMaxDesc][kMatchLanes];   // thMin | thMax << 8
+    uint8_t desc[kMaxDesc][kMatchLanes];
+};
+
+// EpipolarDescriptor::compute: the descriptor around `ref` at the first scale whose response passes (else the last one) goes
+// to lds.desc; returns that scale, or -1 when a descriptor leaves the image
+__device__ __forceinline__ int compute_descriptor(const StereoGeom &g, const Raster &ref, const uint8_t *im1, MatchLds &lds, int lane, int &resp)
+{
+    const int L = g.desc_length, H = L / 2;
+    const int wave_thresh = g.desc_resp_thresh * L;
+    int step = -1;
+    resp = 0;
+    for (int si = 0; si < g.n_scales; si++) {
+        const int sc = g.scales[si];
+        Raster r = ref;
+        r.eps *= -sc;
+        r.steps(-H);
+        for (int i = 0; i < L; i++, r.step()) {
+            if (!inside(g, r.u, r.v)) return -1;
+            lds.desc[i][lane] = im1[(int64_t)r.v * g.u_max + r.u];
+        }
+        int tv = 0;
+        for (int i = 1; i < L; i++) tv += abs((int)lds.desc[i - 1][lane] - (int)lds.desc[i][lane]);
+        resp = (tv * 100) / ((int)lds.desc[H][lane] + 30);
+        step = sc;
+        if (abs(resp) > wave_thresh) break;
+    }
+    return step;
+}
+
+// the thresholds of lds.desc (compareDescriptor, eucm_stereo.cpp:81-113)
+__device__ __forceinline__ void descriptor_thresholds(MatchLds &lds, int L, int lane)
+{
+    for (int i = 0; i < L; i++) {
+        const int di = lds.desc[i][lane];
+        int lo, hi;
+        if (i == 0 || i == L - 1) {
+            const int dn = lds.desc[i == 0 ? 1 : L - 2][lane];
+            const int m = (di + dn) / 2;
+            if (di > dn) {
+                lo = m;
+                hi = di;
+            } else {
+                hi = m;
+                lo = di;
+            }
+        } else {
+            const int d1 = (di + lds.desc[i - 1][lane]) / 2, d2 = (di + lds.desc[i + 1][lane]) / 2;
+            lo = imin(di, imin(d1, d2));
+            hi = di > d1 ? (di > d2 ? di : d2) : (d1 > d2 ? d1 : d2);
+        }
+        lds.thr[i][lane] = (uint16_t)(lo | hi << 8);
+    }
+}
+
+// compareDescriptor's two row DPs as one stream over the N samples of a lane.  The first half (descriptor rows 0 .. H, columns
+// left to right) keeps two columns of history per row; the second half (rows L-1 .. H+1, whose recurrence looks two columns to
+// the right) runs row k lagged by 2k columns, so at time t the cost of column t - 2H is final.  The samples and the first-half
+// results of the last kRing columns live in lds.ring.  Per time step t = 0 .. N + 2H - 1: push (while t < N), then advance.
+struct MatchDp {
+    int v1[kMaxHalf], v2[kMaxHalf];                 // first half: rows 0 .. H-1, columns t-1 and t-2
+    int w0[kMaxHalf], w1[kMaxHalf], w2[kMaxHalf];   // second half, level k = row L-1-k: its last three columns
+
+    __device__ __forceinline__ void init()
+    {
+#pragma unroll
+        for (int i = 0; i < kMaxHalf; i++) {
+            v1[i] = v2[i] = kInf;
+            w0[i] = w1[i] = w2[i] = kInf;
+        }
+    }
+    // first half, column t, and the ring write
+    __device__ __forceinline__ void push(MatchLds &lds, int lane, int H, int f, int t, int s)
+    {
+        int cur = compute_error(s, lds.thr[0][lane]);
+#pragma unroll
+        for (int i = 1; i <= kMaxHalf; i++) {
+            if (i <= H) {
+                const int nv = imin(cur + f, imin(v1[i - 1], v2[i - 1] + f)) + compute_error(s, lds.thr[i][lane]);
+                v2[i - 1] = v1[i - 1];
+                v1[i - 1] = cur;
+                cur = nv;
+            }
+        }
+        lds.ring[t % kRing][lane] = cur << 8 | s;
+    }
+    // second half: level k at column t - 2k.  True once column j = t - 2H has all its rows (j >= H), its cost in `total`.
+    __device__ __forceinline__ bool advance(MatchLds &lds, int lane, int L, int f, int t, int N, int &total)
+    {
+        const int H = L / 2;
+#pragma unroll
+        for (int k = 0; k < kMaxHalf; k++) {
+            if (k < H) {
+                const int c = t - 2 * k;
+                int val = kInf;
+                if (c >= 0 && c < N) {
+                    const int sc = lds.ring[c % kRing][lane] & 255;
+                    const int ev = compute_error(sc, lds.thr[L - 1 - k][lane]);
+                    if (k == 0) val = ev;
+                    else val = imin(w2[k - 1] + f, imin(w1[k - 1], w0[k - 1] + f)) + ev;
+                }
+                w2[k] = w1[k];
+                w1[k] = w0[k];
+                w0[k] = val;
+            }
+        }
+        const int j = t - 2 * H;
+        if (j < H) return false;
+        int fw2 = kInf, fw1 = kInf, fw0 = kInf;
+#pragma unroll
+        for (int k = 0; k < kMaxHalf; k++)
+            if (k == H - 1) {
+                fw2 = w2[k];
+                fw1 = w1[k];
+                fw0 = w0[k];
+            }
+        total = (lds.ring[j % kRing][lane] >> 8) + imin(fw2 + f, imin(fw1, fw0 + f));
+        return true;
+    }
+};
 
 }  // namespace vgs

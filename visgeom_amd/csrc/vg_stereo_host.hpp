@@ -1,4 +1,4 @@
-// vg_stereo_host.hpp -- the host half of the stereo handles (vg_stereo, vg_motion_stereo): the parameter checks and
+// vg_stereo_host.hpp -- the host half of the stereo handles (vg_stereo, vg_motion_stereo): the parameter, camera and pose checks and
 // setTransformation in FP64 -- R12 / R21 / t12, StereoEpipoles and the 2 x (planes + 1) curve tables.  vg_stereo builds them
 // once at creation, vg_motion_stereo for every item of every call; both go through build_geometry, in one arithmetic order.
 #pragma once
@@ -97,6 +97,12 @@ inline bool finite_n(const double *v, int n)
         if (!std::isfinite(v[i])) return false;
     return true;
 }
+
+// what both handles ask of a camera pair and of a pose [t, rotvec] besides finite_n
+inline bool focal_nonzero(const double *c1, const double *c2) { return c1[2] != 0. && c1[3] != 0. && c2[2] != 0. && c2[3] != 0.; }
+inline bool has_baseline(const double *xi) { return xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2] > 1e-10; }   // false for NaN
+
+inline unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // the host half of the handle: transform, epipoles (StereoEpipoles ctor, epipoles.cpp:37-57), curve bases and tables
 // (EnhancedEpipolar::initialize, eucm_epipolar.cpp:33-107); `table` holds 2 x (num_epipolar_planes + 1) entries

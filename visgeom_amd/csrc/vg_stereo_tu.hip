@@ -44,8 +44,6 @@ struct vg_stereo {
 
 namespace {
 
-unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
 // device pointers of one chunk's scratch (or of the caller's buffers, for the stage entries)
 struct Bufs {
     uint8_t *err = nullptr, *step = nullptr, *sal = nullptr, *skip = nullptr;
@@ -93,7 +91,7 @@ void launch_cost(vg_stereo *s, int64_t n, const uint8_t *img1, const uint8_t *im
     a.salient = b.sal;
     a.skip = b.skip;
     a.n_pairs = n;
-    hipLaunchKernelGGL(vgs::stereo_curve_cost_kernel, dim3(blocks_of(n * s->P, vgs::kCostLanes)), dim3(vgs::kCostLanes), 0, s->stream,
+    hipLaunchKernelGGL(vgs::stereo_curve_cost_kernel, dim3(blocks_of(n * s->P, vgs::kMatchLanes)), dim3(vgs::kMatchLanes), 0, s->stream,
                        s->g, a);
 }
 
@@ -179,9 +177,8 @@ int vg_stereo_create(vg_stereo **out, int device, void *hip_stream, const double
     if (const int rc = check_params(*params, x_max, y_max)) return rc;
     if (!finite_n(eucm1, 6) || !finite_n(eucm2, 6) || !finite_n(xi12, 6))
         return fail(VG_ERR_INVALID_ARGUMENT, "camera parameters and transformation must be finite");
-    if (eucm1[2] == 0. || eucm1[3] == 0. || eucm2[2] == 0. || eucm2[3] == 0.) return fail(VG_ERR_INVALID_ARGUMENT, "fu, fv must be non-zero");
-    if (!(xi12[0] * xi12[0] + xi12[1] * xi12[1] + xi12[2] * xi12[2] > 1e-10))
-        return fail(VG_ERR_INVALID_ARGUMENT, "the stereo baseline must not vanish (|t|^2 > 1e-10)");
+    if (!focal_nonzero(eucm1, eucm2)) return fail(VG_ERR_INVALID_ARGUMENT, "fu, fv must be non-zero");
+    if (!has_baseline(xi12)) return fail(VG_ERR_INVALID_ARGUMENT, "the stereo baseline must not vanish (|t|^2 > 1e-10)");
     std::unique_ptr<vg_stereo> s(new (std::nothrow) vg_stereo());
     if (!s) return fail(VG_ERR_ALLOC, "out of host memory");
     s->prm = *params;
