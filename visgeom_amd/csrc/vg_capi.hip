@@ -81,9 +81,10 @@ int64_t emit_nt_min_bytes()
     return h ? (int64_t)h : (int64_t)230000000;
 }
 
-// Store policy of a single-dataset emit launch by its output: non-temporal past the Infinity Cache (emit_nt_min_bytes), write-through
+// Store policy of an emit launch (single-dataset or merged) by its output: non-temporal past the Infinity Cache (emit_nt_min_bytes), write-through
 // inside it.  Write-through (`sc1`) leaves no dirty Jacobian lines in the XCD L2s for the launch's end to wait on
-// (profiles/r10_emit_store_policy.txt).  hook emit_write_through: -1 = plain stores inside the cache (the policy before), 0 = the default.
+// (profiles/r10_emit_store_policy.txt); a merged launch (vg_emit_multi_kernel) decides by its summed output: the stereo pair's 104 MB step
+// 25.05 -> 23.5 us with write-through, the rig's 591 MB stay non-temporal (profiles/r14_emit_head_tail.md).  hook emit_write_through: -1 = plain stores inside the cache (the policy before), 0 = the default.
 int emit_store_policy(int64_t launch_output_bytes)
 {
     if (launch_output_bytes >= emit_nt_min_bytes()) return vg::kStoreNonTemporal;
@@ -196,8 +197,12 @@ void fill_emit_args_at(const vg_problem *p, const Dataset &d, vg::EmitArgs &a, i
     a.chain_stride = d.L ? d.chain.stride[0] : 0;
     a.seq_index = d.seq_identity ? nullptr : d.d_seq + b0;
     a.first_block = b0;
-    a.nt_stores = emit_store_policy(emit_output_bytes(a, cam.K));  // a merged launch decides for all its datasets together (plain or non-temporal)
+    a.nt_stores = emit_store_policy(emit_output_bytes(a, cam.K));  // a merged launch decides for all its datasets together
     a.map_window = emit_map_window(emit_output_bytes(a, cam.K));   // likewise
+#ifdef VG_EMIT_STAMPS
+    a.stamps = reinterpret_cast<unsigned long long *>(vgi::debug_hook(vgi::kHookEmitStamps));
+    a.stamps_waves = (unsigned long long)vgi::debug_hook(vgi::kHookEmitStampsWaves);
+#endif
 }
 
 // the same with whole-dataset arrays: block b0's rows lie b0 blocks into each of them
@@ -220,7 +225,7 @@ long long g_debug_hooks[vgi::kHookCount] = {0};
 const char *const kDebugHookNames[vgi::kHookCount] = {"inline_chain_max_bytes", "gram_no_merge", "max_obs_per_launch", "solver_timing",
                                                       "solver_host_loop", "solver_device_loop", "solver_no_fold_frames", "solver_fold_max_groups",
                                                       "emit_nt_min_bytes", "host_chunk_bytes", "gram_persistent", "emit_map_window",
-                                                      "emit_write_through"};
+                                                      "emit_write_through", "emit_stamps", "emit_stamps_waves"};
 }  // namespace
 long long vgi::debug_hook(vgi::DebugHook h) { return g_debug_hooks[h]; }
 #endif
@@ -812,7 +817,7 @@ int vg_problem_evaluate(vg_problem *p, const vg_dataset_outputs *outs)
             int64_t launch_bytes = 0;
             for (int k = 0; k < m.n; k++) launch_bytes += emit_output_bytes(m.ds[k], p->cams[p->dss[shared[g0 + k]].camera].K);
             for (int k = 0; k < m.n; k++) {
-                m.ds[k].nt_stores = launch_bytes >= emit_nt_min_bytes() ? vg::kStoreNonTemporal : vg::kStorePlain;
+                m.ds[k].nt_stores = emit_store_policy(launch_bytes);
                 m.ds[k].map_window = emit_map_window(launch_bytes);
             }
         }
@@ -823,6 +828,8 @@ int vg_problem_evaluate(vg_problem *p, const vg_dataset_outputs *outs)
         for (int k = 0; k < m.n; k++) longest += (m.first_tile[k + 1] - m.first_tile[k] + 7) / 8;
         if (m.ds[0].nt_stores == vg::kStoreNonTemporal)
             hipLaunchKernelGGL(vg::vg_emit_multi_kernel<vg::kStoreNonTemporal>, dim3(8 * longest), dim3(vg::kEmitThreads), lds, p->stream, m);
+        else if (m.ds[0].nt_stores == vg::kStoreWriteThrough)
+            hipLaunchKernelGGL(vg::vg_emit_multi_kernel<vg::kStoreWriteThrough>, dim3(8 * longest), dim3(vg::kEmitThreads), lds, p->stream, m);
         else
             hipLaunchKernelGGL(vg::vg_emit_multi_kernel<vg::kStorePlain>, dim3(8 * longest), dim3(vg::kEmitThreads), lds, p->stream, m);
         VG_HIP(hipGetLastError());

@@ -35,7 +35,9 @@ enum DebugHook {
     kHookHostChunkBytes,           // chunk size of vg_dataset_evaluate_to_host in bytes (0 = the default, 32 MiB): tests force many small chunks
     kHookGramPersistent,           // persistent form of the direct Gram kernel (vg_gram_valu_pers_kernel): 1 = never, 2 / 3 = its four- / eight-wave shape whenever it applies, 0 = by size
     kHookEmitMapWindow,            // tile map of the emit launches: W > 0 = windows of 8 W tiles, XCD x the x-th run of W tiles in each (1 = linear map); -1 = one contiguous eighth per XCD (the map before round 6); 0 = the default (kEmitMapWindow)
-    kHookEmitWriteThrough,         // store policy of single-dataset emit launches inside the Infinity Cache: -1 = plain stores; 0 = the default (write-through, emit_store_policy)
+    kHookEmitWriteThrough,         // store policy of emit launches inside the Infinity Cache: -1 = plain stores; 0 = the default (write-through, emit_store_policy)
+    kHookEmitStamps,               // measurement build (-DVG_EMIT_STAMPS) only: device address of the per-wave clock stamps of the next emit launches
+    kHookEmitStampsWaves,          // with emit_stamps: the number of waves that buffer holds (4 stamps of 8 bytes each); waves past it do not stamp
     kHookCount
 };
 #ifdef VG_DEBUG_HOOKS

@@ -162,7 +162,23 @@ struct EmitArgs {
     int nt_stores;         // store policy of the launch (EmitStorePolicy): 1 = past the Infinity Cache, non-temporal; 2 = inside it, write-through
     unsigned int map_window;  // tile map of the launch: 0 = every XCD one contiguous eighth of the tiles; W > 0 = windows of 8 W tiles,
                               // XCD x the x-th run of W tiles in each window (W = 1: the linear map); xcd_window_block, kEmitMapWindow
+#ifdef VG_EMIT_STAMPS   // measurement build (tools/exp/emit_stamps_probe.py): four wall-clock stamps (100 MHz) per wave of the launch, or NULL
+    unsigned long long *stamps;
+    unsigned long long stamps_waves;   // waves the buffer holds: a launch with more stamps only those
+#endif
 };
+
+#ifdef VG_EMIT_STAMPS
+// stamp k of this wave: 0 entry, 1 after the barrier, 2 at the first store, 3 after the last store; an ordinary vector store of lane 0
+__device__ __forceinline__ void emit_stamp(const EmitArgs &a, int k)
+{
+    const unsigned long long w = (unsigned long long)blockIdx.x * (kEmitThreads / kWave) + (threadIdx.x >> 6);
+    if (a.stamps && w < a.stamps_waves && (threadIdx.x & (kWave - 1)) == 0) a.stamps[w * 4 + k] = wall_clock64();
+}
+#define VG_EMIT_STAMP(a, k) emit_stamp(a, k)
+#else
+#define VG_EMIT_STAMP(a, k) ((void)0)
+#endif
 
 // Each lane holds the 2S doubles of its observation's two rows; the wave's 64 observations are one
 // contiguous 1024*S-byte run of the output.  Lanes write their rows to the wave's private LDS tile
@@ -326,22 +342,19 @@ __device__ __forceinline__ unsigned int xcd_window_block(unsigned int b, unsigne
     return base + x * q + (x < r ? x : r) + i;
 }
 
-// The store sequence of one tile: its residual pair, then (WANT_JAC) the intrinsic and pose row blocks through the wave's LDS tile.
-// With the frames in LDS nothing in it waits on vmcnt from its first store on: every global load of the tile was consumed before it.
+// The Jacobian row blocks of one tile (WANT_JAC), after its residual pair has left: the intrinsic and pose row blocks through the wave's
+// LDS tile.  With the frames in LDS nothing waits on vmcnt from the tile's first store on: every global load was consumed before it.
 template <int MODEL, bool WANT_JAC, int POLICY>
-__device__ __forceinline__ void emit_tile_stores(const EmitArgs &a, const unsigned int o0, bool active, const HIP_vector_type<double, 2> &r,
+__device__ __forceinline__ void emit_tile_rows(const EmitArgs &a, const unsigned int o0, const unsigned int o_end,
                                                  const CornerEval<CameraTraits<MODEL>::K> &e, double X0, double X1, double X2,
                                                  const double *fr, double *stage)
 {
     constexpr int K = CameraTraits<MODEL>::K;
-    using d2 = HIP_vector_type<double, 2>;
     const int lane = threadIdx.x & (kWave - 1);
-    if (active) stream_store16<POLICY>(reinterpret_cast<d2 *>(a.res) + o0 + threadIdx.x, r);
-
     if (WANT_JAC) {
         const unsigned int ow = o0 + (threadIdx.x & ~(kWave - 1));  // first observation of this wave
         int n_valid = 0;
-        if (ow < a.n_obs) n_valid = (a.n_obs - ow < (unsigned)kWave) ? (int)(a.n_obs - ow) : kWave;
+        if (ow < o_end) n_valid = (o_end - ow < (unsigned)kWave) ? (int)(o_end - ow) : kWave;
 
         // intrinsic block, rows 2i / 2i+1 of [2N x K]       calib_cost_functions.cpp:105-114
         if (a.jac_intr) {
@@ -370,9 +383,13 @@ __device__ __forceinline__ void emit_tile_stores(const EmitArgs &a, const unsign
 // (thread f walks image b_first + f with build_frame_single_direct) instead of reading them from the chain-prep
 // kernel's output -- a full evaluation is then ONE launch.
 // One 256-observation tile of one dataset (o0 = first observation of the tile), its stores of policy POLICY (EmitStorePolicy).
-template <int MODEL, bool WANT_JAC, bool FRAMES_LDS, bool INLINE_CHAIN, int POLICY>
+// HEAD_FIRST (the single-dataset kernel): the tile is ordered for an early first store -- the chain parameters are its first load and
+// the residual pair leaves before the Jacobian arithmetic.  The merged kernel keeps the plain order: with the early order its stereo
+// launch ran 18.5-18.7 us against the parent's 18.1 and the rig's 100.3-101.1 against 99.4-99.5 (profiles/r14_emit_head_tail.md).
+template <int MODEL, bool WANT_JAC, bool FRAMES_LDS, bool INLINE_CHAIN, int POLICY, bool HEAD_FIRST = false>
 __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int o0)
 {
+    VG_EMIT_STAMP(a, 0);
     static_assert(!INLINE_CHAIN || FRAMES_LDS, "the inline chain writes its frames to LDS");
     constexpr int K = CameraTraits<MODEL>::K;
     using d2 = HIP_vector_type<double, 2>;
@@ -381,9 +398,28 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wave = tid >> 6;
+    const unsigned int o_end = o0 + kEmitThreads < a.n_obs ? o0 + kEmitThreads : a.n_obs;   // o0 < n_obs
+    const unsigned int b_first = o0 / a.N;
+
+    // INLINE_CHAIN, HEAD_FIRST: the walk is the longest dependent chain in front of the tile's first store; its parameters are the first load of
+    // the kernel, ahead of the per-lane address arithmetic (an integer division by the run-time N) of the board / observation loads.
+    // A tile of 256 consecutive observations touches at most 256 images: at most one frame per thread (as a loop the walk was
+    // scheduled across iterations and cost 16 more VGPRs: 114 instead of 98).
+    const unsigned int nf = (o_end - 1) / a.N - b_first + 1;
+    double xi_r[6];
+    auto load_chain_params = [&]() {
+        if ((unsigned)tid < nf) {
+            const long long bi = (long long)b_first + tid;
+            const long long si = a.seq_index ? (long long)a.seq_index[bi] : a.first_block + bi;
+#pragma unroll
+            for (int k = 0; k < 6; k++) xi_r[k] = (a.chain_params + a.chain_stride * si)[k];
+        }
+    };
+    if (INLINE_CHAIN && HEAD_FIRST) load_chain_params();
+
     const unsigned int o = o0 + tid;
-    const bool active = o < a.n_obs;
-    const unsigned int oc = active ? o : a.n_obs - 1;
+    const bool active = o < o_end;
+    const unsigned int oc = active ? o : o_end - 1;
     const unsigned int b = oc / a.N;
     const unsigned int c = oc - b * a.N;
 
@@ -394,23 +430,14 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
     const double *fr;
     if (FRAMES_LDS) {
         double *fr_lds = smem + (kEmitThreads / kWave) * emit_stage_doubles_per_wave<MODEL>();
-        const unsigned int b_first = o0 / a.N;
-        const unsigned int o_last = (o0 + kEmitThreads - 1 < a.n_obs) ? o0 + kEmitThreads - 1 : a.n_obs - 1;
-        const unsigned int nf = o_last / a.N - b_first + 1;
         if (INLINE_CHAIN) {
-            // a tile of 256 consecutive observations touches at most 256 images: at most one frame per thread (as a loop
-            // the walk was scheduled across iterations and cost 16 more VGPRs: 114 instead of 98)
+            if (!HEAD_FIRST) load_chain_params();
             if (const unsigned int f = tid; f < nf) {
-                const long long bi = (long long)b_first + f;
-                const long long si = a.seq_index ? (long long)a.seq_index[bi] : a.first_block + bi;
                 {   // The short walk of the Gram kernels (one sincos at the half angle, R12 = I, M12 from uhat^2 = u u^T - I: the
                     // reference's frame to 1e-16; inside and just above its first-order branches it IS the reference-order
                     // routine).  While <= 4 lanes walk, the tile's other 252 wait at the barrier below with no store in
                     // flight: a third of the chain gone is 36.3 -> 34.1 us at 10 k images, 22.0 -> 19.8 at 5 k, 161 -> 152 at 50 k
                     // (same box, alternating; profiles/r06q_emit_fastwalk_ab.txt).  The corner arithmetic stays in reference order.
-                    double xi_r[6];
-#pragma unroll
-                    for (int k = 0; k < 6; k++) xi_r[k] = (a.chain_params + a.chain_stride * si)[k];
                     build_frame_single_direct_fast(xi_r, fr_lds + f * a.frame_stride_d);
                 }
             }
@@ -421,6 +448,7 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
             for (int i = tid; i < n16; i += kEmitThreads) dst[i] = src[i];
         }
         __syncthreads();
+        VG_EMIT_STAMP(a, 1);
         fr = fr_lds + (b - b_first) * a.frame_stride_d;
     } else {
         fr = a.frames + (size_t)b * a.frame_stride_d;
@@ -431,8 +459,16 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
     const double X1 = (fr[3] * g0 + fr[4] * g1 + fr[5] * g2) + fr[10];
     const double X2 = (fr[6] * g0 + fr[7] * g1 + fr[8] * g2) + fr[11];
 
+    // HEAD_FIRST: the projection alone first: the residual pair leaves before the Jacobian arithmetic below starts (the same operations in the
+    // same order per value as in one eval_corner<.., WANT_JAC, WANT_JAC>: what the two calls share is computed once, here).
+    // The intrinsics are read once, into registers: the store below is a memory barrier to the compiler, and a second read behind it
+    // would be a global load the wave waits for with its own store in flight.
+    double intr[K];
+#pragma unroll
+    for (int i = 0; i < K; i++) intr[i] = a.intr[i];
     CornerEval<K> e;
-    eval_corner<MODEL, WANT_JAC, WANT_JAC>(a.intr, X0, X1, X2, e);
+    if (HEAD_FIRST) eval_corner<MODEL, false, false>(intr, X0, X1, X2, e);
+    else eval_corner<MODEL, WANT_JAC, WANT_JAC>(intr, X0, X1, X2, e);
 
     // residual pair, or the in-band failure value       calib_cost_functions.cpp:57-71
     d2 r;
@@ -460,7 +496,14 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
         }
     }
 
-    emit_tile_stores<MODEL, WANT_JAC, POLICY>(a, o0, active, r, e, X0, X1, X2, fr, smem + wave * emit_stage_doubles_per_wave<MODEL>());
+    VG_EMIT_STAMP(a, 2);
+    if (active) stream_store16<POLICY>(reinterpret_cast<d2 *>(a.res) + o, r);
+
+    if (WANT_JAC) {
+        if (HEAD_FIRST) eval_corner<MODEL, true, true>(intr, X0, X1, X2, e);
+        emit_tile_rows<MODEL, WANT_JAC, POLICY>(a, o0, o_end, e, X0, X1, X2, fr, smem + wave * emit_stage_doubles_per_wave<MODEL>());
+    }
+    VG_EMIT_STAMP(a, 3);
 }
 
 // POLICY: the launch's store policy (EmitArgs::nt_stores), a template argument so that the tile's stores are straight-line code
@@ -474,7 +517,7 @@ template <int MODEL, bool WANT_JAC, bool FRAMES_LDS, bool INLINE_CHAIN, int POLI
 __global__ __launch_bounds__(kEmitThreads) __attribute__((amdgpu_waves_per_eu(VG_EMIT_WAVES, 8))) void vg_emit_kernel(EmitArgs a)
 {
     const unsigned int t = a.map_window ? xcd_window_block(blockIdx.x, gridDim.x, a.map_window) : xcd_contiguous_block(blockIdx.x, gridDim.x);
-    emit_tile<MODEL, WANT_JAC, FRAMES_LDS, INLINE_CHAIN, POLICY>(a, t * (unsigned)kEmitThreads);
+    emit_tile<MODEL, WANT_JAC, FRAMES_LDS, INLINE_CHAIN, POLICY, true>(a, t * (unsigned)kEmitThreads);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -507,7 +550,7 @@ __device__ __forceinline__ void emit_tile_route(const EmitArgs &a, unsigned int 
 }
 
 #ifdef VG_TU_CORE  // this kernel is launched by one translation unit only; the others see the header without it
-// POLICY: the store policy of the launch, shared by all its datasets (plain or non-temporal)
+// POLICY: the store policy of the launch, shared by all its datasets (emit_store_policy on the launch's summed output)
 template <int POLICY>
 __global__ __launch_bounds__(kEmitThreads) __attribute__((amdgpu_waves_per_eu(VG_EMIT_MULTI_WAVES, 8))) void vg_emit_multi_kernel(EmitMultiArgs m)
 {
