@@ -20,7 +20,7 @@ def heads(tmp_path_factory):
     hipcc = isa.hipcc()
     if hipcc is None:
         pytest.skip("hipcc not found")
-    text = isa.device_asm(hipcc, "vg_capi.hip", str(tmp_path_factory.mktemp("isa_head") / "vg_capi.s"))
+    text = isa.device_asm(hipcc, "vg_emit_tu.hip", str(tmp_path_factory.mktemp("isa_head") / "vg_emit_tu.s"))
     out = {}
     for m in re.finditer(r"^(_Z\w+):", text, flags=re.M):
         if HEADLINE.match(m.group(1)):
@@ -69,7 +69,7 @@ def test_merged_emit_kernel_keeps_four_waves_and_no_scratch(tmp_path):
     hipcc = isa.hipcc()
     if hipcc is None:
         pytest.skip("hipcc not found")
-    meta = isa.kernel_metadata(isa.device_asm(hipcc, "vg_capi.hip", str(tmp_path / "vg_capi.s")))
+    meta = isa.kernel_metadata(isa.device_asm(hipcc, "vg_emit_tu.hip", str(tmp_path / "vg_emit_tu.s")))
     multi = [k for k in meta if "vg_emit_multi_kernel" in k]
     assert len(multi) == 3, multi
     for k in multi:

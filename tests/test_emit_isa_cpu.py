@@ -22,7 +22,7 @@ def asm(tmp_path_factory):
     hipcc = isa.hipcc()
     if hipcc is None:
         pytest.skip("hipcc not found")
-    return isa.device_asm(hipcc, "vg_capi.hip", str(tmp_path_factory.mktemp("isa") / "vg_capi.s"))
+    return isa.device_asm(hipcc, "vg_emit_tu.hip", str(tmp_path_factory.mktemp("isa") / "vg_emit_tu.s"))
 
 
 def kernel_bodies(text):

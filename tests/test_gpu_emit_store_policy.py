@@ -1,4 +1,4 @@
-"""The store policy of the emit launches inside the Infinity Cache (vg_kernels.hpp: stream_store16, vg_capi.hip: emit_store_policy):
+"""The store policy of the emit launches inside the Infinity Cache (vg_kernels.hpp: stream_store16, vg_emit_launch.hpp: emit_store_policy):
 write-through (`sc1`) 16-byte stores by default, plain write-back stores under the hook emit_write_through = -1.  The policy changes
 where the lines wait, never what is written: both must give the same rows BIT FOR BIT, the failed-projection count included."""
 import numpy as np

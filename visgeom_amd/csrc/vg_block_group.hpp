@@ -63,7 +63,7 @@ namespace vgg {
 
 using vgi::fail;
 
-inline int ensure_private(vg_block *b);  // the block's own one-image problem (vg_capi.hip)
+inline int ensure_private(vg_block *b);  // the block's own one-image problem (vg_block_tu.hip)
 
 inline bool same_board(const std::vector<double> &a, const std::vector<double> &b)
 {

@@ -2,7 +2,7 @@
 // (include/calibration/unified_calibration.h:91-180, src/calibration/unified_calibration.cpp) for problems made of
 // grid-reprojection residual blocks.  Same JSON schema (README.md:36-223), same parse order and error behaviour,
 // same pose-initialisation recipe, same report / image_error_<i>.txt formats; the numerical work (pose refinement,
-// the solve) goes through the C ABI of this library to the GPU.  Included at the end of vg_capi.hip.
+// the solve) goes through the C ABI of this library to the GPU.  Included by vg_frontend_tu.hip.
 //
 // Differences from the reference, all stated in DESIGN.md section 8:
 //   * "images" datasets read 8-bit PGM files (images.prefix / images.names) and find the board with this library's corner

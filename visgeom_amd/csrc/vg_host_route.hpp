@@ -1,6 +1,6 @@
 // vg_host_route.hpp -- vg_dataset_evaluate_to_host: one evaluation delivered to HOST memory (the route of a Ceres
 // EvaluationCallback, INTEGRATION.md section 2: ceres::Solve at src/calibration/unified_calibration.cpp:53 walks the residual
-// blocks after ONE batched evaluation).  Included by vg_capi.hip (it uses that unit's launch helpers).
+// blocks after ONE batched evaluation).  Included by vg_emit_tu.hip; the launches go through vg_emit_launch.hpp.
 //
 // The rows are 208 bytes per observation on a bus of ~55 GB/s: the evaluation is 36 us of kernel in front of 3.6 ms of copy at
 // the headline size.  So the route is built around the copy:
@@ -17,6 +17,7 @@
 
 #include <cstring>
 
+#include "vg_emit_launch.hpp"
 #include "vg_host_parallel.hpp"
 
 namespace {
@@ -42,19 +43,15 @@ extern "C" int vg_dataset_evaluate_to_host(vg_problem *p, int dataset_id, double
     if (rc != VG_OK) return rc;
     if (!p->finalized) return fail(VG_ERR_STATE, "problem not finalized");
     Dataset &d = p->dss[dataset_id];
-    d.epoch = (d.epoch + 1) & 0xFFFFFFull;
-    if (d.epoch == 0) d.epoch = 1;
+    next_epoch(d);
     if (!d.n_blocks) return VG_OK;
     if (!residuals) return fail(VG_ERR_INVALID_ARGUMENT, "residuals is NULL");
     VG_HIP(hipSetDevice(p->device));
     const Camera &cam = p->cams[d.camera];
     const int K = cam.K;
     bool want_jm[vg::kMaxChain] = {false};
-    bool want_jac = jac_intr != nullptr;
-    for (int l = 0; l < d.L; l++) {
-        want_jm[l] = jac_member && jac_member[l];
-        want_jac = want_jac || want_jm[l];
-    }
+    for (int l = 0; l < d.L; l++) want_jm[l] = jac_member && jac_member[l];
+    const bool want_jac = wants_jacobian(d, jac_intr, jac_member);
     // doubles per image in a chunk: residuals, then the requested Jacobian arrays
     const size_t rows = 2 * (size_t)d.N;
     size_t per_image = rows;
@@ -65,10 +62,7 @@ extern "C" int vg_dataset_evaluate_to_host(vg_problem *p, int dataset_id, double
     int64_t chunk_images = (chunk_hook > 0 ? (int64_t)chunk_hook : kHostChunkBytes) / (int64_t)(per_image * sizeof(double));
     if (chunk_images < 1) chunk_images = 1;
     if ((d.n_blocks + chunk_images - 1) / chunk_images > kHostMaxChunks) chunk_images = (d.n_blocks + kHostMaxChunks - 1) / kHostMaxChunks;
-    {   // the launches index observations with 32 bits
-        const int64_t max_blocks = (((int64_t)1 << 30) / d.N) > 0 ? ((int64_t)1 << 30) / d.N : 1;
-        if (chunk_images > max_blocks) chunk_images = max_blocks;
-    }
+    if (chunk_images > max_blocks_per_launch(d)) chunk_images = max_blocks_per_launch(d);  // the launches index observations with 32 bits
     const int n_chunks = (int)((d.n_blocks + chunk_images - 1) / chunk_images);
 
     // destinations: all pinned -> straight from the copy engine; otherwise through the library's pinned staging block.  (A few
@@ -125,13 +119,9 @@ extern "C" int vg_dataset_evaluate_to_host(vg_problem *p, int dataset_id, double
             }
         vg::EmitArgs a;
         fill_emit_args_at(p, d, a, b0, nb, c_res, c_ji, c_jm);
-        a.nt_stores = 0;
-        switch (cam.model) {
-        case VG_MODEL_EUCM: rc = launch_emit<vg::kEUCM>(p->stream, a, want_jac, inline_chain); break;
-        case VG_MODEL_UCM: rc = launch_emit<vg::kUCM>(p->stream, a, want_jac, inline_chain); break;
-        default: rc = launch_emit<vg::kMEI>(p->stream, a, want_jac, inline_chain); break;
-        }
-        if (rc != VG_OK) return rc;
+        a.nt_stores = vg::kStorePlain;  // chunks are small: see the header
+        a.map_window = emit_map_window(emit_output_bytes(a, K));
+        if ((rc = launch_emit(p->stream, cam.model, a, want_jac, inline_chain)) != VG_OK) return rc;
         VG_HIP(hipEventRecord(d.host_chunk_ready[(size_t)k], p->stream));
         VG_HIP(hipStreamWaitEvent(cs, d.host_chunk_ready[(size_t)k], 0));
         const size_t chunk_doubles = per_image * (size_t)nb;

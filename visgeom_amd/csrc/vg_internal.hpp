@@ -274,7 +274,7 @@ inline int valid_dataset(const vg_problem *p, int d)
 }
 
 // kernel launches on an explicit parameter buffer (the solver evaluates candidate points without
-// touching the problem's own parameter vector); implemented in vg_capi.hip
+// touching the problem's own parameter vector); implemented in vg_emit_tu.hip
 int prepare_at(vg_problem *p, const double *d_params);
 int ensure_frames(vg_problem *p);  // chain prep at the problem's own parameters if the frames are stale
 // sum != NULL: also the fixed-order sum over the dataset's blocks, [W*W] (one extra launch on the vector-pipe route)

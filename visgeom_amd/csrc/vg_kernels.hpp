@@ -56,7 +56,7 @@ struct PrepMultiArgs {
 };
 constexpr unsigned int kPrepStagedMinWaves = 512;   // 32 768 images
 
-#ifdef VG_TU_CORE  // this kernel is launched by one translation unit only; the others see the header without it
+#ifdef VG_TU_EMIT  // these kernels are launched by one translation unit only; the others see the header without them
 // problems of more than kPrepMax datasets: the descriptors in a table in global memory, one lane per block across all datasets
 __global__ __launch_bounds__(64) void vg_chain_prep_table_kernel(const double *__restrict__ params,
                                                                   const PrepDataset *__restrict__ dsets, int n_dsets,
@@ -333,7 +333,7 @@ __device__ __forceinline__ unsigned int xcd_contiguous_block(unsigned int b, uns
 // on the same box and arrays; where the eighths run at full rate, 341 us, the windows give 344 us); inside the Infinity Cache
 // the maps do not differ.  The counters say it is the DRAM side: no address-translation misses (TCP_UTCL1_TRANSLATION_MISS
 // 1e3 of 4e7 requests), FEWER L2 -> fabric credit stalls and fewer writes in flight than at 1 GB, i.e. requests retire slower.
-constexpr unsigned int kEmitMapWindow = 16;   // runs of 16 tiles: 384 KiB of a 6-column Jacobian array per die and window (launches >= 1.2 GB: emit_map_window, vg_capi.hip)
+constexpr unsigned int kEmitMapWindow = 16;   // runs of 16 tiles: 384 KiB of a 6-column Jacobian array per die and window (launches >= 1.2 GB: emit_map_window, vg_emit_launch.hpp)
 __device__ __forceinline__ unsigned int xcd_window_block(unsigned int b, unsigned int n, unsigned int W)
 {
     const unsigned int x = b & 7u, j = b >> 3, w = j / W, i = j - w * W, base = w * 8u * W, rem = n - base;
@@ -549,7 +549,6 @@ __device__ __forceinline__ void emit_tile_route(const EmitArgs &a, unsigned int 
     else emit_tile<MODEL, true, true, false, POLICY>(a, o0);
 }
 
-#ifdef VG_TU_CORE  // this kernel is launched by one translation unit only; the others see the header without it
 // POLICY: the store policy of the launch, shared by all its datasets (emit_store_policy on the launch's summed output)
 template <int POLICY>
 __global__ __launch_bounds__(kEmitThreads) __attribute__((amdgpu_waves_per_eu(VG_EMIT_MULTI_WAVES, 8))) void vg_emit_multi_kernel(EmitMultiArgs m)
@@ -575,80 +574,5 @@ __global__ __launch_bounds__(kEmitThreads) __attribute__((amdgpu_waves_per_eu(VG
     default: emit_tile_route<kMEI, POLICY>(m.ds[d], o0, inl); break;
     }
 }
-#endif
-
-// ------------------------------------------------------------------------------------------
-// measurement helpers: pure streaming write / copy with the emit kernel's store pattern -- every wave
-// instruction moves 1 KiB of consecutive bytes (16 B per lane) and a workgroup owns one contiguous
-// 16 KiB run.  Used to calibrate rocprofv3's FETCH_SIZE / WRITE_SIZE and as the box's measured
-// streaming rate.
-// ------------------------------------------------------------------------------------------
-constexpr int kStreamUnroll = 4;
-
-#ifdef VG_TU_CORE  // this kernel is launched by one translation unit only; the others see the header without it
-__global__ __launch_bounds__(256) void vg_stream_write_kernel(double *__restrict__ dst, long long n2, double value)
-{
-    using d2 = HIP_vector_type<double, 2>;
-    d2 v;
-    v.x = value;
-    v.y = value;
-    d2 *d = reinterpret_cast<d2 *>(dst);
-    const long long base = (long long)blockIdx.x * (256 * kStreamUnroll) + threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < kStreamUnroll; k++) {
-        const long long i = base + k * 256;
-        if (i < n2) d[i] = v;
-    }
-}
-#endif
-
-#ifdef VG_TU_CORE  // this kernel is launched by one translation unit only; the others see the header without it
-__global__ __launch_bounds__(256) void vg_stream_copy_kernel(double *__restrict__ dst, const double *__restrict__ src,
-                                                              long long n2)
-{
-    using d2 = HIP_vector_type<double, 2>;
-    d2 *d = reinterpret_cast<d2 *>(dst);
-    const d2 *s = reinterpret_cast<const d2 *>(src);
-    const long long base = (long long)blockIdx.x * (256 * kStreamUnroll) + threadIdx.x;
-    d2 t[kStreamUnroll];
-#pragma unroll
-    for (int k = 0; k < kStreamUnroll; k++) {
-        const long long i = base + k * 256;
-        if (i < n2) t[k] = s[i];
-    }
-#pragma unroll
-    for (int k = 0; k < kStreamUnroll; k++) {
-        const long long i = base + k * 256;
-        if (i < n2) d[i] = t[k];
-    }
-}
-#endif
-
-// What the FP64 vector pipe delivers on this box under the occupancy of the fused Gram kernels (two waves per SIMD: 256-thread
-// workgroups, two per CU by their LDS reservation): every lane runs kFmaChains independent chains of dependent v_fma_f64 -- no
-// memory, a loop of a few hundred bytes.  The guide's 78.6 TFLOP/s assume 2.4 GHz; under this load the part runs lower
-// (profiles/NOTES.md, tools/exp/fp64_ramp.hip), and bench.py prints this next to the Gram kernel's roofline fraction.
-constexpr int kFmaChains = 8;
-#ifdef VG_TU_CORE  // this kernel is launched by one translation unit only; the others see the header without it
-__global__ __launch_bounds__(256) void vg_fp64_fma_kernel(double *__restrict__ out, int iters, double seed)
-{
-    extern __shared__ double fma_pad[];   // reserves the LDS that limits a CU to two workgroups; never touched
-    double x[kFmaChains];
-#pragma unroll
-    for (int i = 0; i < kFmaChains; i++) x[i] = seed + 1e-3 * i + 1e-9 * threadIdx.x;
-    const double a = 1.0000001, b = 1e-9;
-#pragma unroll 4
-    for (int k = 0; k < iters; k++)
-#pragma unroll
-        for (int i = 0; i < kFmaChains; i++) x[i] = __builtin_fma(x[i], a, b);
-    double t = 0.;
-#pragma unroll
-    for (int i = 0; i < kFmaChains; i++) t += x[i];
-    if (t == 12345.678) {   // never: keeps the chains alive
-        fma_pad[threadIdx.x] = t;
-        out[blockIdx.x] = fma_pad[threadIdx.x ^ 1];
-    }
-}
-#endif
 
 }  // namespace vg

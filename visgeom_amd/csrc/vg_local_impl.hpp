@@ -1,6 +1,5 @@
 // vg_local_impl.hpp -- host side of the localization reprojection costs (vg_local.hpp): resident sets of blocks, the
-// batched device entries and the per-block host entries that mirror Ceres' Evaluate contract.  Included at the end of
-// vg_capi.hip (the library is one translation unit).
+// batched device entries and the per-block host entries that mirror Ceres' Evaluate contract.  Included by vg_local_tu.hip.
 #include <memory>
 #include <new>
 

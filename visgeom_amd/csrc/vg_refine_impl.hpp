@@ -1,4 +1,4 @@
-// vg_refine_impl.hpp -- host side of vg_refine_poses (kernel: vg_pose_lm.hpp).  Included at the end of vg_capi.hip.
+// vg_refine_impl.hpp -- host side of vg_refine_poses (kernel: vg_pose_lm.hpp).  Included by vg_refine_tu.hip.
 #pragma once
 
 #include <mutex>
