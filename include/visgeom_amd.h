@@ -710,6 +710,50 @@ int vg_motion_stereo_mask(vg_motion_stereo *s, uint8_t *mask);
 int vg_motion_stereo_select(vg_motion_stereo *s, int64_t n, const double *xi12, const uint8_t *img2, const double *depth_in,
                             const double *sigma_in, const double *cost_in, int32_t *record);
 
+/* =====================================================================================
+ * 11. Depth map propagation and fusion: what the reference's mapping loop does to a key frame's map besides refining it
+ *     (src/localization/mapping.cpp:181-220) -- DepthMap::wrapDepth, merge and filterNoise (src/reconstruction/depth_map.cpp).
+ *     Maps are the (depth, sigma, cost) triples of sections 9 and 10: DEVICE FP64 [n][y_max][x_max], depth 0 = none.  Every
+ *     call is synchronous on the handle's stream and checks its arguments before HIP is touched.  Constants (stereo_misc.h):
+ *     MIN_DEPTH 0.25, OUT_OF_RANGE 0, DEFAULT_SIGMA_DEPTH 30, DEFAULT_COST_DEPTH 5.  Deviations: DESIGN.md section 9,
+ *     "Depth map propagation".
+ * ===================================================================================== */
+typedef struct vg_depth_fusion vg_depth_fusion;
+/* A handle for maps of one EUCM camera (eucm: HOST 6 intrinsics; the reference warps within one camera).  Of `params` only
+ * the ScaleParameters fields are read (scale, u0, v0, u_max, v_max, x_max, y_max, equal_margins), under the ranges of
+ * vg_stereo_create.  The handle owns its scratch (12 bytes per depth pixel and item for the warp, 16 for the filter in
+ * place); a second call with the same n allocates nothing. */
+int vg_depth_fusion_create(vg_depth_fusion **out, int device, void *hip_stream, const double *eucm, const vg_stereo_params *params);
+void vg_depth_fusion_destroy(vg_depth_fusion *h);
+int vg_depth_fusion_size(const vg_depth_fusion *h, int *x_max, int *y_max);
+/* DepthMap::wrapDepth (depth_map.cpp:723-760) of n maps: item k is carried into the frame xi12[k] (HOST [n][6], [t, rotvec] of the
+ * new key frame in the old, the argument of vg_motion_stereo_compute; every entry finite).  A source pixel with depth >=
+ * MIN_DEPTH is reconstructed at its range, moved by the inverse transformation, projected and rounded to a target pixel; a
+ * target keeps the source with the smallest new range (on an exact tie the smallest source index) and holds that range,
+ * sigma_in + 0.005 range and cost_in; a target no source reaches holds 0 / 30 / 5.  The result is bit-identical from run to
+ * run.  The outputs must not overlap the inputs or each other.  counts (HOST int64 [n][6], may be NULL): sources, dropped by
+ * reconstructPoint, dropped by projectPoint, outside the map, lost the depth test, targets written; [0] is the sum of [1..5]. */
+int vg_depth_warp(vg_depth_fusion *h, int64_t n, const double *xi12, const double *depth_in, const double *sigma_in,
+                  const double *cost_in, double *depth, double *sigma, double *cost, int64_t *counts);
+/* DepthMap::merge (depth_map.cpp:917-958) of map 2 into map 1, in place; cost is not touched.  Per pixel: depth2 < MIN_DEPTH
+ * skipped; depth 0: map 2's pair copied; |depth - depth2| < 2 (sigma + sigma2): the two fused by filter (depth_map.cpp:32-36);
+ * else the nearer of the two kept.  The four arrays must not overlap.  counts (HOST int64 [n][5], may be NULL): skipped,
+ * copied, fused, replaced by map 2, kept. */
+int vg_depth_merge(vg_depth_fusion *h, int64_t n, double *depth, double *sigma, const double *depth2, const double *sigma2,
+                   int64_t *counts);
+/* DepthMap::filterNoise (depth_map.cpp:868-914): every interior pixel with a depth is compared with its eight neighbours of
+ * the INPUT map; it is cleared (0 / 0) when fewer than two neighbours hold a depth or fewer than two, and not all, of them
+ * match it, and otherwise becomes the mean of itself (weight 5) and the matching neighbours.  Border pixels, and maps with
+ * x_max < 3 or y_max < 3, pass through.  depth == depth_in and sigma == sigma_in are allowed (the handle then reads its own
+ * copy); any other overlap of an output with an input is refused.  counts (HOST int64 [n][3], may be NULL): interior pixels
+ * with a depth, cleared, smoothed. */
+int vg_depth_filter_noise(vg_depth_fusion *h, int64_t n, const double *depth_in, const double *sigma_in, double *depth, double *sigma,
+                          int64_t *counts);
+/* Host only, for the key-frame loop: Transformation::inverse (transformation.h:112-119) and inverseCompose (:90-99, a^-1 o b:
+ * the pose b re-expressed in the frame a), on [t, rotvec]. */
+int vg_transform_inverse(const double *xi, double *out6);
+int vg_transform_inverse_compose(const double *a6, const double *b6, double *out6);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",
  * "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop", "solver_no_fold_frames",

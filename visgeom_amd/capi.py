@@ -210,6 +210,14 @@ SIGNATURES = {
     "vg_motion_stereo_compute": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64p]),
     "vg_motion_stereo_mask": (ctypes.c_int, [_vp, _vp]),
     "vg_motion_stereo_select": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _vp, _vp, _vp, _vp, _vp]),
+    "vg_depth_fusion_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, _dp, _vp]),
+    "vg_depth_fusion_destroy": (None, [_vp]),
+    "vg_depth_fusion_size": (ctypes.c_int, [_vp, _ip, _ip]),
+    "vg_depth_warp": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _i64p]),
+    "vg_depth_merge": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _i64p]),
+    "vg_depth_filter_noise": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _i64p]),
+    "vg_transform_inverse": (ctypes.c_int, [_dp, _dp]),
+    "vg_transform_inverse_compose": (ctypes.c_int, [_dp, _dp, _dp]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),

@@ -1,0 +1,223 @@
+// vg_depth.hpp -- depth map propagation and fusion: DepthMap::wrapDepth, merge and filterNoise of the reference
+// (src/reconstruction/depth_map.cpp:723-760, 917-958, 868-914) on the EUCM device functions of vg_stereo_device.hpp.
+// The warp is a forward splat in three launches over all items: every source min-reduces the bit pattern of its range into a
+// 64-bit z-buffer entry of its target, every source whose range won min-reduces its index into a 32-bit winner entry, and
+// every target gathers the winner's sigma and cost.  Integer min is commutative, so the map is the one the reference's ascending
+// loop with a strict "<" leaves, bit for bit and from run to run.  Merge and the noise filter are one elementwise launch each.
+// Evaluated in the order written (-ffp-contract=off), so tests/depth_ref.py agrees bit for bit.
+#pragma once
+
+#include "vg_stereo_device.hpp"
+
+namespace vgd {
+
+using namespace vgs;
+
+constexpr double kDefaultSigma = 30.;   // DEFAULT_SIGMA_DEPTH (stereo_misc.h)
+constexpr double kDefaultCost = 5.;     // DEFAULT_COST_DEPTH
+constexpr int kLanes = 256;
+constexpr unsigned long long kZEmpty = ~0ull;
+constexpr unsigned kNoWinner = ~0u;
+
+struct Grid {   // ScaleParameters
+    int scale, u0, v0, x_max, y_max;
+};
+
+// one item of a warp call, as it goes up and comes back: the pose and the counters (zero on the way up)
+struct WarpItem {
+    double Rinv[9], t[3];
+    unsigned long long counts[6];   // sources, dropped by reconstruct, dropped by project, outside the map, reached a target, targets written
+};
+
+struct WarpArgs {
+    WarpItem *item;   // DEVICE [n]
+    double cam[6];
+    Grid g;
+    int64_t P;
+    const double *depth_in, *sigma_in, *cost_in;   // [n][P]
+    unsigned long long *zbuf;                      // [n][P], all ones between calls
+    unsigned *winner;                              // [n][P], all ones between calls
+    double *depth, *sigma, *cost;                  // [n][P]
+    bool count;
+#ifdef VG_DEPTH_WARP_STORE
+    int *src_target;    // [n][P]: what (a) found per source, -1 for none
+    double *src_dist;
+#endif
+};
+
+enum : int { kNotSource = 0, kDropReconstruct = 1, kDropProject = 2, kOutside = 3, kReached = 4 };
+
+// one source pixel of wrapDepth: its target index and its range in the new frame
+VGS_HD int warp_source(const double *cam, const Grid &g, const WarpItem &it, int64_t pix, double d, int64_t &target, double &dist)
+{
+    if (!(d >= kMinDepth)) return kNotSource;   // getIdxVec (depth_map.cpp:525); false for NaN
+    const int x = (int)(pix % g.x_max), y = (int)(pix / g.x_max);
+    double X[3], X1[3], X2[3], q[2];
+    if (!eucm_reconstruct(cam, (double)(x * g.scale + g.u0), (double)(y * g.scale + g.v0), X)) return kDropReconstruct;
+    const double nrm = sqrt(dot3(X, X));
+    for (int i = 0; i < 3; i++) X1[i] = X[i] / nrm * d - it.t[i];   // normalized() * depth, then inverseTransform
+    mat_vec(it.Rinv, X1, X2);
+    if (!eucm_project(cam, X2, q)) return kDropProject;
+    dist = sqrt(dot3(X2, X2));
+    if (!(dist > 0.)) return kDropProject;   // a point at the new origin: project refuses it already (denom < 1e-3)
+    if (!coord_ok(q)) return kOutside;       // NaN or beyond +-2^24, before any conversion to int
+    const int xd = round_int((q[0] - g.u0) / g.scale), yd = round_int((q[1] - g.v0) / g.scale);   // xConv, yConv
+    if (xd < 0 || xd >= g.x_max || yd < 0 || yd >= g.y_max) return kOutside;
+    target = (int64_t)yd * g.x_max + xd;
+    return kReached;
+}
+
+// every lane of the block calls this: one atomic per wave and counter
+__device__ __forceinline__ void count_wave(unsigned long long *c, bool hit)
+{
+    const int k = __popcll(__ballot(hit));
+    if ((threadIdx.x & 63) == 0 && k) atomicAdd(c, (unsigned long long)k);
+}
+
+// (a) the z-buffer: min over the sources of a target of the bits of dist (monotone for positive doubles)
+__global__ __launch_bounds__(kLanes) void depth_warp_zbuf_kernel(WarpArgs a)
+{
+    const int64_t item = blockIdx.y, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
+    int st = kNotSource;
+    if (pix < a.P) {
+        int64_t target = 0;
+        double dist = 0.;
+        st = warp_source(a.cam, a.g, a.item[item], pix, a.depth_in[item * a.P + pix], target, dist);
+        if (st == kReached) atomicMin(a.zbuf + item * a.P + target, (unsigned long long)__double_as_longlong(dist));
+#ifdef VG_DEPTH_WARP_STORE
+        a.src_target[item * a.P + pix] = st == kReached ? (int)target : -1;
+        a.src_dist[item * a.P + pix] = dist;
+#endif
+    }
+    if (a.count) {
+        unsigned long long *c = a.item[item].counts;
+        count_wave(c + 0, st != kNotSource);
+        for (int k = kDropReconstruct; k <= kReached; k++) count_wave(c + k, st == k);
+    }
+}
+
+// (b) the winner: among the sources whose range is the target's minimum, the smallest index.  The source is recomputed
+// (8 bytes read again and the arithmetic of (a)); -DVG_DEPTH_WARP_STORE builds the other shape, in which (a) stores the
+// target and the range (12 bytes per source) and (b) loads them: DESIGN.md section 5.12.
+__global__ __launch_bounds__(kLanes) void depth_warp_winner_kernel(WarpArgs a)
+{
+    const int64_t item = blockIdx.y, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
+    if (pix >= a.P) return;
+    int64_t target = 0;
+    double dist = 0.;
+#ifdef VG_DEPTH_WARP_STORE
+    target = a.src_target[item * a.P + pix];
+    if (target < 0) return;
+    dist = a.src_dist[item * a.P + pix];
+#else
+    if (warp_source(a.cam, a.g, a.item[item], pix, a.depth_in[item * a.P + pix], target, dist) != kReached) return;
+#endif
+    if (a.zbuf[item * a.P + target] == (unsigned long long)__double_as_longlong(dist)) atomicMin(a.winner + item * a.P + target, (unsigned)pix);
+}
+
+// (c) one lane per target: gather the winner, write the three maps, leave the scratch all ones for the next call
+__global__ __launch_bounds__(kLanes) void depth_warp_gather_kernel(WarpArgs a)
+{
+    const int64_t item = blockIdx.y, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
+    bool written = false;
+    if (pix < a.P) {
+        const int64_t gi = item * a.P + pix;
+        const unsigned w = a.winner[gi];
+        double d = 0., s = kDefaultSigma, c = kDefaultCost;   // DepthMap's initial values
+        if (w != kNoWinner) {
+            d = __longlong_as_double((long long)a.zbuf[gi]);
+            s = a.sigma_in[item * a.P + w] + 0.005 * d;
+            c = a.cost_in[item * a.P + w];
+            a.zbuf[gi] = kZEmpty;
+            a.winner[gi] = kNoWinner;
+            written = true;
+        }
+        a.depth[gi] = d;
+        a.sigma[gi] = s;
+        a.cost[gi] = c;
+    }
+    if (a.count) count_wave(a.item[item].counts + 5, written);
+}
+
+// DepthMap::merge (depth_map.cpp:917-958), in place on map 1; counts [n][5]: skipped, copied, fused, replaced, kept
+__global__ __launch_bounds__(kLanes) void depth_merge_kernel(double *depth, double *sigma, const double *depth2, const double *sigma2,
+                                                            int64_t P, unsigned long long *counts)
+{
+    const int64_t item = blockIdx.y, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
+    int st = -1;
+    if (pix < P) {
+        const int64_t gi = item * P + pix;
+        const double d2 = depth2[gi];
+        st = 0;
+        if (!(d2 < kMinDepth || d2 == 0.)) {
+            const double s2 = sigma2[gi];
+            double d = depth[gi], s = sigma[gi];
+            if (d == 0.) {
+                d = d2;
+                s = s2;
+                st = 1;
+            } else if (fabs(d - d2) < 2 * (s + s2)) {
+                fuse(d, s, d2, s2);
+                st = 2;
+            } else if (d2 < d) {
+                d = d2;
+                s = s2;
+                st = 3;
+            } else {
+                st = 4;
+            }
+            if (st != 4) {
+                depth[gi] = d;
+                sigma[gi] = s;
+            }
+        }
+    }
+    if (counts)
+        for (int k = 0; k < 5; k++) count_wave(counts + item * 5 + k, st == k);
+}
+
+// DepthMap::filterNoise (depth_map.cpp:868-914): reads (depth_in, sigma_in) only, writes every pixel of (depth, sigma);
+// counts [n][3]: interior pixels with a depth, cleared, smoothed
+__global__ __launch_bounds__(kLanes) void depth_filter_noise_kernel(const double *depth_in, const double *sigma_in, double *depth, double *sigma,
+                                                                   Grid g, int64_t P, unsigned long long *counts)
+{
+    const int dx[8] = {-1, 0, 1, 1, 1, 0, -1, -1}, dy[8] = {1, 1, 1, 0, -1, -1, -1, 0};
+    const int64_t item = blockIdx.y, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
+    int st = 0;   // 1 cleared, 2 smoothed
+    if (pix < P) {
+        const double *din = depth_in + item * P, *sin = sigma_in + item * P;
+        const int x = (int)(pix % g.x_max), y = (int)(pix / g.x_max);
+        double d = din[pix], s = sin[pix];
+        if (x >= 1 && x < g.x_max - 1 && y >= 1 && y < g.y_max - 1 && d != 0.) {
+            int filled = 0, matches = 0;
+            double acc = d * 5;   // CENTRAL_WEIGHT
+            for (int i = 0; i < 8; i++) {
+                const int64_t j = (int64_t)(y + dy[i]) * g.x_max + (x + dx[i]);
+                const double nd = din[j];
+                if (nd == 0.) continue;
+                filled++;
+                const double err = fabs(d - nd);
+                if (err > s || err > 3 * sin[j]) continue;
+                matches++;
+                acc += nd;
+            }
+            if ((matches < 2 && matches < filled) || filled < 2) {
+                d = 0.;
+                s = 0.;
+                st = 1;
+            } else {
+                d = acc / (matches + 5);
+                st = 2;
+            }
+        }
+        depth[item * P + pix] = d;
+        sigma[item * P + pix] = s;
+    }
+    if (counts) {
+        count_wave(counts + item * 3 + 0, st != 0);
+        count_wave(counts + item * 3 + 1, st == 1);
+        count_wave(counts + item * 3 + 2, st == 2);
+    }
+}
+
+}  // namespace vgd

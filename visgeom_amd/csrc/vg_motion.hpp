@@ -1,6 +1,6 @@
 // vg_motion.hpp -- motion stereo: the reference's MotionStereo (src/reconstruction/eucm_motion_stereo.cpp) on the device
 // functions of vg_stereo_device.hpp (Poly2, Raster, EUCM reconstruct / project, curve index, epipole choice, the four-point
-// triangulation, the descriptor and its matching).
+// triangulation, the descriptor and its matching; MIN_DEPTH, the coordinate limit and DepthMap's filter, shared with vg_depth.hpp).
 // Two kernels: the gradient mask of the key frames (computeMask) and one lane per (item, depth pixel) through selectPoint,
 // computeUncertainty, sampleImage and reconstruct.  Every item has its own StereoGeom in device memory (the pose changes with
 // every call).  Evaluated in the order written (-ffp-contract=off), so tests/motion_ref.py agrees bit for bit.
@@ -14,8 +14,6 @@ using namespace vgs;
 
 // status of a depth pixel: the stage that rejected it, or what reconstruct did
 enum : int { kRejSelect = 1, kRejUncertainty = 2, kTooCertain = 3, kRejSample = 4, kNotUpdated = 5, kUpdated = 6 };
-constexpr double kMinDepth = 0.25;          // MIN_DEPTH (stereo_misc.h:24)
-constexpr double kCoordLimit = 16777216.;   // a projected search end beyond +-2^24 px is refused
 
 struct Rec {   // the record of vg_motion_stereo_select, 16 x int32
     int status, gstep, gu2, gv2, su, sv, fu, fv, disp_max, inverted, best, best_cost, index2, pad0, pad1, pad2;
@@ -81,18 +79,6 @@ struct MotionArgs {
     int64_t P;
     int gradient_thresh;
 };
-
-VGS_HD double dmax(double a, double b) { return a < b ? b : a; }   // std::max
-
-VGS_HD bool coord_ok(const double *pt) { return fabs(pt[0]) <= kCoordLimit && fabs(pt[1]) <= kCoordLimit; }   // false for NaN
-
-// filter (depth_map.cpp:32-37)
-VGS_HD void fuse(double &v1, double &s1, double v2, double s2)
-{
-    const double K = 1. / (s1 + s2);
-    v1 = (v1 * s2 + v2 * s1) * K;
-    s1 = dmax(s1 * s2 * K, 0.05 * v1);
-}
 
 // MotionStereo::compute (eucm_motion_stereo.cpp:258-358) for one depth pixel per lane.  The descriptor, its thresholds and
 // compareDescriptor's DP are vg_stereo_device.hpp's, as in stereo_curve_cost_kernel; here the samples are the prior's segment

@@ -396,4 +396,20 @@ struct MatchDp {
     }
 };
 
+// ---- what motion stereo (vg_motion.hpp) and the depth map operations (vg_depth.hpp) share
+constexpr double kMinDepth = 0.25;          // MIN_DEPTH (stereo_misc.h:24)
+constexpr double kCoordLimit = 16777216.;   // a projected point beyond +-2^24 px is refused
+
+VGS_HD double dmax(double a, double b) { return a < b ? b : a; }   // std::max
+
+VGS_HD bool coord_ok(const double *pt) { return fabs(pt[0]) <= kCoordLimit && fabs(pt[1]) <= kCoordLimit; }   // false for NaN
+
+// filter (depth_map.cpp:32-37)
+VGS_HD void fuse(double &v1, double &s1, double v2, double s2)
+{
+    const double K = 1. / (s1 + s2);
+    v1 = (v1 * s2 + v2 * s1) * K;
+    s1 = dmax(s1 * s2 * K, 0.05 * v1);
+}
+
 }  // namespace vgs
