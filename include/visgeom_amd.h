@@ -754,6 +754,54 @@ int vg_depth_filter_noise(vg_depth_fusion *h, int64_t n, const double *depth_in,
 int vg_transform_inverse(const double *xi, double *out6);
 int vg_transform_inverse_compose(const double *a6, const double *b6, double *out6);
 
+/* =====================================================================================
+ * 12. Photometric localization: the reference's ScalePhotometric::computePose (src/localization/photometric.cpp:46-157) -- the
+ *     pose of a new image against a key frame's depth map, by minimising the photometric error coarse to fine over a binary
+ *     image pyramid (BinaryScalSpace, include/localization/scale_space.h) with PhotometricCostFunction
+ *     (src/localization/local_cost_functions.cpp:35-210).  Images are DEVICE u8 [height][width], the depth map DEVICE FP64
+ *     [y_max][x_max] (sections 9 to 11), poses HOST [t, rotvec] of the new frame's base in the key frame's base.  Every call is
+ *     synchronous on the handle's stream and checks its arguments before HIP is touched.  Constants: GRAD_THRESH 250,
+ *     DIST_MAX 50, grey limit 240, LOSS_FACTOR 3, margin 50 / scale pixels, at most 150 iterations per scale.  Deviations:
+ *     DESIGN.md section 9, "Photometric localization".
+ * ===================================================================================== */
+typedef struct vg_photometric vg_photometric;
+/* A handle for one EUCM camera (eucm: HOST 6 intrinsics), the depth map's geometry (of `params` only the ScaleParameters
+ * fields are read, as by vg_depth_fusion_create), xi_base_cam (HOST [6], the camera in the base frame), the image size and
+ * num_scales in [1, 8] pyramid levels (the reference uses 5); level i is (width >> i) x (height >> i), and a num_scales that
+ * shrinks the coarsest level to zero size is refused. */
+int vg_photometric_create(vg_photometric **out, int device, void *hip_stream, const double *eucm, const vg_stereo_params *params,
+                          const double *xi_base_cam, int width, int height, int num_scales);
+void vg_photometric_destroy(vg_photometric *h);
+int vg_photometric_level_size(const vg_photometric *h, int scale_idx, int *width, int *height);
+/* setBaseImage + setDepth + initPhotometricData of every scale: the key frame's pyramid with its Sobel / 8 gradients, and per
+ * scale the data pack -- the pixels with gu^2 + gv^2 >= 250 whose depth (DepthMap::nearest at the pixel's full-size position)
+ * is neither 0 nor above 50, whose grey is at most 240 and which reconstruct, in raster order: packed index v * cols + u, grey
+ * value, and the point at its depth moved by xi_base_cam.  The depth map is read during the call only. */
+int vg_photometric_set_base(vg_photometric *h, const uint8_t *img, const double *depth);
+/* setTargetImage of n images (DEVICE u8 [n][height][width], n in [1, 65535]): n pyramids, one launch per level; they replace
+ * the earlier targets. */
+int vg_photometric_set_targets(vg_photometric *h, int64_t n, const uint8_t *imgs);
+/* Stage entry: one pyramid level as DEVICE float [rows][cols], each output may be NULL: target = -1 the key frame, else a
+ * target index.  A target's gradients are computed for this call (the reference keeps none for the target). */
+int vg_photometric_level(vg_photometric *h, int64_t target, int scale_idx, float *img, float *grad_u, float *grad_v);
+/* Stage entry: the data pack of a scale.  *count (HOST) receives the number of points; indices (DEVICE int32 [count]), values
+ * (DEVICE FP64 [count]) and cloud (DEVICE FP64 [count][3]) may be NULL -- ask for the count first. */
+int vg_photometric_pack(vg_photometric *h, int scale_idx, int64_t *count, int32_t *indices, double *values, double *cloud);
+/* PhotometricCostFunction::Evaluate of n poses at one scale: xi HOST [n][6], target HOST int32 [n] (which target image a pose
+ * is matched against).  With m the pack's count: residuals DEVICE [n][m], jacobians DEVICE [n][m][6]; cost (1/2 sum r^2, HOST
+ * [n]), jtj (J^T J, upper triangle row-major, HOST [n][21]) and jtr (J^T r, HOST [n][6]).  Any output may be NULL.  A point
+ * that does not project, or that projects into the margin of 50 / scale pixels, has a zero residual and a zero row.  The sums
+ * are FP64, added in a fixed order: bit-identical from run to run. */
+int vg_photometric_evaluate(vg_photometric *h, int scale_idx, int64_t n, const double *xi, const int32_t *target, double *residuals,
+                            double *jacobians, double *cost, double *jtj, double *jtr);
+/* computePose of n start poses (HOST [n][6]) against target[k] each: from the coarsest scale to the finest a trust-region
+ * Levenberg-Marquardt of at most 150 iterations with Ceres' default tolerances, all poses advancing in the same launches.
+ * xi_prior (HOST [n][6], or NULL for none) adds the reference's OdometryPrior(0.03, 0.03, 0.01, 0.01, xi_prior[k]) rows (the
+ * reference passes the start pose).  xi_out HOST [n][6]; report (HOST [n][num_scales][4], may be NULL): iterations, initial
+ * cost, final cost, vg_termination per scale. */
+int vg_photometric_compute_pose(vg_photometric *h, int64_t n, const double *xi_start, const int32_t *target, const double *xi_prior,
+                                double *xi_out, double *report);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",
  * "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop", "solver_no_fold_frames",

@@ -218,6 +218,15 @@ SIGNATURES = {
     "vg_depth_filter_noise": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _i64p]),
     "vg_transform_inverse": (ctypes.c_int, [_dp, _dp]),
     "vg_transform_inverse_compose": (ctypes.c_int, [_dp, _dp, _dp]),
+    "vg_photometric_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, _dp, _vp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "vg_photometric_destroy": (None, [_vp]),
+    "vg_photometric_level_size": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _ip]),
+    "vg_photometric_set_base": (ctypes.c_int, [_vp, _vp, _vp]),
+    "vg_photometric_set_targets": (ctypes.c_int, [_vp, ctypes.c_int64, _vp]),
+    "vg_photometric_level": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
+    "vg_photometric_pack": (ctypes.c_int, [_vp, ctypes.c_int, _i64p, _vp, _vp, _vp]),
+    "vg_photometric_evaluate": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _dp, _i32p, _vp, _vp, _dp, _dp, _dp]),
+    "vg_photometric_compute_pose": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _i32p, _dp, _dp, _dp]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),

@@ -1,0 +1,613 @@
+// vg_photometric_tu.hip -- translation unit of libvisgeom_amd.so: photometric pose estimation against a depth key frame
+// (section 12 of the C ABI).  Built with hipcc for gfx950 only; compiled on its own so that an edit of one subsystem does not
+// rebuild the others.
+//
+// A vg_photometric handle owns the base pyramid with its gradients, the data pack of every scale (built once per key frame),
+// the target pyramids, and the staging of a cost evaluation: the per-pose frames and the 28 sums per pose in pinned memory.
+// compute_pose drives the trust-region loop from the host: per iteration one upload of the candidate frames, the cost and the
+// reduce launch over all poses that still move, and one download of 28 doubles per pose.
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <vector>
+
+#include "vg_internal.hpp"
+#include "vg_local.hpp"
+#include "vg_photometric.hpp"
+#include "vg_stereo_host.hpp"
+#include "vg_transf_host.hpp"
+
+struct vg_photometric {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    double cam[6], xbc[6];
+    vgp::Grid g;
+    int levels = 0, w[vgp::kMaxLevels], h[vgp::kMaxLevels];
+    int64_t off[vgp::kMaxLevels + 1];   // pixel offset of a level inside one pyramid; off[levels] = pixels of a pyramid
+    bool has_base = false;
+    int64_t n_targets = 0, cap_targets = 0, cap_poses = 0, cap_partials = 0;
+    int64_t m[vgp::kMaxLevels];         // points of the pack per scale
+    vgi::DeviceMem<float> d_base, d_targets, d_grad;   // [3][total]: img | gu | gv; [n][total]; [2][level 0] for vg_photometric_level
+    vgi::DeviceMem<int32_t> d_idx;                     // the packs: level i at off[i], room for every pixel
+    vgi::DeviceMem<double> d_val, d_cloud;
+    vgi::DeviceMem<unsigned> d_counts, d_offsets, d_total;
+    vgi::PinnedMem<unsigned> h_total;
+    vgi::DeviceMem<vgp::PoseFrame> d_frames;
+    vgi::PinnedMem<vgp::PoseFrame> h_frames;
+    vgi::DeviceMem<double> d_partials, d_sums;
+    vgi::PinnedMem<double> h_sums;
+};
+
+namespace {
+
+using vgi::fail;
+using vgsh::blocks_of;
+using vgth::Array6d;
+constexpr int64_t kMaxItems = 65535;   // poses and targets ride on gridDim.y
+constexpr int kMaxIterations = 150;    // photometric.cpp:150
+// Ceres' defaults, which the reference leaves in place (photometric.cpp:148-150), under the rules of the calibration LM
+// (lm_accept of vg_solver_device.hpp: step quality, radius update, the three tolerances)
+constexpr double kFtol = 1e-6, kGtol = 1e-10, kPtol = 1e-8, kRadius0 = 1e4, kMaxRadius = 1e16, kMinRadius = 1e-32;
+constexpr double kMinRelDecrease = 1e-3, kDiagMin = 1e-6, kDiagMax = 1e32;
+
+int64_t level_pixels(const vg_photometric *s, int i) { return (int64_t)s->w[i] * s->h[i]; }
+
+// the frame of pose xi: xiCam = xi o xi_base_cam for the points, CameraJacobian(camera, xi, xi_base_cam) for the rows
+void make_frame(const vg_photometric *s, const double *xi, int target, bool active, vgp::PoseFrame &f)
+{
+    Array6d a, b;
+    std::memcpy(a.data(), xi, sizeof(double) * 6);
+    std::memcpy(b.data(), s->xbc, sizeof(double) * 6);
+    const Array6d c = vgth::compose(a, b);
+    const vg::RotTrig rt = vg::rot_trig(c.data() + 3, true, false);
+    vg::rotation_matrix(c.data() + 3, -1., rt, f.Rinv);
+    for (int i = 0; i < 3; i++) f.t[i] = c[i];
+    vg::camera_jacobian_frame(xi, s->xbc, f.L11, f.L12, f.L22);
+    f.target = target;
+    f.active = active ? 1 : 0;
+}
+
+int ensure_poses(vg_photometric *s, int64_t n)
+{
+    if (n <= s->cap_poses) return VG_OK;
+    s->cap_poses = 0;
+    if (s->d_frames.alloc((size_t)n * sizeof(vgp::PoseFrame)) != hipSuccess || s->d_sums.alloc((size_t)n * vgp::kSums * sizeof(double)) != hipSuccess)
+        return fail(VG_ERR_ALLOC, "device allocation of the photometric poses failed");
+    if (s->h_frames.alloc((size_t)n * sizeof(vgp::PoseFrame), hipHostMallocDefault) != hipSuccess ||
+        s->h_sums.alloc((size_t)n * vgp::kSums * sizeof(double), hipHostMallocDefault) != hipSuccess)
+        return fail(VG_ERR_ALLOC, "pinned allocation of the photometric staging failed");
+    s->cap_poses = n;
+    return VG_OK;
+}
+
+// the cost of the n frames in h_frames at one scale: residuals / rows to res / jac (DEVICE, may be NULL), the 28 sums per
+// active pose to h_sums when `sums`.  Synchronous.
+int run_cost(vg_photometric *s, int scale, int64_t n, double *res, double *jac, bool sums)
+{
+    const int64_t m = s->m[scale];
+    if (m == 0) {
+        if (sums) std::memset(s->h_sums.get(), 0, (size_t)n * vgp::kSums * sizeof(double));
+        return VG_OK;
+    }
+    const unsigned blocks = blocks_of(m, vgp::kLanes);
+    if (sums && n * blocks > s->cap_partials) {
+        s->cap_partials = 0;
+        if (s->d_partials.alloc((size_t)(n * blocks) * vgp::kSums * sizeof(double)) != hipSuccess)
+            return fail(VG_ERR_ALLOC, "device allocation of the photometric partial sums failed");
+        s->cap_partials = n * blocks;
+    }
+    vgi::StreamDrain drain{s->stream};
+    VG_HIP(hipMemcpyAsync(s->d_frames, s->h_frames, (size_t)n * sizeof(vgp::PoseFrame), hipMemcpyHostToDevice, s->stream));
+    vgp::EvalArgs a;
+    a.frames = s->d_frames;
+    a.targets = s->d_targets;
+    a.target_stride = s->off[s->levels];
+    a.level_off = s->off[scale];
+    a.w = s->w[scale];
+    a.h = s->h[scale];
+    const double level_scale = (double)(1 << scale);
+    a.inv_scale = 1. / level_scale;
+    a.margin = vgp::kMarginPixels / level_scale;
+    for (int i = 0; i < 6; i++) a.cam[i] = s->cam[i];
+    a.val = s->d_val.get() + s->off[scale];
+    a.cloud = s->d_cloud.get() + 3 * s->off[scale];
+    a.m = (int)m;
+    a.blocks = (int)blocks;
+    a.res = res;
+    a.jac = jac;
+    a.partials = sums ? s->d_partials.get() : nullptr;
+    hipLaunchKernelGGL(vgp::photo_eval_kernel, dim3(blocks, (unsigned)n), dim3(vgp::kLanes), 0, s->stream, a);
+    if (sums) {
+        hipLaunchKernelGGL(vgp::photo_reduce_kernel, dim3((unsigned)n), dim3(64), 0, s->stream, (const vgp::PoseFrame *)s->d_frames.get(),
+                           (const double *)s->d_partials.get(), (int)blocks, s->d_sums.get());
+        VG_HIP(hipGetLastError());
+        VG_HIP(hipMemcpyAsync(s->h_sums, s->d_sums, (size_t)n * vgp::kSums * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    } else {
+        VG_HIP(hipGetLastError());
+    }
+    drain.armed = false;
+    VG_HIP(hipStreamSynchronize(s->stream));
+    return VG_OK;
+}
+
+int check_poses(const vg_photometric *s, int64_t n, const double *xi, const int32_t *target)
+{
+    if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "photometric handle is NULL");
+    if (!s->has_base) return fail(VG_ERR_INVALID_ARGUMENT, "no key frame: call vg_photometric_set_base first");
+    if (s->n_targets == 0) return fail(VG_ERR_INVALID_ARGUMENT, "no target image: call vg_photometric_set_targets first");
+    if (n < 1 || n > kMaxItems) return fail(VG_ERR_INVALID_ARGUMENT, "the pose count must be in [1, 65535]");
+    if (!xi || !target) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!vgsh::finite_n(xi, 6 * (int)n)) return fail(VG_ERR_INVALID_ARGUMENT, "the poses must be finite");
+    for (int64_t k = 0; k < n; k++)
+        if (target[k] < 0 || target[k] >= s->n_targets) return fail(VG_ERR_INVALID_ARGUMENT, "target index out of range");
+    return VG_OK;
+}
+
+// OdometryPrior(errV, errW, lambdaT, lambdaR, xiOdom) of the localization costs (local_cost_functions.cpp:393-470): the
+// weighting A and the constant Jacobian J, both row-major 6 x 6.  (vg_odometry.hpp holds the calibration's block of the same
+// name, which couples two poses and clamps its variances; this one does neither.)
+struct MotionPrior {
+    double A[36], J[36];
+    Array6d xi;
+};
+
+MotionPrior make_prior(const double *xi_odom)
+{
+    const double errV = 0.03, errW = 0.03, lambdaT = 0.01, lambdaR = 0.01;   // photometric.cpp:143
+    MotionPrior p;
+    std::memcpy(p.xi.data(), xi_odom, sizeof(double) * 6);
+    const double delta = xi_odom[5], l = vg::norm3(xi_odom);
+    const double s = std::sin(delta / 2.), c = std::cos(delta / 2.), l2 = l / 2.;
+    const double dfdu[3][2] = {{c, l2 * s}, {-s, l2 * c}, {0., 1.}};
+    const double Cu[2] = {errV * errV * l * l, errW * errW * delta * delta};
+    const double lam[3] = {lambdaT * lambdaT, lambdaT * lambdaT, lambdaR * lambdaR};
+    double Cx[9];
+    for (int r = 0; r < 3; r++)
+        for (int q = 0; q < 3; q++) Cx[3 * r + q] = dfdu[r][0] * Cu[0] * dfdu[q][0] + dfdu[r][1] * Cu[1] * dfdu[q][1] + (r == q ? lam[r] : 0.);
+    const double c00 = Cx[4] * Cx[8] - Cx[5] * Cx[7], c01 = Cx[5] * Cx[6] - Cx[3] * Cx[8], c02 = Cx[3] * Cx[7] - Cx[4] * Cx[6];
+    const double id = 1. / (Cx[0] * c00 + Cx[1] * c01 + Cx[2] * c02);
+    const double Ci[9] = {c00 * id, (Cx[2] * Cx[7] - Cx[1] * Cx[8]) * id, (Cx[1] * Cx[5] - Cx[2] * Cx[4]) * id,
+                          c01 * id, (Cx[0] * Cx[8] - Cx[2] * Cx[6]) * id, (Cx[2] * Cx[3] - Cx[0] * Cx[5]) * id,
+                          c02 * id, (Cx[1] * Cx[6] - Cx[0] * Cx[7]) * id, (Cx[0] * Cx[4] - Cx[1] * Cx[3]) * id};
+    double L[9] = {0.};   // CxInv = L L^T; LLT::matrixU is L^T: U(i, j) = L[3 j + i]
+    for (int r = 0; r < 3; r++)
+        for (int q = 0; q <= r; q++) {
+            double v = Ci[3 * r + q];
+            for (int k = 0; k < q; k++) v -= L[3 * r + k] * L[3 * q + k];
+            L[3 * r + q] = r == q ? std::sqrt(v) : v / L[3 * q + q];
+        }
+    for (int k = 0; k < 36; k++) p.A[k] = p.J[k] = 0.;
+    p.A[6 * 1 + 1] = L[0];        // U(0, 0)
+    p.A[6 * 0 + 0] = -L[4];       // -U(1, 1)
+    p.A[6 * 0 + 1] = -L[3];       // -U(0, 1)
+    p.A[6 * 0 + 5] = -L[7];       // -U(1, 2)
+    p.A[6 * 1 + 5] = L[6];        // U(0, 2)
+    p.A[6 * 2 + 2] = 1. / lambdaT;
+    p.A[6 * 3 + 3] = 1. / lambdaR;
+    p.A[6 * 4 + 4] = 1. / lambdaR;
+    p.A[6 * 5 + 5] = L[8];        // U(2, 2)
+    double R[9], M[9], RM[9], blk[9], out[9];
+    const vg::RotTrig rt = vg::rot_trig(xi_odom + 3, true, true);
+    vg::rotation_matrix(xi_odom + 3, -1., rt, R);
+    vg::inter_omega_rot(xi_odom + 3, rt, M);
+    vg::mat3_mul(R, M, RM);
+    const int r0[3] = {0, 0, 3}, c0[3] = {0, 3, 3};   // J's blocks: top left A R, top right A R M, bottom right A R M
+    for (int b = 0; b < 3; b++) {
+        for (int r = 0; r < 3; r++)
+            for (int q = 0; q < 3; q++) blk[3 * r + q] = p.A[6 * (r0[b] + r) + c0[b] + q];
+        vg::mat3_mul(blk, b == 0 ? R : RM, out);
+        for (int r = 0; r < 3; r++)
+            for (int q = 0; q < 3; q++) p.J[6 * (r0[b] + r) + c0[b] + q] = out[3 * r + q];
+    }
+    return p;
+}
+
+// OdometryPrior::Evaluate (:472-493) added to the 28 sums of a pose
+void add_prior(const MotionPrior &p, const double *x, double *G)
+{
+    Array6d a;
+    std::memcpy(a.data(), x, sizeof(double) * 6);
+    const Array6d d = vgth::inverse_compose(p.xi, a);
+    double r[6];
+    for (int i = 0; i < 6; i++) {
+        r[i] = 0.;
+        for (int k = 0; k < 6; k++) r[i] += p.A[6 * i + k] * d[k];
+    }
+    int q = 0;
+    for (int i = 0; i < 6; i++)
+        for (int j = i; j < 6; j++, q++)
+            for (int k = 0; k < 6; k++) G[q] += p.J[6 * k + i] * p.J[6 * k + j];
+    for (int i = 0; i < 6; i++)
+        for (int k = 0; k < 6; k++) G[21 + i] += p.J[6 * k + i] * r[k];
+    for (int k = 0; k < 6; k++) G[27] += 0.5 * (r[k] * r[k]);
+}
+
+struct LmPose {
+    double x[6], xc[6], dx[6], G[vgp::kSums];
+    double cost = 0., radius = kRadius0, decrease_factor = 2., mu = 0., gdx = 0., ddx = 0., dx2 = 0., x2 = 0., gmax = 0.;
+    int iterations = 0, term = VG_TERM_NO_CONVERGENCE;
+    bool done = false, step_ok = false;
+};
+
+// (J^T J + mu D) dx = -J^T r, D = clamp(diag(J^T J)): the damped 6 x 6 solve of vg_pose_lm.hpp, on the host
+void lm_step(LmPose &p)
+{
+    double A[6][6], Lc[6][6], g[6], D[6], y[6];
+    int q = 0;
+    for (int i = 0; i < 6; i++)
+        for (int j = i; j < 6; j++, q++) A[i][j] = A[j][i] = p.G[q];
+    p.mu = 1. / p.radius;
+    for (int i = 0; i < 6; i++) {
+        g[i] = p.G[21 + i];
+        D[i] = A[i][i] < kDiagMin ? kDiagMin : (A[i][i] > kDiagMax ? kDiagMax : A[i][i]);
+        A[i][i] += p.mu * D[i];
+    }
+    p.step_ok = true;
+    for (int r = 0; r < 6; r++)
+        for (int c = 0; c <= r; c++) {
+            double s = A[r][c];
+            for (int k = 0; k < c; k++) s -= Lc[r][k] * Lc[c][k];
+            if (r == c) {
+                if (!(s > 0.)) {
+                    p.step_ok = false;
+                    s = 1.;
+                }
+                Lc[r][r] = std::sqrt(s);
+            } else {
+                Lc[r][c] = s / Lc[c][c];
+            }
+        }
+    for (int r = 0; r < 6; r++) {
+        double s = g[r];
+        for (int k = 0; k < r; k++) s -= Lc[r][k] * y[k];
+        y[r] = s / Lc[r][r];
+    }
+    for (int r = 5; r >= 0; r--) {
+        double s = y[r];
+        for (int k = r + 1; k < 6; k++) s -= Lc[k][r] * p.dx[k];
+        p.dx[r] = s / Lc[r][r];
+    }
+    p.gdx = p.ddx = p.dx2 = p.x2 = p.gmax = 0.;
+    for (int k = 0; k < 6; k++) {
+        p.dx[k] = -p.dx[k];
+        p.xc[k] = p.x[k] + p.dx[k];
+        p.gdx += g[k] * p.dx[k];
+        p.ddx += D[k] * p.dx[k] * p.dx[k];
+        p.dx2 += p.dx[k] * p.dx[k];
+        p.x2 += p.x[k] * p.x[k];
+        p.gmax = std::fmax(p.gmax, std::fabs(g[k]));
+        if (!std::isfinite(p.xc[k])) p.step_ok = false;
+    }
+}
+
+// lm_accept of vg_solver_device.hpp for one pose: Gc the sums at the candidate
+void lm_accept(LmPose &p, const double *Gc)
+{
+    p.iterations++;
+    const double cost_c = Gc[27];
+    double rho = 0.;
+    if (p.step_ok) {
+        const double model_change = 0.5 * (p.mu * p.ddx - p.gdx);
+        const double cost_change = p.cost - cost_c;
+        rho = model_change > 0. ? cost_change / model_change : -1.;
+        if (p.gmax <= kGtol) {
+            p.term = VG_TERM_CONVERGENCE_GRADIENT;
+            p.done = true;
+        } else if (std::sqrt(p.dx2) <= kPtol * (std::sqrt(p.x2) + kPtol)) {
+            p.term = VG_TERM_CONVERGENCE_PARAMETER;
+            p.done = true;
+        } else if (model_change > 0. && std::isfinite(cost_c) && std::fabs(p.cost - cost_c) <= kFtol * p.cost) {
+            p.term = VG_TERM_CONVERGENCE_FUNCTION;
+            p.done = true;
+        }
+    }
+    if (p.done) return;
+    if (p.step_ok && std::isfinite(cost_c) && rho > kMinRelDecrease) {
+        for (int k = 0; k < 6; k++) p.x[k] = p.xc[k];
+        std::memcpy(p.G, Gc, sizeof p.G);
+        p.cost = cost_c;
+        const double t = 2. * rho - 1.;
+        p.radius = std::fmin(p.radius / std::fmax(1. - t * t * t, 1. / 3.), kMaxRadius);
+        p.decrease_factor = 2.;
+    } else {
+        p.radius /= p.decrease_factor;
+        p.decrease_factor *= 2.;
+        if (p.radius < kMinRadius) {
+            p.term = VG_TERM_RADIUS_TOO_SMALL;
+            p.done = true;
+        }
+    }
+    if (p.iterations >= kMaxIterations) p.done = true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vg_photometric_create(vg_photometric **out, int device, void *hip_stream, const double *eucm, const vg_stereo_params *params,
+                          const double *xi_base_cam, int width, int height, int num_scales)
+{
+    if (!out) return fail(VG_ERR_INVALID_ARGUMENT, "NULL output");
+    *out = nullptr;
+    if (!eucm || !params || !xi_base_cam) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    const vg_stereo_params &p = *params;   // only the ScaleParameters fields are read, under vg_depth_fusion_create's ranges
+    if (p.scale < 1 || p.scale > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "scale must be in [1, 16384]");
+    if (std::abs(p.u0) > 16384 || std::abs(p.v0) > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "|u0|, |v0| must be at most 16384");
+    int x_max = p.x_max, y_max = p.y_max;
+    if (p.equal_margins) {   // ScaleParameters::setEqualMargin (scale_parameters.cpp:44-52)
+        if (p.u_max < 1 || p.u_max > 16384 || p.v_max < 1 || p.v_max > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "uMax / vMax must be in [1, 16384]");
+        x_max = (p.u_max - 2 * p.u0) / p.scale + 1;
+        y_max = (p.v_max - 2 * p.v0) / p.scale + 1;
+    }
+    if (x_max < 1 || y_max < 1 || x_max > 16384 || y_max > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "xMax / yMax must be in [1, 16384]");
+    if (width < 1 || width > 16384 || height < 1 || height > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "the image size must be in [1, 16384]");
+    if (num_scales < 1 || num_scales > vgp::kMaxLevels) return fail(VG_ERR_INVALID_ARGUMENT, "num_scales must be in [1, 8]");
+    if ((width >> (num_scales - 1)) < 1 || (height >> (num_scales - 1)) < 1)
+        return fail(VG_ERR_INVALID_ARGUMENT, "num_scales shrinks the coarsest level to zero size");
+    if (!vgsh::finite_n(eucm, 6) || !vgsh::finite_n(xi_base_cam, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "camera parameters and xi_base_cam must be finite");
+    if (!vgsh::focal_nonzero(eucm, eucm)) return fail(VG_ERR_INVALID_ARGUMENT, "fu, fv must be non-zero");
+    std::unique_ptr<vg_photometric> s(new (std::nothrow) vg_photometric());
+    if (!s) return fail(VG_ERR_ALLOC, "out of host memory");
+    for (int i = 0; i < 6; i++) {
+        s->cam[i] = eucm[i];
+        s->xbc[i] = xi_base_cam[i];
+    }
+    s->g = vgp::Grid{p.scale, p.u0, p.v0, x_max, y_max};
+    s->levels = num_scales;
+    s->off[0] = 0;
+    for (int i = 0; i < num_scales; i++) {
+        s->w[i] = i ? s->w[i - 1] / 2 : width;
+        s->h[i] = i ? s->h[i - 1] / 2 : height;
+        s->off[i + 1] = s->off[i] + (int64_t)s->w[i] * s->h[i];
+        s->m[i] = 0;
+    }
+    if (const int rc = vgi::check_device(device, "photometric localization")) return rc;
+    s->device = device;
+    s->stream = reinterpret_cast<hipStream_t>(hip_stream);
+    *out = s.release();
+    return VG_OK;
+}
+
+void vg_photometric_destroy(vg_photometric *s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    (void)hipStreamSynchronize(s->stream);
+    delete s;
+}
+
+int vg_photometric_level_size(const vg_photometric *s, int scale_idx, int *width, int *height)
+{
+    if (!s || !width || !height) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (scale_idx < 0 || scale_idx >= s->levels) return fail(VG_ERR_INVALID_ARGUMENT, "scale index out of range");
+    *width = s->w[scale_idx];
+    *height = s->h[scale_idx];
+    return VG_OK;
+}
+
+// the pyramids of n images into dst ([n][total]): one launch per level over all images
+static int build_pyramids(vg_photometric *s, int64_t n, const uint8_t *img, float *dst)
+{
+    const int64_t total = s->off[s->levels];
+    hipLaunchKernelGGL(vgp::photo_convert_kernel, dim3(blocks_of(level_pixels(s, 0), vgp::kLanes), (unsigned)n), dim3(vgp::kLanes), 0, s->stream, img,
+                       dst, level_pixels(s, 0), total);
+    for (int i = 1; i < s->levels; i++)
+        hipLaunchKernelGGL(vgp::photo_down_kernel, dim3(blocks_of(level_pixels(s, i), vgp::kLanes), (unsigned)n), dim3(vgp::kLanes), 0, s->stream, dst,
+                           total, s->off[i - 1], s->w[i - 1], s->h[i - 1], s->off[i], s->w[i], s->h[i]);
+    VG_HIP(hipGetLastError());
+    return VG_OK;
+}
+
+int vg_photometric_set_base(vg_photometric *s, const uint8_t *img, const double *depth)
+{
+    if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "photometric handle is NULL");
+    if (!img || !depth) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    VG_HIP(hipSetDevice(s->device));
+    const int64_t total = s->off[s->levels];
+    s->has_base = false;
+    if (!s->d_base.get()) {
+        const unsigned nb = blocks_of(level_pixels(s, 0), vgp::kLanes);
+        if (s->d_base.alloc((size_t)(3 * total) * sizeof(float)) != hipSuccess || s->d_idx.alloc((size_t)total * sizeof(int32_t)) != hipSuccess ||
+            s->d_val.alloc((size_t)total * sizeof(double)) != hipSuccess || s->d_cloud.alloc((size_t)(3 * total) * sizeof(double)) != hipSuccess ||
+            s->d_counts.alloc((size_t)nb * sizeof(unsigned)) != hipSuccess || s->d_offsets.alloc((size_t)nb * sizeof(unsigned)) != hipSuccess ||
+            s->d_total.alloc(vgp::kMaxLevels * sizeof(unsigned)) != hipSuccess)
+            return fail(VG_ERR_ALLOC, "device allocation of the key frame's pyramid and data packs failed");
+        if (s->h_total.alloc(vgp::kMaxLevels * sizeof(unsigned), hipHostMallocDefault) != hipSuccess)
+            return fail(VG_ERR_ALLOC, "pinned allocation of the pack counts failed");
+    }
+    vgi::StreamDrain drain{s->stream};
+    float *base = s->d_base.get();
+    if (const int rc = build_pyramids(s, 1, img, base)) return rc;
+    vgp::SelectArgs a;
+    for (int i = 0; i < 6; i++) a.cam[i] = s->cam[i];
+    a.g = s->g;
+    a.depth = depth;
+    const vg::RotTrig rt = vg::rot_trig(s->xbc + 3, true, false);
+    vg::rotation_matrix(s->xbc + 3, 1., rt, a.Rb);
+    for (int i = 0; i < 3; i++) a.tb[i] = s->xbc[i];
+    a.block_counts = s->d_counts;
+    a.block_offsets = s->d_offsets;
+    for (int i = 0; i < s->levels; i++) {
+        const unsigned nb = blocks_of(level_pixels(s, i), vgp::kLanes);
+        hipLaunchKernelGGL(vgp::photo_sobel_kernel, dim3(nb, 1), dim3(vgp::kLanes), 0, s->stream, (const float *)(base + s->off[i]),
+                           base + total + s->off[i], base + 2 * total + s->off[i], (int64_t)0, s->w[i], s->h[i]);
+        a.img = base + s->off[i];
+        a.gu = base + total + s->off[i];
+        a.gv = base + 2 * total + s->off[i];
+        a.w = s->w[i];
+        a.h = s->h[i];
+        a.level_scale = 1 << i;
+        a.idx = s->d_idx.get() + s->off[i];
+        a.val = s->d_val.get() + s->off[i];
+        a.cloud = s->d_cloud.get() + 3 * s->off[i];
+        hipLaunchKernelGGL((vgp::photo_select_kernel<false>), dim3(nb), dim3(vgp::kLanes), 0, s->stream, a);
+        hipLaunchKernelGGL(vgp::photo_scan_kernel, dim3(1), dim3(vgp::kLanes), 0, s->stream, (const unsigned *)s->d_counts.get(), s->d_offsets.get(),
+                           (int)nb, s->d_total.get() + i);
+        hipLaunchKernelGGL((vgp::photo_select_kernel<true>), dim3(nb), dim3(vgp::kLanes), 0, s->stream, a);
+    }
+    VG_HIP(hipGetLastError());
+    VG_HIP(hipMemcpyAsync(s->h_total, s->d_total, vgp::kMaxLevels * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+    drain.armed = false;
+    VG_HIP(hipStreamSynchronize(s->stream));
+    for (int i = 0; i < s->levels; i++) s->m[i] = s->h_total.get()[i];
+    s->has_base = true;
+    return VG_OK;
+}
+
+int vg_photometric_set_targets(vg_photometric *s, int64_t n, const uint8_t *imgs)
+{
+    if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "photometric handle is NULL");
+    if (n < 1 || n > kMaxItems) return fail(VG_ERR_INVALID_ARGUMENT, "the target count must be in [1, 65535]");
+    if (!imgs) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    VG_HIP(hipSetDevice(s->device));
+    s->n_targets = 0;
+    if (n > s->cap_targets) {
+        s->cap_targets = 0;
+        if (s->d_targets.alloc((size_t)(n * s->off[s->levels]) * sizeof(float)) != hipSuccess)
+            return fail(VG_ERR_ALLOC, "device allocation of the target pyramids failed");
+        s->cap_targets = n;
+    }
+    vgi::StreamDrain drain{s->stream};
+    if (const int rc = build_pyramids(s, n, imgs, s->d_targets)) return rc;
+    drain.armed = false;
+    VG_HIP(hipStreamSynchronize(s->stream));
+    s->n_targets = n;
+    return VG_OK;
+}
+
+int vg_photometric_level(vg_photometric *s, int64_t target, int scale_idx, float *img, float *grad_u, float *grad_v)
+{
+    if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "photometric handle is NULL");
+    if (scale_idx < 0 || scale_idx >= s->levels) return fail(VG_ERR_INVALID_ARGUMENT, "scale index out of range");
+    if (target < 0 ? !s->has_base : target >= s->n_targets) return fail(VG_ERR_INVALID_ARGUMENT, "no such pyramid: set_base / set_targets first");
+    VG_HIP(hipSetDevice(s->device));
+    const int64_t total = s->off[s->levels], P = level_pixels(s, scale_idx);
+    const size_t bytes = (size_t)P * sizeof(float);
+    const float *src = (target < 0 ? s->d_base.get() : s->d_targets.get() + target * total) + s->off[scale_idx];
+    vgi::StreamDrain drain{s->stream};
+    if (img) VG_HIP(hipMemcpyAsync(img, src, bytes, hipMemcpyDeviceToDevice, s->stream));
+    if (grad_u || grad_v) {
+        const float *gu = nullptr, *gv = nullptr;
+        if (target < 0) {
+            gu = s->d_base.get() + total + s->off[scale_idx];
+            gv = s->d_base.get() + 2 * total + s->off[scale_idx];
+        } else {   // a target keeps no gradients (scaleSpace2 has none): made here, for the caller
+            if (!s->d_grad.get() && s->d_grad.alloc((size_t)(2 * level_pixels(s, 0)) * sizeof(float)) != hipSuccess)
+                return fail(VG_ERR_ALLOC, "device allocation of the gradient scratch failed");
+            hipLaunchKernelGGL(vgp::photo_sobel_kernel, dim3(blocks_of(P, vgp::kLanes), 1), dim3(vgp::kLanes), 0, s->stream, src, s->d_grad.get(),
+                               s->d_grad.get() + P, (int64_t)0, s->w[scale_idx], s->h[scale_idx]);
+            VG_HIP(hipGetLastError());
+            gu = s->d_grad.get();
+            gv = s->d_grad.get() + P;
+        }
+        if (grad_u) VG_HIP(hipMemcpyAsync(grad_u, gu, bytes, hipMemcpyDeviceToDevice, s->stream));
+        if (grad_v) VG_HIP(hipMemcpyAsync(grad_v, gv, bytes, hipMemcpyDeviceToDevice, s->stream));
+    }
+    drain.armed = false;
+    VG_HIP(hipStreamSynchronize(s->stream));
+    return VG_OK;
+}
+
+int vg_photometric_pack(vg_photometric *s, int scale_idx, int64_t *count, int32_t *indices, double *values, double *cloud)
+{
+    if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "photometric handle is NULL");
+    if (!s->has_base) return fail(VG_ERR_INVALID_ARGUMENT, "no key frame: call vg_photometric_set_base first");
+    if (scale_idx < 0 || scale_idx >= s->levels) return fail(VG_ERR_INVALID_ARGUMENT, "scale index out of range");
+    const int64_t m = s->m[scale_idx], o = s->off[scale_idx];
+    if (count) *count = m;
+    if (m == 0 || (!indices && !values && !cloud)) return VG_OK;
+    VG_HIP(hipSetDevice(s->device));
+    vgi::StreamDrain drain{s->stream};
+    if (indices) VG_HIP(hipMemcpyAsync(indices, s->d_idx.get() + o, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToDevice, s->stream));
+    if (values) VG_HIP(hipMemcpyAsync(values, s->d_val.get() + o, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+    if (cloud) VG_HIP(hipMemcpyAsync(cloud, s->d_cloud.get() + 3 * o, (size_t)(3 * m) * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+    drain.armed = false;
+    VG_HIP(hipStreamSynchronize(s->stream));
+    return VG_OK;
+}
+
+int vg_photometric_evaluate(vg_photometric *s, int scale_idx, int64_t n, const double *xi, const int32_t *target, double *residuals,
+                            double *jacobians, double *cost, double *jtj, double *jtr)
+{
+    if (const int rc = check_poses(s, n, xi, target)) return rc;
+    if (scale_idx < 0 || scale_idx >= s->levels) return fail(VG_ERR_INVALID_ARGUMENT, "scale index out of range");
+    VG_HIP(hipSetDevice(s->device));
+    if (const int rc = ensure_poses(s, n)) return rc;
+    for (int64_t k = 0; k < n; k++) make_frame(s, xi + 6 * k, target[k], true, s->h_frames.get()[k]);
+    const bool sums = cost || jtj || jtr;
+    if (const int rc = run_cost(s, scale_idx, n, residuals, jacobians, sums)) return rc;
+    for (int64_t k = 0; sums && k < n; k++) {
+        const double *G = s->h_sums.get() + k * vgp::kSums;
+        if (jtj) std::memcpy(jtj + 21 * k, G, 21 * sizeof(double));
+        if (jtr) std::memcpy(jtr + 6 * k, G + 21, 6 * sizeof(double));
+        if (cost) cost[k] = G[27];
+    }
+    return VG_OK;
+}
+
+int vg_photometric_compute_pose(vg_photometric *s, int64_t n, const double *xi_start, const int32_t *target, const double *xi_prior, double *xi_out,
+                                double *report)
+{
+    if (const int rc = check_poses(s, n, xi_start, target)) return rc;
+    if (!xi_out) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (xi_prior && !vgsh::finite_n(xi_prior, 6 * (int)n)) return fail(VG_ERR_INVALID_ARGUMENT, "the priors must be finite");
+    VG_HIP(hipSetDevice(s->device));
+    if (const int rc = ensure_poses(s, n)) return rc;
+    std::vector<LmPose> P((size_t)n);
+    std::vector<MotionPrior> prior;
+    for (int64_t k = 0; k < n; k++) {
+        std::memcpy(P[k].x, xi_start + 6 * k, sizeof(double) * 6);
+        if (xi_prior) prior.push_back(make_prior(xi_prior + 6 * k));
+    }
+    for (int scale = s->levels - 1; scale >= 0; scale--) {
+        for (int64_t k = 0; k < n; k++) {
+            const double x[6] = {P[k].x[0], P[k].x[1], P[k].x[2], P[k].x[3], P[k].x[4], P[k].x[5]};
+            P[k] = LmPose();
+            std::memcpy(P[k].x, x, sizeof x);
+            make_frame(s, P[k].x, target[k], true, s->h_frames.get()[k]);
+        }
+        if (const int rc = run_cost(s, scale, n, nullptr, nullptr, true)) return rc;
+        for (int64_t k = 0; k < n; k++) {
+            std::memcpy(P[k].G, s->h_sums.get() + k * vgp::kSums, sizeof P[k].G);
+            if (xi_prior) add_prior(prior[k], P[k].x, P[k].G);
+            P[k].cost = P[k].G[27];
+            if (report) report[(k * s->levels + scale) * 4 + 1] = P[k].cost;
+        }
+        for (;;) {
+            bool any = false, launch = false;
+            for (int64_t k = 0; k < n; k++) {
+                if (!P[k].done) {
+                    lm_step(P[k]);
+                    any = true;
+                }
+                const bool active = !P[k].done && P[k].step_ok;   // a pose that has converged is masked
+                make_frame(s, active ? P[k].xc : P[k].x, target[k], active, s->h_frames.get()[k]);
+                launch = launch || active;
+            }
+            if (!any) break;
+            if (launch)
+                if (const int rc = run_cost(s, scale, n, nullptr, nullptr, true)) return rc;
+            for (int64_t k = 0; k < n; k++) {
+                if (P[k].done) continue;
+                double Gc[vgp::kSums] = {0.};
+                if (P[k].step_ok) {
+                    std::memcpy(Gc, s->h_sums.get() + k * vgp::kSums, sizeof Gc);
+                    if (xi_prior) add_prior(prior[k], P[k].xc, Gc);
+                }
+                lm_accept(P[k], Gc);
+            }
+        }
+        for (int64_t k = 0; report && k < n; k++) {
+            double *r = report + (k * s->levels + scale) * 4;
+            r[0] = P[k].iterations;
+            r[2] = P[k].cost;
+            r[3] = P[k].term;
+        }
+    }
+    for (int64_t k = 0; k < n; k++) std::memcpy(xi_out + 6 * k, P[k].x, sizeof(double) * 6);
+    return VG_OK;
+}
+
+}  // extern "C"

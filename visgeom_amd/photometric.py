@@ -1,0 +1,185 @@
+"""Photometric pose estimation against a depth key frame on the GPU (include/visgeom_amd.h section 12): the reference's
+ScalePhotometric::computePose -- a binary image pyramid with gradients, the data pack of the key frame's salient pixels with
+a depth, the photometric cost with its Jacobian, and a coarse-to-fine trust-region solve.  Thin torch wrapper over a
+vg_photometric handle; library errors raise capi.VisgeomError, argument errors ValueError before the library is called."""
+import ctypes
+
+import numpy as np
+
+from . import capi
+from . import stereo as _stereo
+
+_dp = ctypes.POINTER(ctypes.c_double)
+_i32p = ctypes.POINTER(ctypes.c_int32)
+REPORT = ("iterations", "initial_cost", "final_cost", "termination")
+
+
+class Photometric:
+    """A vg_photometric handle on one device: one EUCM camera, the depth map geometry of `params` (a vg_stereo_params or
+    vg_motion_stereo_params; only the scale fields are read), xi_base_cam, the image size and num_scales pyramid levels.
+    Images are uint8 CUDA tensors [height, width] (targets: [n, height, width]), the depth map a float64 CUDA tensor [y_max,
+    x_max].  The handle's stream is torch's current stream of the device at creation; each call first makes it wait for the
+    caller's current stream (where the inputs were produced and the outputs are allocated) and is complete when it returns."""
+
+    def __init__(self, eucm, params, xi_base_cam, width, height, num_scales=5, device=0):
+        import torch
+
+        self._c = _stereo._vec(eucm, 6, "eucm")
+        self._xbc = _stereo._vec(xi_base_cam, 6, "xi_base_cam")
+        self.device = torch.device("cuda", device)
+        self.params = params.stereo if isinstance(params, capi.MotionStereoParams) else params
+        if not isinstance(self.params, capi.StereoParams):
+            raise ValueError("params must be a vg_stereo_params or a vg_motion_stereo_params")
+        self.width, self.height, self.num_scales = int(width), int(height), int(num_scales)
+        self.n_targets = 0
+        L = capi.load()
+        h = ctypes.c_void_p()
+        self._stream = torch.cuda.current_stream(self.device)
+        capi.check(L.vg_photometric_create(ctypes.byref(h), self.device.index, ctypes.c_void_p(self._stream.cuda_stream),
+                                           self._c.ctypes.data_as(_dp), ctypes.byref(self.params), self._xbc.ctypes.data_as(_dp),
+                                           self.width, self.height, self.num_scales))
+        self._h = h
+        self.sizes = []   # (width, height) per level
+        for i in range(self.num_scales):
+            w, hh = ctypes.c_int(), ctypes.c_int()
+            capi.check(L.vg_photometric_level_size(h, i, ctypes.byref(w), ctypes.byref(hh)))
+            self.sizes.append((w.value, hh.value))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            capi.load().vg_photometric_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _enter(self):
+        import torch
+
+        cur = torch.cuda.current_stream(self.device)
+        if cur != self._stream:
+            self._stream.wait_stream(cur)
+
+    def _leave(self, *tensors):
+        import torch
+
+        if torch.cuda.current_stream(self.device) != self._stream:
+            for t in tensors:
+                if t is not None:
+                    t.record_stream(self._stream)
+        return tensors[0] if len(tensors) == 1 else tensors
+
+    def _image(self, img, what):
+        import torch
+
+        if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.uint8 or tuple(img.shape[-2:]) != (self.height, self.width):
+            raise ValueError("%s must be a uint8 CUDA tensor [..., %d, %d]" % (what, self.height, self.width))
+        return img.contiguous()
+
+    def set_base(self, img, depth):
+        """the key frame: its image and its depth map; builds the pyramid with gradients and the data pack of every scale"""
+        import torch
+
+        img = self._image(img, "img")
+        if img.dim() != 2:
+            raise ValueError("img must be [height, width]")
+        if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dtype != torch.float64 or depth.dim() != 2:
+            raise ValueError("depth must be a float64 CUDA tensor [y_max, x_max]")
+        p = self.params
+        x_max = (p.u_max - 2 * p.u0) // p.scale + 1 if p.equal_margins else p.x_max
+        y_max = (p.v_max - 2 * p.v0) // p.scale + 1 if p.equal_margins else p.y_max
+        if tuple(depth.shape) != (y_max, x_max):
+            raise ValueError("depth must be [y_max, x_max] = [%d, %d]" % (y_max, x_max))
+        depth = depth.contiguous()
+        self._enter()
+        capi.check(capi.load().vg_photometric_set_base(self._h, img.data_ptr(), depth.data_ptr()))
+        self._leave(img, depth)
+
+    def set_targets(self, imgs):
+        """the images the poses are estimated for: [n, height, width] or one [height, width]"""
+        imgs = self._image(imgs, "imgs")
+        imgs = imgs[None] if imgs.dim() == 2 else imgs
+        if imgs.dim() != 3:
+            raise ValueError("imgs must be [n, height, width]")
+        self._enter()
+        capi.check(capi.load().vg_photometric_set_targets(self._h, imgs.shape[0], imgs.data_ptr()))
+        self.n_targets = imgs.shape[0]
+        self._leave(imgs)
+
+    def level(self, scale_idx, target=None):
+        """(img, grad_u, grad_v) float32 [rows, cols] of one pyramid level: the key frame's, or target image `target`'s"""
+        import torch
+
+        if not 0 <= scale_idx < self.num_scales:
+            raise ValueError("scale index out of range")
+        w, h = self.sizes[scale_idx]
+        out = [torch.empty((h, w), dtype=torch.float32, device=self.device) for _ in range(3)]
+        self._enter()
+        capi.check(capi.load().vg_photometric_level(self._h, -1 if target is None else int(target), scale_idx, *[t.data_ptr() for t in out]))
+        return self._leave(*out)
+
+    def pack(self, scale_idx):
+        """the data pack of a scale: (indices int32 [m], values float64 [m], cloud float64 [m, 3])"""
+        import torch
+
+        L = capi.load()
+        m = ctypes.c_int64()
+        capi.check(L.vg_photometric_pack(self._h, scale_idx, ctypes.byref(m), None, None, None))
+        idx = torch.empty((m.value,), dtype=torch.int32, device=self.device)
+        val = torch.empty((m.value,), dtype=torch.float64, device=self.device)
+        cloud = torch.empty((m.value, 3), dtype=torch.float64, device=self.device)
+        self._enter()
+        capi.check(L.vg_photometric_pack(self._h, scale_idx, ctypes.byref(m), idx.data_ptr(), val.data_ptr(), cloud.data_ptr()))
+        return self._leave(idx, val, cloud)
+
+    def _poses(self, xi, target):
+        xi = np.ascontiguousarray(xi, dtype=np.float64).reshape(-1, 6)
+        tg = np.zeros(xi.shape[0], dtype=np.int32) if target is None else np.ascontiguousarray(target, dtype=np.int32).reshape(-1)
+        if tg.shape[0] != xi.shape[0]:
+            raise ValueError("%d poses but %d target indices" % (xi.shape[0], tg.shape[0]))
+        return xi, tg
+
+    def evaluate(self, scale_idx, xi, target=None, rows=True):
+        """PhotometricCostFunction::Evaluate of the poses xi [n, 6] against target[k] (default: target 0) at one scale: a dict
+        with cost [n], jtj [n, 21] (upper triangle, row-major), jtr [n, 6] (numpy) and, with rows, residuals [n, m] and
+        jacobians [n, m, 6] (CUDA tensors)"""
+        import torch
+
+        xi, tg = self._poses(xi, target)
+        n = xi.shape[0]
+        L = capi.load()
+        res = jac = None
+        if rows:
+            m = ctypes.c_int64()
+            capi.check(L.vg_photometric_pack(self._h, scale_idx, ctypes.byref(m), None, None, None))
+            res = torch.zeros((n, m.value), dtype=torch.float64, device=self.device)
+            jac = torch.zeros((n, m.value, 6), dtype=torch.float64, device=self.device)
+        cost, jtj, jtr = np.zeros(n), np.zeros((n, 21)), np.zeros((n, 6))
+        self._enter()
+        capi.check(L.vg_photometric_evaluate(self._h, scale_idx, n, xi.ctypes.data_as(_dp), tg.ctypes.data_as(_i32p),
+                                             res.data_ptr() if rows else None, jac.data_ptr() if rows else None,
+                                             cost.ctypes.data_as(_dp), jtj.ctypes.data_as(_dp), jtr.ctypes.data_as(_dp)))
+        self._leave(res, jac)
+        return {"cost": cost, "jtj": jtj, "jtr": jtr, "residuals": res, "jacobians": jac}
+
+    def compute_pose(self, xi_start, target=None, xi_prior=None):
+        """computePose from the start poses xi_start [n, 6] (or one [6]) against target[k]: (poses, report); report is
+        float64 [n, num_scales, 4]: REPORT per scale.  xi_prior ([n, 6]): the motion prior's pose per start pose (the
+        reference passes the start pose itself); None switches the prior off."""
+        single = np.ndim(xi_start) == 1
+        xi, tg = self._poses(xi_start, target)
+        n = xi.shape[0]
+        prior = None
+        if xi_prior is not None:
+            prior = np.ascontiguousarray(xi_prior, dtype=np.float64).reshape(-1, 6)
+            if prior.shape[0] != n:
+                raise ValueError("%d poses but %d priors" % (n, prior.shape[0]))
+        out, report = np.zeros((n, 6)), np.zeros((n, self.num_scales, 4))
+        self._enter()
+        capi.check(capi.load().vg_photometric_compute_pose(self._h, n, xi.ctypes.data_as(_dp), tg.ctypes.data_as(_i32p),
+                                                           prior.ctypes.data_as(_dp) if prior is not None else None,
+                                                           out.ctypes.data_as(_dp), report.ctypes.data_as(_dp)))
+        return (out[0], report[0]) if single else (out, report)
