@@ -802,6 +802,52 @@ int vg_photometric_evaluate(vg_photometric *h, int scale_idx, int64_t n, const d
 int vg_photometric_compute_pose(vg_photometric *h, int64_t n, const double *xi_start, const int32_t *target, const double *xi_prior,
                                 double *xi_out, double *report);
 
+/* ---- 12, continued: mutual-information localization, the reference's ScalePhotometric::computePoseMI
+ * (src/localization/photometric.cpp:159-189, 260-385) on the MutualInformation / MutualInformationOdom cost
+ * (src/localization/cost_function_mi.cpp) -- re-localization against a key frame whose image comes from another pass, with
+ * another exposure and lighting, where the squared grey difference of computePose is not meant to work.  The cost is the
+ * negative mutual information -sum p12 log(p12 / (p1 p2)) of a soft joint histogram of the key frame's grey values and the
+ * target's samples, at the settings of computePoseMI below.  Same handle, same packs, pyramids and pose conventions as above;
+ * the entries carry the prefix of their options struct, vg_mi_, and take the vg_photometric handle.
+ * Deviations: DESIGN.md section 9, "Mutual-information localization". */
+#define VG_MI_NUM_BINS 8                 /* numBins; the joint histogram is row-major [second image's bin][key frame's bin] */
+#define VG_MI_VALUE_MAX 255.0            /* valMax; the bin width is 255 / 7 */
+#define VG_MI_FUNCTION_TOLERANCE 1e-2    /* GradientProblemSolver::Options of computePoseMI */
+#define VG_MI_GRADIENT_TOLERANCE 1e-3
+#define VG_MI_MAX_ITERATIONS 50          /* Ceres' default */
+#define VG_MI_ODOMETRY_DAMPING 0.0002    /* DAMPING of MutualInformationOdom::Evaluate */
+typedef struct vg_mi_options {
+    double function_tolerance; /* |f - f_previous| <= function_tolerance * |f_previous| ends a scale; 0: 1e-2 */
+    double gradient_tolerance; /* max |gradient| <= gradient_tolerance ends a scale; 0: 1e-3 */
+    int max_iterations;        /* per scale; 0: 50 */
+} vg_mi_options;
+/* MutualInformation::Evaluate of n poses at one scale: xi HOST [n][6], target HOST int32 [n].  With m the pack's count: values
+ * (valVec2, DEVICE [n][m]) the target's grey at every point, hist (HOST [n][64]) the joint histogram, cost (HOST [n]) and
+ * gradient (HOST [n][6]).  Any output may be NULL; without a gradient its two launches are skipped and the other outputs keep
+ * their bits.  There is no margin: a point that projects is sampled wherever it lands, through the interpolator's clamping
+ * grid; a point that does not project has the value 0, is still counted (in bin 0 of the second axis) and has no gradient.
+ * All sums are FP64 in a fixed order: bit-identical from run to run and in every batch.  Refused with
+ * VG_ERR_INVALID_ARGUMENT before HIP is touched: no key frame or no targets, a scale or target index out of range, a pose that
+ * is not finite (the reference's Evaluate returns false), a scale whose pack is empty (the increment would be 1 / 0). */
+int vg_mi_evaluate(vg_photometric *h, int scale_idx, int64_t n, const double *xi, const int32_t *target, double *values,
+                   double *hist, double *cost, double *gradient);
+/* computePoseMI of n start poses (HOST [n][6]) against target[k] each, from the coarsest scale to the finest; a scale whose
+ * pack is empty is skipped (0 iterations in its report), and the call is refused when every pack is.  In place of Ceres'
+ * GradientProblemSolver (BFGS) a BFGS of this library's own: inverse Hessian from the identity, first step length
+ * min(1, 1 / max|g|), a strong-Wolfe line search (c1 1e-4, c2 0.9, bracketing and zoom with cubic interpolation, at most 20
+ * evaluations), no update when s^T y <= 0; a scale ends on the function tolerance, the gradient tolerance, max_iterations
+ * (VG_TERM_NO_CONVERGENCE) or a failed line search (VG_TERM_FAILURE).  All poses advance in the same launches, a finished
+ * pose is masked; a trial pose that is not finite counts as a failed trial.  options NULL or zero fields: the reference's.
+ * xi_odom (HOST [n][6], or NULL) selects MutualInformationOdom(xiOdom = xi_odom[k], xiPrior = xi_start[k], errV 0.1, errW
+ * 0.01, lambdaT = lambdaR 0.01): VG_MI_ODOMETRY_DAMPING err (C / 2) err^T is added to the cost and DAMPING err J to the
+ * gradient, err = xiPrior^-1 o xi, in host arithmetic.  xi_out HOST [n][6]; report (HOST [n][num_scales][4], may be NULL):
+ * iterations, initial cost, final cost, vg_termination per scale. */
+int vg_mi_compute_pose(vg_photometric *h, int64_t n, const double *xi_start, const int32_t *target, const double *xi_odom,
+                       const vg_mi_options *options, double *xi_out, double *report);
+/* Host only: the odometry term of MutualInformationOdom alone, as compute_pose_mi adds it -- *cost = DAMPING err (C / 2) err^T,
+ * gradient (HOST [6], may be NULL) = DAMPING err J, for the pose xi (all HOST [6]). */
+int vg_mi_odometry(const double *xi_odom, const double *xi_prior, const double *xi, double *cost, double *gradient);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",
  * "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop", "solver_no_fold_frames",

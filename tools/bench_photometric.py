@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One-GPU measurement of photometric localization (include/visgeom_amd.h section 12; visgeom_amd/csrc/vg_photometric.hpp):
 time per call of set_base, set_targets, one evaluate (sums only) at the finest scale and one compute_pose from HIP events,
-next to the motion stereo refine call on the same maps in the same run.  tools only -- bench.py stays the driver's contract.
+the same for the mutual-information cost (evaluate_mi with its gradient, compute_pose_mi), next to the motion stereo refine
+call on the same maps in the same run.  tools only -- bench.py stays the driver's contract.
 
 Case: the reference's example geometry (ex_epipolar_stereo.json: 1280 x 800 images, margins 50: 1181 x 701 depth pixels), 5
 scales, n in {1, 8} poses, each against its own target image.  The depth map is the SGM map of the first pair; the targets
@@ -9,7 +10,8 @@ are the second view, the start poses its pose moved by up to 1 cm and 0.2 degree
 
 Algorithmic bytes: set_base reads 1 + 8 bytes per pixel (image, depth) and writes 12 per pyramid pixel (level, two gradients)
 plus 36 per pack point; set_targets reads 1 and writes 4 per pyramid pixel (1.33 x the image); evaluate reads 32 per pack
-point and pose (value, cloud) and 16 target samples of 4 bytes, mostly from cache.
+point and pose (value, cloud) and 16 target samples of 4 bytes, mostly from cache; evaluate_mi reads the same twice (the
+gradient pass samples again) and writes 560 bytes of partial sums per 256 points.
 
 usage: python tools/bench_photometric.py [reps]     (one JSON line per case)
 """
@@ -77,6 +79,9 @@ def main():
         t_eval = timed(lambda: h.evaluate(0, starts, idx, rows=False), h._stream)
         t_pose = timed(lambda: h.compute_pose(starts, idx), h._stream)
         poses, report = h.compute_pose(starts, idx)
+        t_eval_mi = timed(lambda: h.evaluate_mi(0, starts, idx, values=False), h._stream)
+        t_pose_mi = timed(lambda: h.compute_pose_mi(starts, idx), h._stream)
+        poses_mi, report_mi = h.compute_pose_mi(starts, idx)
         h.close()
 
         def ms(t):
@@ -85,6 +90,9 @@ def main():
         rec = {"workload": "photometric", "width": p.u_max, "height": p.v_max, "x_max": int(sgm[0].shape[-1]), "y_max": int(sgm[0].shape[-2]),
                "scales": NUM_SCALES, "poses": n, "pack_points": points, "set_base": ms(t_base), "set_targets": ms(t_targets),
                "evaluate_finest": ms(t_eval), "compute_pose": ms(t_pose),
+               "evaluate_mi_finest": ms(t_eval_mi), "compute_pose_mi": ms(t_pose_mi),
+               "mi_iterations_per_scale": report_mi[:, :, 0].mean(axis=0).tolist(), "mi_final_cost_finest": report_mi[:, 0, 2].tolist(),
+               "mi_pose_moved_m": float(np.linalg.norm(poses_mi[:, :3] - np.array(xi[:3]), axis=1).max()),
                "iterations_per_scale": report[:, :, 0].mean(axis=0).tolist(), "final_cost_finest": report[:, 0, 2].tolist(),
                "pose_moved_m": float(np.linalg.norm(poses[:, :3] - np.array(xi[:3]), axis=1).max()),
                "motion_stereo_refine_ms_same_run": t_refine[0] * 1e3, "compute_pose_ratio_to_refine": t_pose[0] / t_refine[0],

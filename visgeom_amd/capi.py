@@ -227,6 +227,9 @@ SIGNATURES = {
     "vg_photometric_pack": (ctypes.c_int, [_vp, ctypes.c_int, _i64p, _vp, _vp, _vp]),
     "vg_photometric_evaluate": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _dp, _i32p, _vp, _vp, _dp, _dp, _dp]),
     "vg_photometric_compute_pose": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _i32p, _dp, _dp, _dp]),
+    "vg_mi_evaluate": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _dp, _i32p, _vp, _dp, _dp, _dp]),
+    "vg_mi_compute_pose": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _i32p, _dp, _vp, _dp, _dp]),
+    "vg_mi_odometry": (ctypes.c_int, [_dp, _dp, _dp, _dp, _dp]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),
@@ -248,6 +251,15 @@ class StereoParams(ctypes.Structure):
 class MotionStereoParams(ctypes.Structure):
     """struct vg_motion_stereo_params"""
     _fields_ = [("stereo", StereoParams), ("gradient_thresh", ctypes.c_int)]
+
+
+class MiOptions(ctypes.Structure):
+    """struct vg_mi_options; a zero field means the reference's value (MI_DEFAULTS)"""
+    _fields_ = [("function_tolerance", ctypes.c_double), ("gradient_tolerance", ctypes.c_double), ("max_iterations", ctypes.c_int)]
+
+
+MI_NUM_BINS, MI_VALUE_MAX, MI_ODOMETRY_DAMPING = 8, 255., 0.0002
+MI_DEFAULTS = {"function_tolerance": 1e-2, "gradient_tolerance": 1e-3, "max_iterations": 50}
 
 
 class VisgeomError(RuntimeError):

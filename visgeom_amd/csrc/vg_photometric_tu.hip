@@ -6,6 +6,8 @@
 // the target pyramids, and the staging of a cost evaluation: the per-pose frames and the 28 sums per pose in pinned memory.
 // compute_pose drives the trust-region loop from the host: per iteration one upload of the candidate frames, the cost and the
 // reduce launch over all poses that still move, and one download of 28 doubles per pose.
+// evaluate_mi / compute_pose_mi are the mutual-information cost and its quasi-Newton solve on the same handle: four launches per
+// evaluation and one download of 72 doubles per pose (vg_photometric_mi.hpp).
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -16,6 +18,7 @@
 #include "vg_internal.hpp"
 #include "vg_local.hpp"
 #include "vg_photometric.hpp"
+#include "vg_photometric_mi.hpp"
 #include "vg_stereo_host.hpp"
 #include "vg_transf_host.hpp"
 
@@ -38,6 +41,11 @@ struct vg_photometric {
     vgi::PinnedMem<vgp::PoseFrame> h_frames;
     vgi::DeviceMem<double> d_partials, d_sums;
     vgi::PinnedMem<double> h_sums;
+    // the mutual-information cost: _hist1 per scale, and the staging of an evaluation
+    int64_t cap_mi_poses = 0, cap_mi_partials = 0;
+    vgi::DeviceMem<double> d_hist1, d_hist1_partials;   // [kMaxLevels][8]; [workgroups of level 0][8]
+    vgi::DeviceMem<double> d_mi_hist, d_mi_grad, d_mi_log, d_mi_out;   // [n][blocks][64], [n][blocks][6], [n][64], [n][kMiOut]
+    vgi::PinnedMem<double> h_mi_out;
 };
 
 namespace {
@@ -322,6 +330,91 @@ void lm_accept(LmPose &p, const double *Gc)
     if (p.iterations >= kMaxIterations) p.done = true;
 }
 
+// ---- mutual information ------------------------------------------------------------------------------------------------
+
+int ensure_mi(vg_photometric *s, int64_t n, unsigned blocks)
+{
+    if (n > s->cap_mi_poses) {
+        s->cap_mi_poses = 0;
+        if (s->d_mi_log.alloc((size_t)n * vgp::kMiCells * sizeof(double)) != hipSuccess || s->d_mi_out.alloc((size_t)n * vgp::kMiOut * sizeof(double)) != hipSuccess)
+            return fail(VG_ERR_ALLOC, "device allocation of the mutual-information results failed");
+        if (s->h_mi_out.alloc((size_t)n * vgp::kMiOut * sizeof(double), hipHostMallocDefault) != hipSuccess)
+            return fail(VG_ERR_ALLOC, "pinned allocation of the mutual-information staging failed");
+        s->cap_mi_poses = n;
+    }
+    if (n * blocks > s->cap_mi_partials) {
+        s->cap_mi_partials = 0;
+        if (s->d_mi_hist.alloc((size_t)(n * blocks) * vgp::kMiCells * sizeof(double)) != hipSuccess ||
+            s->d_mi_grad.alloc((size_t)(n * blocks) * 6 * sizeof(double)) != hipSuccess)
+            return fail(VG_ERR_ALLOC, "device allocation of the mutual-information partial sums failed");
+        s->cap_mi_partials = n * blocks;
+    }
+    return VG_OK;
+}
+
+// MutualInformation::Evaluate of the n frames in h_frames at one scale (its pack is not empty): valVec2 to values (DEVICE, may
+// be NULL), hist12 | cost | gradient of every active pose to h_mi_out; the gradient launches only with `grad`.  Synchronous.
+int run_mi(vg_photometric *s, int scale, int64_t n, double *values, bool grad)
+{
+    const int64_t m = s->m[scale];
+    const unsigned blocks = blocks_of(m, vgp::kLanes);
+    if (const int rc = ensure_mi(s, n, blocks)) return rc;
+    vgi::StreamDrain drain{s->stream};
+    VG_HIP(hipMemcpyAsync(s->d_frames, s->h_frames, (size_t)n * sizeof(vgp::PoseFrame), hipMemcpyHostToDevice, s->stream));
+    vgp::MiArgs a;
+    a.frames = s->d_frames;
+    a.targets = s->d_targets;
+    a.target_stride = s->off[s->levels];
+    a.level_off = s->off[scale];
+    a.w = s->w[scale];
+    a.h = s->h[scale];
+    a.inv_scale = 1. / (double)(1 << scale);
+    for (int i = 0; i < 6; i++) a.cam[i] = s->cam[i];
+    a.val = s->d_val.get() + s->off[scale];
+    a.cloud = s->d_cloud.get() + 3 * s->off[scale];
+    a.hist1 = s->d_hist1.get() + vgp::kMiBins * scale;
+    a.m = (int)m;
+    a.blocks = (int)blocks;
+    a.increment = 1. / (double)m;
+    a.values = values;
+    a.hist_partials = s->d_mi_hist;
+    a.grad_partials = s->d_mi_grad;
+    a.logv = s->d_mi_log;
+    a.out = s->d_mi_out;
+    hipLaunchKernelGGL(vgp::mi_hist_kernel, dim3(blocks, (unsigned)n), dim3(vgp::kLanes), 0, s->stream, a);
+    hipLaunchKernelGGL(vgp::mi_finish_kernel, dim3((unsigned)n), dim3(64), 0, s->stream, a);
+    if (grad) {
+        hipLaunchKernelGGL(vgp::mi_grad_kernel, dim3(blocks, (unsigned)n), dim3(vgp::kLanes), 0, s->stream, a);
+        hipLaunchKernelGGL(vgp::mi_grad_reduce_kernel, dim3((unsigned)n), dim3(64), 0, s->stream, a);
+    }
+    VG_HIP(hipGetLastError());
+    VG_HIP(hipMemcpyAsync(s->h_mi_out, s->d_mi_out, (size_t)n * vgp::kMiOut * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    drain.armed = false;
+    VG_HIP(hipStreamSynchronize(s->stream));
+    return VG_OK;
+}
+
+// MutualInformationOdom's constructor for xiOdom and xiPrior
+vgp::MiOdometry make_mi_odometry(const double *xi_odom, const double *xi_prior)
+{
+    double R[9], M[9];
+    const vg::RotTrig rt = vg::rot_trig(xi_prior + 3, true, true);
+    vg::rotation_matrix(xi_prior + 3, -1., rt, R);
+    vg::inter_omega_rot(xi_prior + 3, rt, M);
+    vgp::MiOdometry o;
+    vgp::mi_odometry_init(o, xi_odom, xi_prior, R, M);
+    return o;
+}
+
+void add_mi_odometry(const vgp::MiOdometry &o, const double *x, double *cost, double *gradient)
+{
+    Array6d a, p;
+    std::memcpy(a.data(), x, sizeof(double) * 6);
+    std::memcpy(p.data(), o.prior, sizeof(double) * 6);
+    const Array6d err = vgth::inverse_compose(p, a);
+    vgp::mi_odometry_add(o, err.data(), cost, gradient);
+}
+
 }  // namespace
 
 extern "C" {
@@ -412,7 +505,9 @@ int vg_photometric_set_base(vg_photometric *s, const uint8_t *img, const double 
         if (s->d_base.alloc((size_t)(3 * total) * sizeof(float)) != hipSuccess || s->d_idx.alloc((size_t)total * sizeof(int32_t)) != hipSuccess ||
             s->d_val.alloc((size_t)total * sizeof(double)) != hipSuccess || s->d_cloud.alloc((size_t)(3 * total) * sizeof(double)) != hipSuccess ||
             s->d_counts.alloc((size_t)nb * sizeof(unsigned)) != hipSuccess || s->d_offsets.alloc((size_t)nb * sizeof(unsigned)) != hipSuccess ||
-            s->d_total.alloc(vgp::kMaxLevels * sizeof(unsigned)) != hipSuccess)
+            s->d_total.alloc(vgp::kMaxLevels * sizeof(unsigned)) != hipSuccess ||
+            s->d_hist1.alloc(vgp::kMaxLevels * vgp::kMiBins * sizeof(double)) != hipSuccess ||
+            s->d_hist1_partials.alloc((size_t)nb * vgp::kMiBins * sizeof(double)) != hipSuccess)
             return fail(VG_ERR_ALLOC, "device allocation of the key frame's pyramid and data packs failed");
         if (s->h_total.alloc(vgp::kMaxLevels * sizeof(unsigned), hipHostMallocDefault) != hipSuccess)
             return fail(VG_ERR_ALLOC, "pinned allocation of the pack counts failed");
@@ -446,6 +541,11 @@ int vg_photometric_set_base(vg_photometric *s, const uint8_t *img, const double 
         hipLaunchKernelGGL(vgp::photo_scan_kernel, dim3(1), dim3(vgp::kLanes), 0, s->stream, (const unsigned *)s->d_counts.get(), s->d_offsets.get(),
                            (int)nb, s->d_total.get() + i);
         hipLaunchKernelGGL((vgp::photo_select_kernel<true>), dim3(nb), dim3(vgp::kLanes), 0, s->stream, a);
+        // MutualInformation's _hist1 depends on the pack only
+        hipLaunchKernelGGL(vgp::mi_hist1_kernel, dim3(nb), dim3(vgp::kLanes), 0, s->stream, (const double *)a.val, (const unsigned *)(s->d_total.get() + i),
+                           s->d_hist1_partials.get());
+        hipLaunchKernelGGL(vgp::mi_hist1_reduce_kernel, dim3(1), dim3(64), 0, s->stream, (const double *)s->d_hist1_partials.get(), (int)nb,
+                           s->d_hist1.get() + vgp::kMiBins * i);
     }
     VG_HIP(hipGetLastError());
     VG_HIP(hipMemcpyAsync(s->h_total, s->d_total, vgp::kMaxLevels * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
@@ -607,6 +707,112 @@ int vg_photometric_compute_pose(vg_photometric *s, int64_t n, const double *xi_s
         }
     }
     for (int64_t k = 0; k < n; k++) std::memcpy(xi_out + 6 * k, P[k].x, sizeof(double) * 6);
+    return VG_OK;
+}
+
+int vg_mi_evaluate(vg_photometric *s, int scale_idx, int64_t n, const double *xi, const int32_t *target, double *values, double *hist,
+                   double *cost, double *gradient)
+{
+    if (const int rc = check_poses(s, n, xi, target)) return rc;
+    if (scale_idx < 0 || scale_idx >= s->levels) return fail(VG_ERR_INVALID_ARGUMENT, "scale index out of range");
+    if (s->m[scale_idx] == 0) return fail(VG_ERR_INVALID_ARGUMENT, "the data pack of this scale is empty: the histogram increment would be 1 / 0");
+    VG_HIP(hipSetDevice(s->device));
+    if (const int rc = ensure_poses(s, n)) return rc;
+    for (int64_t k = 0; k < n; k++) make_frame(s, xi + 6 * k, target[k], true, s->h_frames.get()[k]);
+    if (const int rc = run_mi(s, scale_idx, n, values, gradient != nullptr)) return rc;
+    for (int64_t k = 0; k < n; k++) {
+        const double *o = s->h_mi_out.get() + k * vgp::kMiOut;
+        if (hist) std::memcpy(hist + vgp::kMiCells * k, o, vgp::kMiCells * sizeof(double));
+        if (cost) cost[k] = o[vgp::kMiCells];
+        if (gradient) std::memcpy(gradient + 6 * k, o + vgp::kMiCells + 1, 6 * sizeof(double));
+    }
+    return VG_OK;
+}
+
+int vg_mi_odometry(const double *xi_odom, const double *xi_prior, const double *xi, double *cost, double *gradient)
+{
+    if (!xi_odom || !xi_prior || !xi || !cost) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!vgsh::finite_n(xi_odom, 6) || !vgsh::finite_n(xi_prior, 6) || !vgsh::finite_n(xi, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "the poses must be finite");
+    const vgp::MiOdometry o = make_mi_odometry(xi_odom, xi_prior);
+    *cost = 0.;
+    for (int i = 0; gradient && i < 6; i++) gradient[i] = 0.;
+    add_mi_odometry(o, xi, cost, gradient);
+    return VG_OK;
+}
+
+int vg_mi_compute_pose(vg_photometric *s, int64_t n, const double *xi_start, const int32_t *target, const double *xi_odom,
+                       const vg_mi_options *options, double *xi_out, double *report)
+{
+    if (const int rc = check_poses(s, n, xi_start, target)) return rc;
+    if (!xi_out) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (xi_odom && !vgsh::finite_n(xi_odom, 6 * (int)n)) return fail(VG_ERR_INVALID_ARGUMENT, "the odometry poses must be finite");
+    vg_mi_options opt = {0., 0., 0};
+    if (options) opt = *options;
+    if (!(opt.function_tolerance >= 0.) || !(opt.gradient_tolerance >= 0.) || opt.max_iterations < 0)
+        return fail(VG_ERR_INVALID_ARGUMENT, "the tolerances and max_iterations must not be negative");
+    if (opt.function_tolerance == 0.) opt.function_tolerance = VG_MI_FUNCTION_TOLERANCE;
+    if (opt.gradient_tolerance == 0.) opt.gradient_tolerance = VG_MI_GRADIENT_TOLERANCE;
+    if (opt.max_iterations == 0) opt.max_iterations = VG_MI_MAX_ITERATIONS;
+    bool any_points = false;
+    for (int i = 0; i < s->levels; i++) any_points = any_points || s->m[i] > 0;
+    if (!any_points) return fail(VG_ERR_INVALID_ARGUMENT, "the data pack of every scale is empty");
+    VG_HIP(hipSetDevice(s->device));
+    if (const int rc = ensure_poses(s, n)) return rc;
+    std::vector<vgp::MiBfgs> B((size_t)n);
+    std::vector<vgp::MiOdometry> odom;
+    std::vector<char> active((size_t)n);
+    for (int64_t k = 0; k < n; k++) {
+        std::memcpy(B[k].x, xi_start + 6 * k, sizeof(double) * 6);
+        B[k].ftol = opt.function_tolerance;
+        B[k].gtol = opt.gradient_tolerance;
+        B[k].max_iterations = opt.max_iterations;
+        if (xi_odom) odom.push_back(make_mi_odometry(xi_odom + 6 * k, xi_start + 6 * k));   // xiPrior is the start pose
+    }
+    for (int scale = s->levels - 1; scale >= 0; scale--) {
+        if (s->m[scale] == 0) {   // nothing to match at this scale: the pose passes through
+            for (int64_t k = 0; report && k < n; k++) {
+                double *r = report + (k * s->levels + scale) * 4;
+                r[0] = r[1] = r[2] = 0.;
+                r[3] = VG_TERM_NO_CONVERGENCE;
+            }
+            continue;
+        }
+        for (int64_t k = 0; k < n; k++) {
+            const double x[6] = {B[k].x[0], B[k].x[1], B[k].x[2], B[k].x[3], B[k].x[4], B[k].x[5]};
+            B[k].start(x);
+        }
+        for (;;) {
+            bool any = false, launch = false;
+            for (int64_t k = 0; k < n; k++) {
+                active[k] = !B[k].done && B[k].trial_finite();   // a finished pose is masked; so is a trial that is not finite
+                any = any || !B[k].done;
+                launch = launch || active[k];
+                make_frame(s, active[k] ? B[k].trial() : B[k].x, target[k], active[k] != 0, s->h_frames.get()[k]);
+            }
+            if (!any) break;
+            if (launch)
+                if (const int rc = run_mi(s, scale, n, nullptr, true)) return rc;
+            for (int64_t k = 0; k < n; k++) {
+                if (B[k].done) continue;
+                double f = 0., g[6] = {0., 0., 0., 0., 0., 0.};
+                if (active[k]) {
+                    const double *o = s->h_mi_out.get() + k * vgp::kMiOut;
+                    f = o[vgp::kMiCells];
+                    std::memcpy(g, o + vgp::kMiCells + 1, sizeof g);
+                    if (xi_odom) add_mi_odometry(odom[k], B[k].trial(), &f, g);
+                }
+                B[k].consume(f, g, active[k] != 0);
+            }
+        }
+        for (int64_t k = 0; report && k < n; k++) {
+            double *r = report + (k * s->levels + scale) * 4;
+            r[0] = B[k].iterations;
+            r[1] = B[k].initial_cost;
+            r[2] = B[k].f;
+            r[3] = B[k].term;
+        }
+    }
+    for (int64_t k = 0; k < n; k++) std::memcpy(xi_out + 6 * k, B[k].x, sizeof(double) * 6);
     return VG_OK;
 }
 

@@ -1,6 +1,8 @@
 """Photometric pose estimation against a depth key frame on the GPU (include/visgeom_amd.h section 12): the reference's
 ScalePhotometric::computePose -- a binary image pyramid with gradients, the data pack of the key frame's salient pixels with
-a depth, the photometric cost with its Jacobian, and a coarse-to-fine trust-region solve.  Thin torch wrapper over a
+a depth, the photometric cost with its Jacobian, and a coarse-to-fine trust-region solve; and computePoseMI, the same
+localization on the mutual information of the two images' grey values, for a key frame from another pass with other exposure
+and lighting: its cost with histogram and gradient, and a coarse-to-fine BFGS.  Thin torch wrapper over a
 vg_photometric handle; library errors raise capi.VisgeomError, argument errors ValueError before the library is called."""
 import ctypes
 
@@ -183,3 +185,64 @@ class Photometric:
                                                            prior.ctypes.data_as(_dp) if prior is not None else None,
                                                            out.ctypes.data_as(_dp), report.ctypes.data_as(_dp)))
         return (out[0], report[0]) if single else (out, report)
+
+    def evaluate_mi(self, scale_idx, xi, target=None, values=True, gradient=True):
+        """MutualInformation::Evaluate (8 bins, valMax 255) of the poses xi [n, 6] against target[k] (default: target 0) at one
+        scale: a dict with cost [n] (the negative mutual information), hist [n, 8, 8] (the joint histogram, [bin of the
+        target's sample, bin of the key frame's grey]), gradient [n, 6] or None (numpy) and values [n, m] or None (CUDA
+        tensor: the target's grey at every point of the pack, 0 where the point does not project)"""
+        import torch
+
+        if not 0 <= scale_idx < self.num_scales:
+            raise ValueError("scale index out of range")
+        xi, tg = self._poses(xi, target)
+        n = xi.shape[0]
+        L = capi.load()
+        val = None
+        if values:
+            m = ctypes.c_int64()
+            capi.check(L.vg_photometric_pack(self._h, scale_idx, ctypes.byref(m), None, None, None))
+            val = torch.zeros((n, m.value), dtype=torch.float64, device=self.device)
+        cost, hist = np.zeros(n), np.zeros((n, capi.MI_NUM_BINS, capi.MI_NUM_BINS))
+        grad = np.zeros((n, 6)) if gradient else None
+        self._enter()
+        capi.check(L.vg_mi_evaluate(self._h, scale_idx, n, xi.ctypes.data_as(_dp), tg.ctypes.data_as(_i32p),
+                                                val.data_ptr() if values else None, hist.ctypes.data_as(_dp), cost.ctypes.data_as(_dp),
+                                                grad.ctypes.data_as(_dp) if gradient else None))
+        self._leave(val)
+        return {"cost": cost, "hist": hist, "gradient": grad, "values": val}
+
+    def compute_pose_mi(self, xi_start, target=None, xi_odom=None, function_tolerance=None, gradient_tolerance=None, max_iterations=None):
+        """computePoseMI from the start poses xi_start [n, 6] (or one [6]) against target[k]: (poses, report); report is
+        float64 [n, num_scales, 4]: REPORT per scale.  xi_odom ([n, 6]): the odometry's motion per start pose; it selects
+        MutualInformationOdom, whose prior pose is the start pose; None: the plain cost.  The tolerances and the iteration cap
+        (per scale) default to the reference's: capi.MI_DEFAULTS."""
+        single = np.ndim(xi_start) == 1
+        xi, tg = self._poses(xi_start, target)
+        n = xi.shape[0]
+        odom = None
+        if xi_odom is not None:
+            odom = np.ascontiguousarray(xi_odom, dtype=np.float64).reshape(-1, 6)
+            if odom.shape[0] != n:
+                raise ValueError("%d poses but %d odometry poses" % (n, odom.shape[0]))
+        opt = capi.MiOptions()
+        for name, v in (("function_tolerance", function_tolerance), ("gradient_tolerance", gradient_tolerance), ("max_iterations", max_iterations)):
+            if v is not None:
+                if not v > 0:
+                    raise ValueError("%s must be positive" % name)
+                setattr(opt, name, v)
+        out, report = np.zeros((n, 6)), np.zeros((n, self.num_scales, 4))
+        self._enter()
+        capi.check(capi.load().vg_mi_compute_pose(self._h, n, xi.ctypes.data_as(_dp), tg.ctypes.data_as(_i32p),
+                                                              odom.ctypes.data_as(_dp) if odom is not None else None, ctypes.byref(opt),
+                                                              out.ctypes.data_as(_dp), report.ctypes.data_as(_dp)))
+        return (out[0], report[0]) if single else (out, report)
+
+
+def mi_odometry(xi_odom, xi_prior, xi):
+    """the odometry term of MutualInformationOdom at the pose xi, host arithmetic: (cost, gradient [6])"""
+    a, p, x = (_stereo._vec(v, 6, name) for v, name in ((xi_odom, "xi_odom"), (xi_prior, "xi_prior"), (xi, "xi")))
+    cost, grad = ctypes.c_double(), np.zeros(6)
+    capi.check(capi.load().vg_mi_odometry(a.ctypes.data_as(_dp), p.ctypes.data_as(_dp), x.ctypes.data_as(_dp), ctypes.byref(cost),
+                                                      grad.ctypes.data_as(_dp)))
+    return cost.value, grad
