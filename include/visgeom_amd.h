@@ -504,6 +504,8 @@ int vg_transform_from_values(int n, const double *values, double *out6);
  *    blocks resident in HBM; one evaluation of the whole set is two launches (one lane per block for the transform chain,
  *    one lane per feature for triangulation / projection / the 2 x 6 rows).  The camera is constant (the reference clones
  *    it in the constructor).  xi_base_cam: the base -> camera transform shared by all blocks of the set.
+ *    These entries evaluate the costs for a solver of the caller's; section 13 (sparse visual odometry) is the library's own
+ *    caller: it solves the SparseReprojectCost problems of a frame pair on the device, prior included.
  * ===================================================================================== */
 typedef struct vg_reproject_set vg_reproject_set;
 /* SparseReprojectCost ctor (.h:185-195) for n_blocks blocks; block b owns points [offsets[b], offsets[b + 1]) of the
@@ -847,6 +849,102 @@ int vg_mi_compute_pose(vg_photometric *h, int64_t n, const double *xi_start, con
 /* Host only: the odometry term of MutualInformationOdom alone, as compute_pose_mi adds it -- *cost = DAMPING err (C / 2) err^T,
  * gradient (HOST [6], may be NULL) = DAMPING err J, for the pose xi (all HOST [6]). */
 int vg_mi_odometry(const double *xi_odom, const double *xi_prior, const double *xi, double *cost, double *gradient);
+
+/* =====================================================================================
+ * 13. Sparse visual odometry: the reference's SparseOdometry::feedData (src/localization/sparse_odom.cpp:240-437) -- the camera
+ *     motion between two consecutive images before any depth map exists, from Harris corners (:161-203), 9 x 9 weighted
+ *     patches (:205-238), brute-force L1 matching with cross-check (:266-300), a RANSAC of small SparseReprojectCost +
+ *     OdometryPrior solves (:511-606, :440-469) and two refinements (:336-387).  Images are DEVICE u8 [n][height][width],
+ *     poses HOST [t, rotvec] of the base frame.  Every call is synchronous on the handle's stream and checks its arguments
+ *     before HIP is touched.  All arithmetic is FP64 or integer and every floating-point sum has a fixed order: results are
+ *     bit-identical from run to run and do not depend on the batch a problem is part of.  Deviations: DESIGN.md section 9,
+ *     "Sparse visual odometry".
+ * ===================================================================================== */
+typedef struct vg_sparse_odom vg_sparse_odom;
+typedef struct vg_sparse_odom_params {
+    int max_features;         /* NUM_FEATURES 500; in [1, 1024] */
+    double match_threshold;   /* distThresh 2500: a match with a larger L1 distance is dropped */
+    int num_ransac_points;    /* numRansacPoints 2; in [2, 16] */
+    int ransac_iterations;    /* maxIteration 200; in [1, 65535] */
+    double inlier_threshold;  /* thresh 1.0 pixel */
+    int max_lm_iterations;    /* max_num_iterations 25 of computeTransfSparse */
+    double prior_err_v, prior_err_w, prior_lambda_t, prior_lambda_r; /* OdometryPrior(0.03, 0.5, 0.03, 0.05, xiOdom) */
+    double outlier_gate;      /* 3.6: an inlier stays in the last solve when err^2 < outlier_gate * sigma^2 */
+    double min_stereo_base;   /* MIN_STEREO_BASE: feed skips a frame whose odometry moves the camera less; 0 */
+} vg_sparse_odom_params;
+void vg_sparse_odom_params_default(vg_sparse_odom_params *params);
+/* A handle for one EUCM camera (eucm: HOST 6 intrinsics), xi_base_cam (HOST [6], the camera in the base frame) and one image
+ * size; images smaller than 15 x 15 are refused (the detector's 7-pixel border leaves no interior). */
+int vg_sparse_odom_create(vg_sparse_odom **out, int device, void *hip_stream, const double *eucm, const double *xi_base_cam, int width,
+                          int height, const vg_sparse_odom_params *params);
+void vg_sparse_odom_destroy(vg_sparse_odom *h);
+/* Stage entry: the Harris map of n images, DEVICE int64 [n][height][width].  cornerHarris(img, 7, 3, 0.05) in exact integer
+ * arithmetic: Sobel 3 x 3 dx, dy (|.| <= 1020), a = sum dx^2, b = sum dx dy, c = sum dy^2 over the 7 x 7 box, R = 20 (a c -
+ * b^2) - (a + c)^2 -- the reference's response times the constant 20 (4 * 7 * 255)^4, |R| < 6e16.  Pixels whose Sobel or box
+ * window leaves the image use BORDER_REFLECT_101. */
+int vg_sparse_odom_response(vg_sparse_odom *h, int64_t n, const uint8_t *img, int64_t *response);
+/* Stage entry: harrisCorners + descriptors of n images.  A pixel with 7 <= u < width - 7, 7 <= v < height - 7 is a feature when
+ * its response is strictly greater than its 8 neighbours'; the max_features largest are kept, ordered by (R descending, raster
+ * index v * width + u descending) -- the order in which the reference's heap of pair<double, int> pops them.  count HOST int32
+ * [n]; keypoints DEVICE int32 [n][max_features][2] as (u, v); descriptors DEVICE float [n][max_features][81]: the 9 x 9 patch,
+ * each grey value times exp(-(x^2 + y^2) / 2), x = du / 2, y = dv / 2 (the weight in double, the product rounded to float).
+ * Entries past count are zero. */
+int vg_sparse_odom_detect(vg_sparse_odom *h, int64_t n, const uint8_t *img, int32_t *count, int32_t *keypoints, float *descriptors);
+/* Stage entry: BFMatcher(NORM_L1, crossCheck) + the distance threshold for n pairs of descriptor sets (count HOST int32 [n],
+ * descriptors DEVICE float [n][max_features][81]; matching reads no key points).  The L1 distance is summed in FP64 over the 81
+ * values in patch order; a nearest neighbour is the lowest index on ties; (i, j) is a match when j is the nearest of set 2 to
+ * i, i the nearest of set 1 to j and the distance is not above match_threshold.  match_count HOST int32 [n]; matches DEVICE
+ * int32 [n][max_features][2], ordered by i; distance DEVICE FP64 [n][max_features]. */
+int vg_sparse_odom_match(vg_sparse_odom *h, int64_t n, const int32_t *count1, const float *descriptors1, const int32_t *count2,
+                         const float *descriptors2, int32_t *match_count, int32_t *matches, double *distance);
+/* Stage entry: computeTransfSparse for n_blocks independent problems in ONE launch.  Block b owns points [offsets[b], offsets[b
+ * + 1]) (offsets HOST int64 [n_blocks + 1], offsets[0] = 0; an empty block is the prior alone) of x1 / x2 (DEVICE [m][3], rays in
+ * camera frames 1 / 2), p2 (DEVICE [m][2], the pixel in image 2) and size (DEVICE [m]).  Every problem is OdometryPrior(params,
+ * xi_odom) + one SparseReprojectCost, started at xi_odom (HOST [6], the odometry increment), solved by a trust-region
+ * Levenberg-Marquardt with Ceres' default tolerances and at most max_lm_iterations iterations, one wave per problem.  xi_out
+ * HOST [n_blocks][6]; report (HOST [n_blocks][4], may be NULL): iterations, initial cost, final cost, vg_termination. */
+int vg_sparse_odom_solve(vg_sparse_odom *h, int64_t n_blocks, const int64_t *offsets, const double *x1, const double *x2,
+                         const double *p2, const double *size, const double *xi_odom, double *xi_out, double *report);
+/* Stage entry: the scoring of ransacNPoints for n_hyp base-frame motions (xi HOST [n_hyp][6]) on m matches, one launch: camera
+ * motion xi_c = xi_base_cam^-1 o xi o xi_base_cam, Triangulator(xi_c).computeRegular, the scaled ray moved by xi_c^-1,
+ * projection, pixel distance to p2.  residual DEVICE FP64 [n_hyp][m] (may be NULL; +inf where the point does not project),
+ * inliers HOST int32 [n_hyp]: the matches with residual < inlier_threshold. */
+int vg_sparse_odom_score(vg_sparse_odom *h, int64_t n_hyp, const double *xi, int64_t m, const double *x1, const double *x2,
+                         const double *p2, double *residual, int32_t *inliers);
+/* The library's own draw of a RANSAC sample table for m matches (HOST int32 [ransac_iterations][num_ransac_points], distinct
+ * within a row): the first num_ransac_points steps of a Fisher-Yates shuffle of an index vector that persists between rows, on
+ * xorshift64* (shifts 12, 25, 27, multiplier 0x2545F4914F6CDD1D) seeded 0x9E3779B97F4A7C15 at creation.  Host only. */
+int vg_sparse_odom_draw_samples(vg_sparse_odom *h, int64_t m, int32_t *samples);
+#define VG_SPARSE_ODOM_REPORT 8          /* best hypothesis (-1: none), its inlier count, inliers kept by the sigma gate, final cost
+                                            and vg_termination of the first, then of the second refinement, status */
+#define VG_SPARSE_ODOM_OK 0
+#define VG_SPARSE_ODOM_TOO_FEW_MATCHES 1 /* fewer matches than num_ransac_points: xi_incr = xi_odom */
+#define VG_SPARSE_ODOM_NO_HYPOTHESIS 2   /* no hypothesis with more than num_ransac_points inliers: xi_incr = xi_odom */
+/* ransacNPoints and the refinement of feedData for one frame pair: m matches as for solve, xi_odom HOST [6] the odometry
+ * increment.  samples: HOST int32 [ransac_iterations][num_ransac_points] with every index in [0, m), or NULL for
+ * vg_sparse_odom_draw_samples (the reference's std::shuffle of mt19937(0) is specific to its standard library).  All hypotheses
+ * are solved in one launch and scored in one; a hypothesis replaces the best only with strictly more inliers, starting from
+ * num_ransac_points.  Then: a solve on the best one's inliers; their reprojection under the camera motion of the ODOMETRY
+ * (what the reference passes, sparse_odom.cpp:354-355); sigma^2 = sum err^2 / (n - 2); a last solve, from xi_odom again, on
+ * the inliers with err^2 < outlier_gate sigma^2.  xi_incr HOST [6]; mask DEVICE u8 [m] (may be NULL): the best hypothesis'
+ * inliers; report HOST [VG_SPARSE_ODOM_REPORT] (may be NULL). */
+int vg_sparse_odom_ransac(vg_sparse_odom *h, int64_t m, const double *x1, const double *x2, const double *p2, const double *size,
+                          const double *xi_odom, const int32_t *samples, double *xi_incr, uint8_t *mask, double *report);
+#define VG_SPARSE_ODOM_FEED_REPORT 12    /* state, key points detected, matches, 0, then the ransac report */
+#define VG_SPARSE_ODOM_FIRST 0           /* no previous frame (or one without key points): detected only */
+#define VG_SPARSE_ODOM_SKIPPED 1         /* the skip rule: nothing changed */
+#define VG_SPARSE_ODOM_ESTIMATED 2
+/* feedData: img DEVICE u8 [height][width], xi_odom_new HOST [6] the wheel odometry's pose of the base frame at the image.  With
+ * a previous frame whose odometry implies a camera translation below min_stereo_base the call returns at once and changes
+ * nothing.  Otherwise: detect; with a previous frame match, lift the matched pixels to rays, ransac with the odometry
+ * increment, integrated = integrated o xi_incr; the new frame becomes the previous one.  samples as for ransac, but an index s
+ * is used as s % (matches found), since the caller cannot know that count; negative indices are refused.  xi_incr (HOST [6],
+ * may be NULL) receives the current increment, report HOST [VG_SPARSE_ODOM_FEED_REPORT] (may be NULL). */
+int vg_sparse_odom_feed(vg_sparse_odom *h, const uint8_t *img, const double *xi_odom_new, const int32_t *samples, double *xi_incr,
+                        double *report);
+/* xiIncr of the last estimated pair and xiLocal, the composition of all increments (HOST [6]; zero at creation) */
+int vg_sparse_odom_increment(const vg_sparse_odom *h, double *xi6);
+int vg_sparse_odom_integrated(const vg_sparse_odom *h, double *xi6);
 
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",

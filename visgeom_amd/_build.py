@@ -30,7 +30,8 @@ def sources():
     helpers; vg_gram_tu: normal equations; vg_solver_tu: LM / Schur + communicator; vg_refine_tu: per-image pose LM; vg_frontend_tu: calibration JSON;
     vg_local_tu: localization costs; vg_rectify_tu: rectification maps and remap;
     vg_corners_tu: checkerboard corner detection; vg_stereo_tu: fisheye semi-global stereo; vg_motion_tu: motion stereo;
-    vg_depth_tu: depth map warp / merge / noise filter; vg_photometric_tu: photometric pose estimation)"""
+    vg_depth_tu: depth map warp / merge / noise filter; vg_photometric_tu: photometric pose estimation;
+    vg_sparse_odom_tu: sparse visual odometry)"""
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
 
 

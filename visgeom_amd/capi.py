@@ -230,6 +230,19 @@ SIGNATURES = {
     "vg_mi_evaluate": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _dp, _i32p, _vp, _dp, _dp, _dp]),
     "vg_mi_compute_pose": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _i32p, _dp, _vp, _dp, _dp]),
     "vg_mi_odometry": (ctypes.c_int, [_dp, _dp, _dp, _dp, _dp]),
+    "vg_sparse_odom_params_default": (None, [_vp]),
+    "vg_sparse_odom_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, _dp, _dp, ctypes.c_int, ctypes.c_int, _vp]),
+    "vg_sparse_odom_destroy": (None, [_vp]),
+    "vg_sparse_odom_response": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp]),
+    "vg_sparse_odom_detect": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _i32p, _vp, _vp]),
+    "vg_sparse_odom_match": (ctypes.c_int, [_vp, ctypes.c_int64, _i32p, _vp, _i32p, _vp, _i32p, _vp, _vp]),
+    "vg_sparse_odom_solve": (ctypes.c_int, [_vp, ctypes.c_int64, _i64p, _vp, _vp, _vp, _vp, _dp, _dp, _dp]),
+    "vg_sparse_odom_score": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, ctypes.c_int64, _vp, _vp, _vp, _vp, _i32p]),
+    "vg_sparse_odom_draw_samples": (ctypes.c_int, [_vp, ctypes.c_int64, _i32p]),
+    "vg_sparse_odom_ransac": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _dp, _i32p, _dp, _vp, _dp]),
+    "vg_sparse_odom_feed": (ctypes.c_int, [_vp, _vp, _dp, _i32p, _dp, _dp]),
+    "vg_sparse_odom_increment": (ctypes.c_int, [_vp, _dp]),
+    "vg_sparse_odom_integrated": (ctypes.c_int, [_vp, _dp]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),
@@ -258,6 +271,17 @@ class MiOptions(ctypes.Structure):
     _fields_ = [("function_tolerance", ctypes.c_double), ("gradient_tolerance", ctypes.c_double), ("max_iterations", ctypes.c_int)]
 
 
+class SparseOdomParams(ctypes.Structure):
+    """struct vg_sparse_odom_params"""
+    _fields_ = [("max_features", ctypes.c_int), ("match_threshold", ctypes.c_double), ("num_ransac_points", ctypes.c_int),
+                ("ransac_iterations", ctypes.c_int), ("inlier_threshold", ctypes.c_double), ("max_lm_iterations", ctypes.c_int),
+                ("prior_err_v", ctypes.c_double), ("prior_err_w", ctypes.c_double), ("prior_lambda_t", ctypes.c_double),
+                ("prior_lambda_r", ctypes.c_double), ("outlier_gate", ctypes.c_double), ("min_stereo_base", ctypes.c_double)]
+
+
+SPARSE_ODOM_REPORT, SPARSE_ODOM_FEED_REPORT = 8, 12
+SPARSE_ODOM_OK, SPARSE_ODOM_TOO_FEW_MATCHES, SPARSE_ODOM_NO_HYPOTHESIS = 0, 1, 2
+SPARSE_ODOM_FIRST, SPARSE_ODOM_SKIPPED, SPARSE_ODOM_ESTIMATED = 0, 1, 2
 MI_NUM_BINS, MI_VALUE_MAX, MI_ODOMETRY_DAMPING = 8, 255., 0.0002
 MI_DEFAULTS = {"function_tolerance": 1e-2, "gradient_tolerance": 1e-3, "max_iterations": 50}
 

@@ -431,16 +431,18 @@ struct SparseArgs {
     unsigned int n_points;     // count
 };
 
-// one point of a SparseReprojectCost block; f = the block's frame (a wave-uniform or a per-lane address)
-template <int MODEL>
-__device__ __forceinline__ void sparse_point(const SparseArgs &a, const double *__restrict__ f, const long long pt, const unsigned int o,
-                                             const bool active, const unsigned int o0, double *stage, const int wave, const int lane)
+// residual pair and (want_jac) the 2 x 6 rows of one point of a SparseReprojectCost block; f = the block's frame (a
+// wave-uniform or a per-lane address).  Shared by the row-streaming kernel below and by the sparse odometry solve
+// (vg_sparse_odom.hpp), which sums the rows instead of storing them.  The observation is loaded (load_obs) and the residual
+// and the rows are handed over (on_residual, on_rows) where the row-streaming kernel has always loaded and stored them: that
+// keeps its live ranges, and with them its registers, what they were before the function was shared.
+template <int MODEL, class LoadObs, class OnResidual, class OnRows>
+__device__ __forceinline__ void sparse_point_eval(const double *__restrict__ intr, const double *__restrict__ f, const double *x1, const double *x2,
+                                                  LoadObs load_obs, const double *size, const bool want_jac, OnResidual on_residual, OnRows on_rows)
 {
     constexpr int K = CameraTraits<MODEL>::K;
     using d2 = HIP_vector_type<double, 2>;
-    const double *x1 = a.x1 + pt * 3, *x2 = a.x2 + pt * 3;
     const double *t12 = f, *Rt = f + 3, *R21 = f + 12;
-    const bool want_jac = a.jac != nullptr;
     double jv[6];
     // Triangulator(xi12): eps = 1e-3.  (Two calls: a pointer chosen at run time would put jv into scratch memory.)
     const double lam = want_jac ? triangulate_regular(Rt, t12, 1e-3, x1, x2, jv) : triangulate_regular(Rt, t12, 1e-3, x1, x2, nullptr);
@@ -449,15 +451,15 @@ __device__ __forceinline__ void sparse_point(const SparseArgs &a, const double *
     double X[3];
     mat3_vec(R21, d, X);
     CornerEval<K> e;
-    eval_corner<MODEL, true, false>(a.intr, X[0], X[1], X[2], e);
-    const d2 ob = reinterpret_cast<const d2 *>(a.p2)[pt];
+    eval_corner<MODEL, true, false>(intr, X[0], X[1], X[2], e);
+    const d2 ob = load_obs();
     // the reference divides two residuals and six Jacobian entries by the feature size; here ONE division and eight products
     // (each within an ulp of the quotient; an IEEE FP64 division is eleven instructions on this part)
-    const double rsz = 1. / a.size[pt];
+    const double rsz = 1. / *size;
     d2 r;
     r.x = e.ok ? (e.u - ob.x) * rsz : kDoubleBig;   // :311-323
     r.y = e.ok ? (e.v - ob.y) * rsz : kDoubleBig;
-    if (active) reinterpret_cast<d2 *>(a.res)[o] = r;
+    on_residual(r);
     if (want_jac) {
         double rows[12];
         pose_rows(e.P, X[0], X[1], X[2], f + 21, rows);   // :331-345 (a failed point has P = 0: zero rows, as :336-339)
@@ -489,11 +491,28 @@ __device__ __forceinline__ void sparse_point(const SparseArgs &a, const double *
         // :383-389: ONLY the u-row is divided by the feature size
 #pragma unroll
         for (int j = 0; j < 6; j++) rows[j] *= rsz;
-        const unsigned int ow = o0 + wave * kWave;
-        int n_valid = 0;
-        if (ow < a.n_points) n_valid = (a.n_points - ow < (unsigned)kWave) ? (int)(a.n_points - ow) : kWave;
-        wave_store_rows<6>(stage, rows, a.jac + (size_t)ow * 12, n_valid, lane);
+        on_rows(rows);
     }
+}
+
+// one point of a SparseReprojectCost block: evaluated, the residual pair stored, the rows streamed out through the wave's tile
+template <int MODEL>
+__device__ __forceinline__ void sparse_point(const SparseArgs &a, const double *__restrict__ f, const long long pt, const unsigned int o,
+                                             const bool active, const unsigned int o0, double *stage, const int wave, const int lane)
+{
+    using d2 = HIP_vector_type<double, 2>;
+    const double *x1 = a.x1 + pt * 3, *x2 = a.x2 + pt * 3;
+    sparse_point_eval<MODEL>(
+        a.intr, f, x1, x2, [&] { return reinterpret_cast<const d2 *>(a.p2)[pt]; }, a.size + pt, a.jac != nullptr,
+        [&](const d2 r) {
+            if (active) reinterpret_cast<d2 *>(a.res)[o] = r;
+        },
+        [&](const double(&rows)[12]) {
+            const unsigned int ow = o0 + wave * kWave;
+            int n_valid = 0;
+            if (ow < a.n_points) n_valid = (a.n_points - ow < (unsigned)kWave) ? (int)(a.n_points - ow) : kWave;
+            wave_store_rows<6>(stage, rows, a.jac + (size_t)ow * 12, n_valid, lane);
+        });
 }
 
 // FUSED: the frames of the blocks this workgroup's points belong to are computed in the kernel (one lane per block, into
