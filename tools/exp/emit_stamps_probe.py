@@ -3,10 +3,12 @@
     python -m visgeom_amd._build --variant stamps -DVG_EMIT_STAMPS
     python tools/exp/emit_stamps_probe.py [--images 10000] [--model eucm] [--out FILE.md]
 
-Every wave of vg_emit_kernel writes four stamps of the 100 MHz wall clock (0 entry, 1 after the barrier, 2 at its first store,
-3 after its last store was issued) to a side buffer; the buffer keeps the LAST launch of a train of 30 back-to-back launches.
-Printed: when the launch's first store leaves, per microsecond the waves resident, the waves
-between their first and last store ("storing") and the workgroups started, and when residency starts to fall."""
+Every wave of vg_emit_kernel writes stamps of the 100 MHz wall clock (0 entry, 1 after the barrier, 2 at its first store,
+3 after its last store was issued; 4 chain-parameter load issued, 5 its data arrived = start of the walk, walking waves only,
+6 intrinsics in registers behind the barrier) to a side buffer; the buffer keeps the LAST launch of a train of 30 back-to-back
+launches.  Printed: when the launch's first store leaves, the two store-less intervals of a wave split at the new stamps (first
+round and median wave), per microsecond the waves resident, the waves between their first and last store ("storing") and the
+workgroups started, and when residency starts to fall.  --lib NAME reads lib/variants/libvisgeom_amd_NAME.so (default: stamps)."""
 import argparse
 import os
 import sys
@@ -19,7 +21,9 @@ import torch  # noqa: E402
 
 from visgeom_amd import _build  # noqa: E402
 
-_build.LIB = os.path.join(_build.LIB_DIR, "variants", "libvisgeom_amd_stamps.so")
+PER_WAVE = 8   # kEmitStampsPerWave (vg_kernels.hpp)
+_variant = sys.argv[sys.argv.index("--lib") + 1] if "--lib" in sys.argv else "stamps"
+_build.LIB = os.path.join(_build.LIB_DIR, "variants", "libvisgeom_amd_%s.so" % _variant)
 
 from visgeom_amd import CalibrationProblem, capi, synthetic  # noqa: E402
 
@@ -35,7 +39,7 @@ def timeline(model, n_images, train=30):
     p.prepare()
     n_obs = n_images * d["board"].shape[0]
     n_wg = (n_obs + 255) // 256
-    stamps = torch.zeros(n_wg * 4 * 4, dtype=torch.int64, device="cuda:0")
+    stamps = torch.zeros(n_wg * 4 * PER_WAVE, dtype=torch.int64, device="cuda:0")
     try:
         for _ in range(5):
             p.evaluate_dataset(ds, res, ji, jm)
@@ -48,7 +52,7 @@ def timeline(model, n_images, train=30):
     finally:
         capi.debug_set("emit_stamps", 0)
         capi.debug_set("emit_stamps_waves", 0)
-    s = stamps.cpu().numpy().reshape(-1, 4).astype(np.int64)
+    s = stamps.cpu().numpy().reshape(-1, PER_WAVE).astype(np.int64)
     p.close()
     return s
 
@@ -72,6 +76,7 @@ def report(s, title, out):
     first_round = work[work[:, 0] < t0 + 50]
     out.append("first round (waves entered within 0.5 us): %d waves, their first stores at %.2f / %.2f / %.2f us (min / median / max)\n"
                % (len(first_round), us(first_round[:, 2].min()), us(np.median(first_round[:, 2])), us(first_round[:, 2].max())))
+    split_table(work, first_round, out)
     end = np.where(work[:, 3] != 0, work[:, 3], work[:, 2])
     n_bins = int(us(end.max())) + 1
     out.append("| us | waves resident | waves storing | waves started |\n|---|---|---|---|\n")
@@ -93,15 +98,34 @@ def report(s, title, out):
                % (steady, fall, us(end.max())))
 
 
+def split_table(work, first_round, out):
+    """the store-less intervals of a wave, split at stamps 4-6: medians in us over the first round and over all waves; the two
+    intervals around the chain-parameter data only over the waves that walk (stamp 5 set)"""
+    rows = [("entry -> chain load issued", 0, 4, False), ("chain load issued -> data arrived", 4, 5, True),
+            ("walk -> barrier", 5, 1, True), ("barrier -> intrinsics in registers", 1, 6, False),
+            ("intrinsics in registers -> first store", 6, 2, False)]
+    out.append("\n| interval (median, us) | first round | all waves |\n|---|---|---|\n")
+    for name, i, j, walking in rows:
+        cells = []
+        for w in (first_round, work):
+            w = w[(w[:, i] != 0) & (w[:, j] != 0)]
+            if walking:
+                w = w[w[:, 5] != 0]
+            cells.append("%.2f (%d waves)" % (np.median(w[:, j] - w[:, i]) / 100.0, len(w)) if len(w) else "-")
+        out.append("| %s | %s | %s |\n" % (name, cells[0], cells[1]))
+    out.append("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=10000)
     ap.add_argument("--model", default="eucm")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default="stamps")
     a = ap.parse_args()
     out = []
     s = timeline(a.model, a.images)
-    report(s, "%s, %d images" % (a.model, a.images), out)
+    report(s, "%s, %d images, library %s" % (a.model, a.images, a.lib), out)
     text = "".join(out)
     print(text)
     if a.out:

@@ -37,7 +37,7 @@ enum DebugHook {
     kHookEmitMapWindow,            // tile map of the emit launches: W > 0 = windows of 8 W tiles, XCD x the x-th run of W tiles in each (1 = linear map); -1 = one contiguous eighth per XCD (the map before round 6); 0 = the default (kEmitMapWindow)
     kHookEmitWriteThrough,         // store policy of emit launches inside the Infinity Cache: -1 = plain stores; 0 = the default (write-through, emit_store_policy)
     kHookEmitStamps,               // measurement build (-DVG_EMIT_STAMPS) only: device address of the per-wave clock stamps of the next emit launches
-    kHookEmitStampsWaves,          // with emit_stamps: the number of waves that buffer holds (4 stamps of 8 bytes each); waves past it do not stamp
+    kHookEmitStampsWaves,          // with emit_stamps: the number of waves that buffer holds (kEmitStampsPerWave stamps of 8 bytes each); waves past it do not stamp
     kHookCount
 };
 #ifdef VG_DEBUG_HOOKS

@@ -162,22 +162,28 @@ struct EmitArgs {
     int nt_stores;         // store policy of the launch (EmitStorePolicy): 1 = past the Infinity Cache, non-temporal; 2 = inside it, write-through
     unsigned int map_window;  // tile map of the launch: 0 = every XCD one contiguous eighth of the tiles; W > 0 = windows of 8 W tiles,
                               // XCD x the x-th run of W tiles in each window (W = 1: the linear map); xcd_window_block, kEmitMapWindow
-#ifdef VG_EMIT_STAMPS   // measurement build (tools/exp/emit_stamps_probe.py): four wall-clock stamps (100 MHz) per wave of the launch, or NULL
+#ifdef VG_EMIT_STAMPS   // measurement build (tools/exp/emit_stamps_probe.py): kEmitStampsPerWave wall-clock stamps (100 MHz) per wave of the launch, or NULL
     unsigned long long *stamps;
     unsigned long long stamps_waves;   // waves the buffer holds: a launch with more stamps only those
 #endif
 };
 
 #ifdef VG_EMIT_STAMPS
-// stamp k of this wave: 0 entry, 1 after the barrier, 2 at the first store, 3 after the last store; an ordinary vector store of lane 0
+// stamp k of this wave: 0 entry, 1 after the barrier, 2 at the first store, 3 after the last store; the two store-less intervals
+// split: 4 chain-parameter load issued, 5 its data arrived (start of the walk; walking waves only), 6 intrinsics in registers
+// (behind the barrier); an ordinary vector store of lane 0
+constexpr int kEmitStampsPerWave = 8;
 __device__ __forceinline__ void emit_stamp(const EmitArgs &a, int k)
 {
     const unsigned long long w = (unsigned long long)blockIdx.x * (kEmitThreads / kWave) + (threadIdx.x >> 6);
-    if (a.stamps && w < a.stamps_waves && (threadIdx.x & (kWave - 1)) == 0) a.stamps[w * 4 + k] = wall_clock64();
+    if (a.stamps && w < a.stamps_waves && (threadIdx.x & (kWave - 1)) == 0) a.stamps[w * kEmitStampsPerWave + k] = wall_clock64();
 }
 #define VG_EMIT_STAMP(a, k) emit_stamp(a, k)
+// the stamp behind it is taken once these values have arrived
+#define VG_EMIT_STAMP_ARRIVED6(x) asm volatile("" ::"v"((x)[0]), "v"((x)[1]), "v"((x)[2]), "v"((x)[3]), "v"((x)[4]), "v"((x)[5]))
 #else
 #define VG_EMIT_STAMP(a, k) ((void)0)
+#define VG_EMIT_STAMP_ARRIVED6(x) ((void)0)
 #endif
 
 // Each lane holds the 2S doubles of its observation's two rows; the wave's 64 observations are one
@@ -344,7 +350,9 @@ __device__ __forceinline__ unsigned int xcd_window_block(unsigned int b, unsigne
 
 // The Jacobian row blocks of one tile (WANT_JAC), after its residual pair has left: the intrinsic and pose row blocks through the wave's
 // LDS tile.  With the frames in LDS nothing waits on vmcnt from the tile's first store on: every global load was consumed before it.
-template <int MODEL, bool WANT_JAC, int POLICY>
+// ONE_MEMBER (an INLINE_CHAIN tile with its state fetched at entry: the chain is one member, dataset_can_inline_chain): no member loop,
+// no fetch of L, jac_member[0] only.
+template <int MODEL, bool WANT_JAC, int POLICY, bool ONE_MEMBER = false>
 __device__ __forceinline__ void emit_tile_rows(const EmitArgs &a, const unsigned int o0, const unsigned int o_end,
                                                  const CornerEval<CameraTraits<MODEL>::K> &e, double X0, double X1, double X2,
                                                  const double *fr, double *stage)
@@ -368,14 +376,51 @@ __device__ __forceinline__ void emit_tile_rows(const EmitArgs &a, const unsigned
             else wave_store_rows<(K > kStageRowDoubles ? 1 : K), POLICY>(stage, rows, a.jac_intr + (size_t)ow * (2 * K), n_valid, lane);
         }
         // pose blocks, u-row at +12i, v-row at +12i+6       calib_cost_functions.cpp:93-101
-        for (int l = 0; l < a.L; l++) {
-            double *Jm = a.jac_member[l];
-            if (!Jm) continue;
-            double rows[12];
-            pose_rows(e.P, X0, X1, X2, fr + 12 + 21 * l, rows);
-            wave_store_rows<6, POLICY>(stage, rows, Jm + (size_t)ow * 12, n_valid, lane);
+        if constexpr (ONE_MEMBER) {
+            if (double *Jm = a.jac_member[0]) {
+                double rows[12];
+                pose_rows(e.P, X0, X1, X2, fr + 12, rows);
+                wave_store_rows<6, POLICY>(stage, rows, Jm + (size_t)ow * 12, n_valid, lane);
+            }
+        } else {
+            for (int l = 0; l < a.L; l++) {
+                double *Jm = a.jac_member[l];
+                if (!Jm) continue;
+                double rows[12];
+                pose_rows(e.P, X0, X1, X2, fr + 12 + 21 * l, rows);
+                wave_store_rows<6, POLICY>(stage, rows, Jm + (size_t)ow * 12, n_valid, lane);
+            }
         }
     }
+}
+
+// Wave-uniform state of a tile whose state is fetched at entry (ENTRY_STATE below).  Left alone, the compiler fetches every kernel
+// argument with an s_load of its own at the point of first use, each behind its own `s_waitcnt lgkmcnt(0)` -- a wait that also drains
+// the wave's LDS reads, SMEM and LDS share the counter -- eleven dependent round trips in front of a tile's first store and three more
+// between its stores (profiles/r15_emit_scalar_head.md).  One statement consumes every field the instantiation uses as an SGPR input:
+// the loads become a few wide ones in the entry block behind ONE wait (the grid size of the tile map, a hidden argument, with them).
+// `epoch` is not listed: only the failed-projection CAS block reads it.  (Input-only constraints: an in/out "+s" does not compile,
+// "illegal VGPR to SGPR copy".)
+template <bool WANT_JAC>
+__device__ __forceinline__ void emit_fetch_args(const EmitArgs &a)
+{
+    if constexpr (WANT_JAC)
+        asm volatile("" ::"s"(a.board), "s"(a.obs), "s"(a.intr), "s"(a.res), "s"(a.jac_intr), "s"(a.jac_member[0]), "s"(a.failed),
+                     "s"(a.chain_params), "s"(a.seq_index), "s"(a.chain_stride), "s"(a.first_block), "s"(a.n_obs), "s"(a.N),
+                     "s"(a.frame_stride_d), "s"(a.map_window), "s"(gridDim.x));
+    else
+        asm volatile("" ::"s"(a.board), "s"(a.obs), "s"(a.intr), "s"(a.res), "s"(a.failed), "s"(a.chain_params), "s"(a.seq_index),
+                     "s"(a.chain_stride), "s"(a.first_block), "s"(a.n_obs), "s"(a.N), "s"(a.frame_stride_d), "s"(a.map_window), "s"(gridDim.x));
+}
+
+// The camera's intrinsics, loaded through EmitArgs::intr at entry, held in SGPRs from here on: one statement, one wait.
+template <int K>
+__device__ __forceinline__ void emit_pin_intrinsics(const double *x)
+{
+    static_assert(K == 5 || K == 6 || K == 10, "UCM, EUCM, Mei");
+    if constexpr (K == 5) asm volatile("" ::"s"(x[0]), "s"(x[1]), "s"(x[2]), "s"(x[3]), "s"(x[4]));
+    else if constexpr (K == 6) asm volatile("" ::"s"(x[0]), "s"(x[1]), "s"(x[2]), "s"(x[3]), "s"(x[4]), "s"(x[5]));
+    else asm volatile("" ::"s"(x[0]), "s"(x[1]), "s"(x[2]), "s"(x[3]), "s"(x[4]), "s"(x[5]), "s"(x[6]), "s"(x[7]), "s"(x[8]), "s"(x[9]));
 }
 
 // dynamic LDS: 4 wave tiles, then (FRAMES_LDS) the frames of the images this workgroup touches
@@ -386,9 +431,15 @@ __device__ __forceinline__ void emit_tile_rows(const EmitArgs &a, const unsigned
 // HEAD_FIRST (the single-dataset kernel): the tile is ordered for an early first store -- the chain parameters are its first load and
 // the residual pair leaves before the Jacobian arithmetic.  The merged kernel keeps the plain order: with the early order its stereo
 // launch ran 18.5-18.7 us against the parent's 18.1 and the rig's 100.3-101.1 against 99.4-99.5 (profiles/r14_emit_head_tail.md).
-template <int MODEL, bool WANT_JAC, bool FRAMES_LDS, bool INLINE_CHAIN, int POLICY, bool HEAD_FIRST = false>
-__device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int o0)
+// ENTRY_STATE (the single-dataset kernel's INLINE_CHAIN tiles): the rule of the tile is that wave-uniform state is fetched at entry
+// and nothing scalar lies behind the first vector access.  The kernel has consumed the arguments (emit_fetch_args) and issued the
+// loads of the intrinsics (intr_entry) before it calls; the intrinsics' round trip overlaps the chain-parameter load and the walk and
+// is waited for once, in front of the barrier.  The chain has one member at compile time.  Only the failed-projection CAS block (rare)
+// may still fetch: the epoch (tests/test_emit_scalar_head_isa_cpu.py).
+template <int MODEL, bool WANT_JAC, bool FRAMES_LDS, bool INLINE_CHAIN, int POLICY, bool HEAD_FIRST = false, bool ENTRY_STATE = false>
+__device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int o0, const double *intr_entry = nullptr)
 {
+    static_assert(!ENTRY_STATE || INLINE_CHAIN, "the entry fetch is built for the tiles that walk their chain");
     VG_EMIT_STAMP(a, 0);
     static_assert(!INLINE_CHAIN || FRAMES_LDS, "the inline chain writes its frames to LDS");
     constexpr int K = CameraTraits<MODEL>::K;
@@ -415,7 +466,10 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
             for (int k = 0; k < 6; k++) xi_r[k] = (a.chain_params + a.chain_stride * si)[k];
         }
     };
-    if (INLINE_CHAIN && HEAD_FIRST) load_chain_params();
+    if (INLINE_CHAIN && HEAD_FIRST) {
+        load_chain_params();
+        VG_EMIT_STAMP(a, 4);
+    }
 
     const unsigned int o = o0 + tid;
     const bool active = o < o_end;
@@ -431,8 +485,13 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
     if (FRAMES_LDS) {
         double *fr_lds = smem + (kEmitThreads / kWave) * emit_stage_doubles_per_wave<MODEL>();
         if (INLINE_CHAIN) {
-            if (!HEAD_FIRST) load_chain_params();
+            if (!HEAD_FIRST) {
+                load_chain_params();
+                VG_EMIT_STAMP(a, 4);
+            }
             if (const unsigned int f = tid; f < nf) {
+                VG_EMIT_STAMP_ARRIVED6(xi_r);
+                VG_EMIT_STAMP(a, 5);
                 {   // The short walk of the Gram kernels (one sincos at the half angle, R12 = I, M12 from uhat^2 = u u^T - I: the
                     // reference's frame to 1e-16; inside and just above its first-order branches it IS the reference-order
                     // routine).  While <= 4 lanes walk, the tile's other 252 wait at the barrier below with no store in
@@ -447,6 +506,7 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
             d2 *dst = reinterpret_cast<d2 *>(fr_lds);
             for (int i = tid; i < n16; i += kEmitThreads) dst[i] = src[i];
         }
+        if constexpr (ENTRY_STATE) emit_pin_intrinsics<K>(intr_entry);
         __syncthreads();
         VG_EMIT_STAMP(a, 1);
         fr = fr_lds + (b - b_first) * a.frame_stride_d;
@@ -465,7 +525,12 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
     // would be a global load the wave waits for with its own store in flight.
     double intr[K];
 #pragma unroll
-    for (int i = 0; i < K; i++) intr[i] = a.intr[i];
+    for (int i = 0; i < K; i++) intr[i] = ENTRY_STATE ? intr_entry[i] : a.intr[i];
+#ifdef VG_EMIT_STAMPS
+#pragma unroll
+    for (int i = 0; i < K; i++) asm volatile("" ::"v"(intr[i]));
+    VG_EMIT_STAMP(a, 6);
+#endif
     CornerEval<K> e;
     if (HEAD_FIRST) eval_corner<MODEL, false, false>(intr, X0, X1, X2, e);
     else eval_corner<MODEL, WANT_JAC, WANT_JAC>(intr, X0, X1, X2, e);
@@ -501,7 +566,7 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &a, const unsigned int 
 
     if (WANT_JAC) {
         if (HEAD_FIRST) eval_corner<MODEL, true, true>(intr, X0, X1, X2, e);
-        emit_tile_rows<MODEL, WANT_JAC, POLICY>(a, o0, o_end, e, X0, X1, X2, fr, smem + wave * emit_stage_doubles_per_wave<MODEL>());
+        emit_tile_rows<MODEL, WANT_JAC, POLICY, ENTRY_STATE>(a, o0, o_end, e, X0, X1, X2, fr, smem + wave * emit_stage_doubles_per_wave<MODEL>());
     }
     VG_EMIT_STAMP(a, 3);
 }
@@ -516,8 +581,21 @@ template <int MODEL, bool WANT_JAC, bool FRAMES_LDS, bool INLINE_CHAIN, int POLI
 #endif
 __global__ __launch_bounds__(kEmitThreads) __attribute__((amdgpu_waves_per_eu(VG_EMIT_WAVES, 8))) void vg_emit_kernel(EmitArgs a)
 {
+    // INLINE_CHAIN: every argument the tile uses in SGPRs behind one wait, then the intrinsics behind their pointer (emit_tile,
+    // ENTRY_STATE).  The prepared-frames instantiations keep the fetch at first use and the run-time member loop.
+    constexpr int K = CameraTraits<MODEL>::K;
+    double intr[K];
+    if constexpr (INLINE_CHAIN) {
+        emit_fetch_args<WANT_JAC>(a);
+        // Nothing writes the parameters while an evaluation reads them: read through the constant address space, the intrinsics are scalar
+        // loads (a plain load behind the statement above becomes a vector load into 2 K VGPRs: the statement counts as a write).
+        // volatile: the loads stay in the entry block; left free, the compiler sinks Mei's ten doubles behind the chain-parameter load.
+        const volatile __attribute__((address_space(4))) double *ci = (const volatile __attribute__((address_space(4))) double *)a.intr;
+#pragma unroll
+        for (int i = 0; i < K; i++) intr[i] = ci[i];
+    }
     const unsigned int t = a.map_window ? xcd_window_block(blockIdx.x, gridDim.x, a.map_window) : xcd_contiguous_block(blockIdx.x, gridDim.x);
-    emit_tile<MODEL, WANT_JAC, FRAMES_LDS, INLINE_CHAIN, POLICY, true>(a, t * (unsigned)kEmitThreads);
+    emit_tile<MODEL, WANT_JAC, FRAMES_LDS, INLINE_CHAIN, POLICY, true, INLINE_CHAIN>(a, t * (unsigned)kEmitThreads, intr);
 }
 
 // ------------------------------------------------------------------------------------------
