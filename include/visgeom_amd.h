@@ -658,7 +658,7 @@ int vg_stereo_curve_cost(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, con
                          uint8_t *salient, uint8_t *skip);
 /* Stage entry: the sum of the four directional tableaux (computeDynamicProgramming), DEVICE int32 [n][y][x][disp_max], and
  * the winner, DEVICE int32 [n][y][x] (NULL allowed).  Not chunked; its device scratch is disp_max + 3 bytes per depth pixel
- * per pair (the error volume, step / salient / skip), 4 more when disparity is NULL. */
+ * per pair (the error volume, step / salient / skip), 4 more and up to 3 of alignment when disparity is NULL. */
 int vg_stereo_aggregate(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const uint8_t *img2, int32_t *total, int32_t *disparity);
 /* Host only: CurveRasterizer<int, Polynomial2>(u, v, eu, ev, poly6) after setStep(step_mult), then `steps` steps (negative:
  * unsteps), one at a time, |steps| <= 1000: uv [|steps| + 1][2] receives the start and every position. */

@@ -1,6 +1,8 @@
 """Synthetic EUCM stereo pairs for the stereo tests: textured planes ray cast into both cameras with supersampling (like
 board_render.py), a band-limited random texture fixed to the planes, and the true range along camera 1's rays per depth
-pixel.  Three rigs: a sideways baseline, a vertical one, and a mostly forward one whose epipoles lie inside the images."""
+pixel.  Three rigs: a sideways baseline, a vertical one, and a mostly forward one whose epipoles lie inside the images.
+Planes, patch, texture periods and cameras are arguments whose defaults are those three rigs' world; STRIP is a fourth
+scene built from them, a wide low pair in front of a near, steep wall whose disparities span 0 ... 255 (see make_strip)."""
 import numpy as np
 
 from tests import stereo_ref
@@ -16,6 +18,22 @@ RIGS = {
 # planes n . X = d in camera 1's frame, nearest hit wins: a slanted wall and a closer patch
 PLANES = [(np.array([0.0, -0.25, 1.0]), 1.4), (np.array([0.3, 0.0, 1.0]), 0.9)]
 PATCH = (-0.35, 0.05, -0.3, 0.1)   # the second plane only where x in [a, b], y in [c, d] (camera 1 frame)
+PERIODS = (0.05, 0.2)              # the texture's band: periods of its plane waves, metres
+
+# The strip scene: 400 x 49 images, a 0.3 m baseline and one wall.  The "steep" wall n . X = 0.45 runs from 0.2 m to 2 m
+# range across the depth grid (96 x 16 pixels from (292, 16)), so the winners cover the whole of [0, 256) while every
+# camera-2 walk of 256 steps stays inside the image; the "flat" wall faces the cameras at 0.7 m (disparities 56 ... 67), for
+# descriptors too long to match across the steep wall's foreshortening.  The "fine" texture gives descriptor step 1 nearly
+# everywhere; "coarse" and "broad" have flat stretches where the descriptor falls through to the larger scales.
+STRIP = {
+    "cam1": [0.6, 1.05, 160., 159., 341.5, 24.5],
+    "cam2": [0.59, 1.0, 159.5, 160.2, 340., 25.],
+    "xi12": [0.3, 0.004, -0.003, 0.004, -0.006, 0.01],
+    "planes": {"steep": [(np.array([2.2, -0.1, 1.0]), 0.45)], "flat": [(np.array([0.0, 0.0, 1.0]), 0.7)]},
+    "periods": {"fine": (0.01, 0.05), "coarse": (0.03, 0.4), "broad": (0.1, 0.4)},
+    "u_max": 400, "v_max": 49,
+    "grid": dict(u0=292, v0=16, x_max=96, y_max=16, scale=1),
+}
 
 
 def reconstruct_np(c, u, v):
@@ -28,12 +46,12 @@ def reconstruct_np(c, u, v):
     return np.stack([xn, yn, z], -1)
 
 
-def texture(P, seed=7, k=24):
-    """band-limited random texture on world points P [..., 3]: a sum of k plane waves, periods 0.05 - 0.2 m"""
+def texture(P, seed=7, k=24, periods=PERIODS):
+    """band-limited random texture on world points P [..., 3]: a sum of k plane waves, periods 0.05 - 0.2 m by default"""
     rng = np.random.default_rng(seed)
     dirs = rng.normal(size=(k, 3))
     dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
-    freq = 2 * np.pi / rng.uniform(0.05, 0.2, k)
+    freq = 2 * np.pi / rng.uniform(periods[0], periods[1], k)
     ph = rng.uniform(0, 2 * np.pi, k)
     s = np.zeros(P.shape[:-1])
     for i in range(k):
@@ -41,22 +59,23 @@ def texture(P, seed=7, k=24):
     return 128. + 95. * s / np.sqrt(k / 2.) / 2.
 
 
-def cast(origin, dirs):
-    """nearest plane hit along rays origin + lam dirs (camera 1 frame): lam [...], inf where none"""
+def cast(origin, dirs, planes=PLANES, patch=PATCH):
+    """nearest plane hit along rays origin + lam dirs (camera 1 frame): lam [...], inf where none.  `patch` bounds the
+    second plane (None: unbounded)."""
     best = np.full(dirs.shape[:-1], np.inf)
-    for i, (n, d) in enumerate(PLANES):
+    for i, (n, d) in enumerate(planes):
         den = dirs @ n
         with np.errstate(divide="ignore", invalid="ignore"):
             lam = (d - origin @ n) / den
         ok = (den != 0) & (lam > 0)
-        if i == 1:
+        if i == 1 and patch is not None:
             P = origin + lam[..., None] * dirs
-            ok &= (P[..., 0] >= PATCH[0]) & (P[..., 0] <= PATCH[1]) & (P[..., 1] >= PATCH[2]) & (P[..., 1] <= PATCH[3])
+            ok &= (P[..., 0] >= patch[0]) & (P[..., 0] <= patch[1]) & (P[..., 1] >= patch[2]) & (P[..., 1] <= patch[3])
         best = np.where(ok & (lam < best), lam, best)
     return best
 
 
-def render(cam, R, t, w, h, ss=3):
+def render(cam, R, t, w, h, ss=3, planes=PLANES, patch=PATCH, periods=PERIODS):
     """u8 image [h][w] of camera `cam` at pose (R, t) in camera 1's frame, ss x ss samples per pixel"""
     acc = np.zeros((h, w))
     offs = (np.arange(ss) + 0.5) / ss - 0.5
@@ -64,25 +83,40 @@ def render(cam, R, t, w, h, ss=3):
     for oy in offs:
         for ox in offs:
             d = reconstruct_np(cam, uu + ox, vv + oy) @ np.asarray(R).T
-            lam = cast(np.asarray(t), d)
+            lam = cast(np.asarray(t), d, planes, patch)
             P = np.asarray(t) + np.where(np.isfinite(lam), lam, 0.)[..., None] * d
-            acc += np.where(np.isfinite(lam), texture(P), 128.)
+            acc += np.where(np.isfinite(lam), texture(P, periods=periods), 128.)
     return np.clip(np.rint(acc / (ss * ss)), 0, 255).astype(np.uint8)
 
 
-def make_scene(rig, u_max=125, v_max=93, margin=15, scale=1):
-    """(img1, img2, true_range [y_max][x_max], xi12): the range along camera 1's ray of every depth pixel"""
-    xi = RIGS[rig]
+def true_range(cam1, u0, v0, x_max, y_max, scale=1, planes=PLANES, patch=PATCH):
+    """the range along camera 1's ray of every depth pixel (u0 + x scale, v0 + y scale): [y_max][x_max], 0 where no plane"""
+    yy, xx = np.mgrid[0:y_max, 0:x_max]
+    d = reconstruct_np(cam1, (xx * scale + u0).astype(float), (yy * scale + v0).astype(float))
+    lam = cast(np.zeros(3), d, planes, patch)
+    rng = lam * np.linalg.norm(d, axis=-1)
+    return np.where(np.isfinite(rng), rng, 0.)
+
+
+def make_scene(rig, u_max=125, v_max=93, margin=15, scale=1, cam1=CAM1, cam2=CAM2, planes=PLANES, patch=PATCH, periods=PERIODS):
+    """(img1, img2, true_range [y_max][x_max], xi12): the range along camera 1's ray of every depth pixel.  `rig` names an
+    entry of RIGS or is xi12 itself."""
+    xi = RIGS[rig] if isinstance(rig, str) else list(rig)
     R = np.array(stereo_ref.rotation_matrix(xi[3:], 1.)).reshape(3, 3)
-    img1 = render(CAM1, np.eye(3), np.zeros(3), u_max, v_max)
-    img2 = render(CAM2, R, np.array(xi[:3]), u_max, v_max)
+    img1 = render(cam1, np.eye(3), np.zeros(3), u_max, v_max, planes=planes, patch=patch, periods=periods)
+    img2 = render(cam2, R, np.array(xi[:3]), u_max, v_max, planes=planes, patch=patch, periods=periods)
     x_max = (u_max - 2 * margin) // scale + 1
     y_max = (v_max - 2 * margin) // scale + 1
-    yy, xx = np.mgrid[0:y_max, 0:x_max]
-    d = reconstruct_np(CAM1, (xx * scale + margin).astype(float), (yy * scale + margin).astype(float))
-    lam = cast(np.zeros(3), d)
-    rng = lam * np.linalg.norm(d, axis=-1)
-    return img1, img2, np.where(np.isfinite(rng), rng, 0.), xi
+    return img1, img2, true_range(cam1, margin, margin, x_max, y_max, scale, planes, patch), xi
+
+
+def make_strip(tex="fine", wall="steep"):
+    """(img1, img2, true_range over STRIP's grid, xi12) of the strip scene with one of STRIP's textures and walls"""
+    S = STRIP
+    planes = S["planes"][wall]
+    img1, img2, _, xi = make_scene(S["xi12"], S["u_max"], S["v_max"], cam1=S["cam1"], cam2=S["cam2"], planes=planes,
+                                   patch=None, periods=S["periods"][tex])
+    return img1, img2, true_range(S["cam1"], planes=planes, patch=None, **S["grid"]), xi
 
 
 def write_pgm(path, img):

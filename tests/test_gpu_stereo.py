@@ -1,11 +1,13 @@
 """Dense stereo on the GPU (vg_stereo_*, visgeom_amd.stereo) against the restatement (tests/stereo_ref.py): per-pixel
-geometry, curve cost, aggregation + winner and depth stage by stage, ground truth on three synthetic rigs, batch
-equivalence and a call whose cost volume passes 2^31 bytes."""
+geometry, curve cost, aggregation + winner and depth stage by stage, on the three small rigs (up to 48 disparities) and on
+the strip scene's cases (tests/stereo_strip.py: 66 ... 256 disparities, where an aggregation lane holds up to four of them);
+ground truth on the three rigs, batch equivalence and a call whose cost volume passes 2^31 bytes."""
 import numpy as np
 import pytest
 
 from tests import stereo_ref as sr
 from tests import stereo_scene
+from tests import stereo_strip as strip
 
 pytestmark = pytest.mark.gpu
 
@@ -69,14 +71,18 @@ COST_CASES = [dict(use_uv_cache=0, scales=[1]), dict(use_uv_cache=1, scales=[1])
               dict(use_uv_cache=1, scales=[4], desc_length=13, disp_max=24, salient_points_only=0)]
 
 
-@pytest.mark.parametrize("case", COST_CASES, ids=[str(i) for i in range(len(COST_CASES))])
-def test_curve_cost_aggregation_depth_bit_exact(torch, case):
-    rig = "sideways"
-    img1, img2, _, xi = scene(rig)
-    p = prm_of(rig, **case)
-    ref = sr.stereo(stereo_scene.CAM1, stereo_scene.CAM2, xi, sr.params(**p), img1, img2)
-    s = handle(rig, p, torch)
-    a, b = cuda(torch, img1, img2)
+def assert_depth_equal(got, ref):
+    """(depth, sigma, cost, disparity) of compute() against a restatement output"""
+    dep, sig, cst, disp = got
+    np.testing.assert_array_equal(disp, ref["disparity"])
+    np.testing.assert_array_equal(cst, ref["cost"])
+    for g, want in ((dep, ref["depth"]), (sig, ref["sigma"])):
+        np.testing.assert_array_equal(g == 0, want == 0)
+        np.testing.assert_allclose(g, want, rtol=1e-12, atol=0)
+
+
+def assert_stages_equal(s, a, b, ref):
+    """every stage of handle `s` on the pair (a, b) against a restatement output"""
     err, step, sal, skip = (t.cpu().numpy()[0] for t in s.curve_cost(a, b))
     np.testing.assert_array_equal(skip, ref["skip"])
     np.testing.assert_array_equal(step, ref["step"])
@@ -85,14 +91,68 @@ def test_curve_cost_aggregation_depth_bit_exact(torch, case):
     tot, disp = (t.cpu().numpy()[0] for t in s.aggregate(a, b))
     np.testing.assert_array_equal(tot, ref["total"])
     np.testing.assert_array_equal(disp, ref["disparity"])
-    dep, sig, cst, disp2 = (t.cpu().numpy() for t in s.compute(a, b))
+    assert_depth_equal([t.cpu().numpy() for t in s.compute(a, b)], ref)
+
+
+@pytest.mark.parametrize("case", COST_CASES, ids=[str(i) for i in range(len(COST_CASES))])
+def test_curve_cost_aggregation_depth_bit_exact(torch, case):
+    rig = "sideways"
+    img1, img2, _, xi = scene(rig)
+    p = prm_of(rig, **case)
+    ref = sr.stereo(stereo_scene.CAM1, stereo_scene.CAM2, xi, sr.params(**p), img1, img2)
+    s = handle(rig, p, torch)
+    assert_stages_equal(s, *cuda(torch, img1, img2), ref)
     s.close()
-    np.testing.assert_array_equal(disp2, ref["disparity"])
-    np.testing.assert_array_equal(cst, ref["cost"])
-    for got, want in ((dep, ref["depth"]), (sig, ref["sigma"])):
-        np.testing.assert_array_equal(got == 0, want == 0)
-        np.testing.assert_allclose(got, want, rtol=1e-12, atol=0)
     assert (ref["skip"] == 0).mean() > 0.3   # the case is not all skipped pixels
+
+
+def strip_handle(p, torch):
+    from visgeom_amd import stereo
+
+    return stereo.Stereo(strip.S["cam1"], strip.S["cam2"], strip.S["xi12"], stereo.make_params(**p))
+
+
+@pytest.mark.parametrize("name", [n for n in strip.CASES if n != "j"])
+def test_strip_stages_bit_exact(torch, name):
+    """Long disparity ranges: the aggregation slots q = 1, 2, 3, the neighbours across d = 63|64, 127|128, 191|192, the tail
+    guard d < D at 66 / 120 / 130 / 200 / 254, a winner at d >= 64; the 31-row descriptor (g), a jump cost that wraps at 8
+    bits (h), step_cost 0 and a tight error_max (i), one-line grids (k).  Each case first meets its conditions on the
+    restatement's output (tests/stereo_strip.py)."""
+    img1, img2, ref = strip.reference(name)
+    strip.check_conditions(name, ref)
+    s = strip_handle(strip.prm_of(name), torch)
+    assert_stages_equal(s, *cuda(torch, img1, img2), ref)
+    s.close()
+
+
+def test_strip_odd_pixel_count_single_and_batch(torch):
+    """Case j: 95 x 15 depth pixels at 130 disparities.  np (D + 3) is 1 past a multiple of 4 for one pair and 3 past it for
+    three, so where the aggregation entry keeps the winner in its own scratch (disparity NULL) that buffer starts 3 and 1
+    bytes behind the byte buffers.  Three distinct pairs, each against its restatement, singly and as a batch."""
+    from visgeom_amd import capi
+
+    p = strip.prm_of("j")
+    P, D = p["x_max"] * p["y_max"], p["disp_max"]
+    assert P % 2 == 1 and (P * (D + 3)) % 4 == 1 and (3 * P * (D + 3)) % 4 == 3
+    cases = [strip.reference("j", w) for w in strip.J_BATCH]
+    strip.check_conditions("j", cases[0][2])
+    for _, _, ref in cases:
+        assert ref["skip"].mean() <= 0.05 and (ref["disparity"] >= 0).mean() > 0.5
+    s = strip_handle(p, torch)
+    ta, tb = cuda(torch, np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]))
+    assert_stages_equal(s, ta[0], tb[0], cases[0][2])
+    tot, disp = (t.cpu().numpy() for t in s.aggregate(ta, tb))
+    batch = [t.cpu().numpy() for t in s.compute(ta, tb)]
+    for i, (_, _, ref) in enumerate(cases):
+        np.testing.assert_array_equal(tot[i], ref["total"])
+        np.testing.assert_array_equal(disp[i], ref["disparity"])
+        assert_depth_equal([t[i] for t in batch], ref)
+        assert_depth_equal([t.cpu().numpy() for t in s.compute(ta[i], tb[i])], ref)
+    for n in (1, 3):   # the winner in the entry's own scratch: the sums must not change
+        own = torch.empty((n, p["y_max"], p["x_max"], D), dtype=torch.int32, device=ta.device)
+        capi.check(capi.load().vg_stereo_aggregate(s._h, n, ta.data_ptr(), tb.data_ptr(), own.data_ptr(), None))   # the first n
+        np.testing.assert_array_equal(own.cpu().numpy(), tot[:n])
+    s.close()
 
 
 @pytest.mark.parametrize("rig", ["sideways", "vertical", "forward"])
@@ -114,9 +174,8 @@ def test_ground_truth(torch, rig):
         assert (g[..., 4] & sr.TOO_CLOSE).any() and (g[..., 5] & sr.INVERTED).any()
 
 
-def _pairs(n, seed=3):
-    """n distinct pairs: the sideways scene with pixel noise and shifts"""
-    img1, img2, _, _ = scene("sideways")
+def _pairs(n, img1, img2, seed=3):
+    """n distinct pairs: a scene's pair with pixel noise and shifts"""
     rng = np.random.default_rng(seed)
     a = np.empty((n,) + img1.shape, np.uint8)
     b = np.empty_like(a)
@@ -129,7 +188,7 @@ def _pairs(n, seed=3):
 def test_batch_of_8_equals_single_calls(torch):
     p = prm_of("sideways", use_uv_cache=1)
     s = handle("sideways", p, torch)
-    a, b = _pairs(8)
+    a, b = _pairs(8, *scene("sideways")[:2])
     ta, tb = cuda(torch, a, b)
     batch = [t.cpu().numpy() for t in s.compute(ta, tb)]
     for i in range(8):
@@ -140,14 +199,19 @@ def test_batch_of_8_equals_single_calls(torch):
 
 
 def test_call_past_2_31_bytes_is_chunked_and_equals_its_parts(torch):
-    p = prm_of("sideways", disp_max=256, use_uv_cache=1)
-    s = handle("sideways", p, torch)
+    """On the strip scene (96 x 40 depth pixels over rows 4 ... 43), where 256 disparities are not all skipped pixels: the
+    eight parts have winners on more than half of their pixels, some of them in the upper slots"""
+    p = dict(strip.BASE, disp_max=256, use_uv_cache=1, v0=4, y_max=40)
+    s = strip_handle(p, torch)
     per_pair = s.x_max * s.y_max * 256
     n = (1 << 31) // per_pair + 8
     assert n * per_pair > 1 << 31 and s.chunk() < n
-    a, b = _pairs(8)
+    a, b = _pairs(8, *strip.images("steep", "fine")[:2])
     ta, tb = cuda(torch, a, b)
     parts = [t.cpu().numpy() for t in s.compute(ta, tb)]
+    disp = parts[3]
+    for i in range(8):
+        assert (disp[i] >= 0).mean() > 0.5 and (disp[i] >= 128).any(), i
     idx = torch.arange(n, device=ta.device) % 8
     big = s.compute(ta[idx].contiguous(), tb[idx].contiguous())
     for got_t, want in zip(big, parts):

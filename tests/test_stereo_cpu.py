@@ -1,7 +1,8 @@
 """Dense stereo without a GPU: the section 9 entries are declared, exported from both libraries and bound; vg_stereo_create
 checks its arguments before touching HIP; the host curve walk equals the restatement (tests/stereo_ref.py) step for step;
 hand values of compareDescriptor, fillGaps and regDiv; the curve table; the restatement recovers the range of a synthetic
-sideways scene."""
+sideways scene; the three rigs' images are what they were before the scene's world became arguments; every case on the strip
+scene meets the conditions under which the GPU tests' comparison with it says something."""
 import ctypes
 import math
 import os
@@ -13,6 +14,7 @@ import pytest
 
 from tests import stereo_ref as sr
 from tests import stereo_scene
+from tests import stereo_strip
 
 ENTRIES = ("vg_stereo_params_default", "vg_stereo_create", "vg_stereo_destroy", "vg_stereo_size", "vg_stereo_chunk",
            "vg_stereo_compute", "vg_stereo_geometry", "vg_stereo_curve_cost", "vg_stereo_aggregate", "vg_stereo_curve_walk")
@@ -207,3 +209,49 @@ def test_restatement_recovers_sideways_range():
     assert m.mean() >= SIDEWAYS_VALID
     assert np.median(np.abs(d[m] - rng[m]) / rng[m]) <= SIDEWAYS_MEDIAN_REL
 
+
+
+# SHA-256 of (img1, img2, true range) of make_scene(rig), recorded before planes, patch, texture band and cameras became
+# arguments of cast, texture, render and make_scene
+RIG_IMAGES = {
+    "sideways": ("ec5cb2e603ec43f05e9861988f954178a4448037a96b28011852f22ac3983354",
+                 "18b5e33ef53602f4a5cd08d990fe2355a07c492a0c82e503da20f8527d82d95f",
+                 "d01efb4002978e5b0901898ad5e3237efe1470b4dd67c1cbb14066b7f16bebed"),
+    "vertical": ("ec5cb2e603ec43f05e9861988f954178a4448037a96b28011852f22ac3983354",
+                 "04db59b12361dfaafa938b5f92bff70d2e4240688ae03eaa12b1b515485f8901",
+                 "d01efb4002978e5b0901898ad5e3237efe1470b4dd67c1cbb14066b7f16bebed"),
+    "forward": ("ec5cb2e603ec43f05e9861988f954178a4448037a96b28011852f22ac3983354",
+                "f38746258ee58cd899b6898c7d6a20d915015ef4839b496a6e735f7cd8482cdd",
+                "d01efb4002978e5b0901898ad5e3237efe1470b4dd67c1cbb14066b7f16bebed"),
+}
+
+
+@pytest.mark.parametrize("rig", sorted(RIG_IMAGES))
+def test_rig_images_are_unchanged(rig):
+    import hashlib
+
+    img1, img2, rng, xi = stereo_scene.make_scene(rig)
+    assert img1.dtype == np.uint8 and img1.shape == (93, 125) and rng.dtype == np.float64 and rng.shape == (64, 96)
+    assert (int(img1.sum()), int(img2.sum())) == {"sideways": (1491971, 1489317), "vertical": (1491971, 1489889),
+                                                  "forward": (1491971, 1494707)}[rig]
+    got = tuple(hashlib.sha256(np.ascontiguousarray(x).tobytes()).hexdigest() for x in (img1, img2, rng))
+    assert got == RIG_IMAGES[rig]
+    assert xi == stereo_scene.RIGS[rig]
+
+
+@pytest.mark.parametrize("name", list(stereo_strip.CASES))
+def test_strip_case_meets_its_conditions(name):
+    """a scene change that empties a quarter of the disparity range, or a descriptor step, fails here before it reaches a GPU"""
+    stereo_strip.check_conditions(name, stereo_strip.reference(name)[2])
+
+
+def test_strip_batch_pairs_are_distinct_and_not_skipped():
+    g = stereo_strip.S["grid"]
+    win = (slice(g["v0"], g["v0"] + g["y_max"]), slice(g["u0"], g["u0"] + g["x_max"]))   # the depth grid in image 1
+    pairs = [stereo_strip.images(*w)[:2] for w in stereo_strip.J_BATCH]
+    for i in range(3):
+        for j in range(i):
+            assert (pairs[i][0][win] != pairs[j][0][win]).mean() > 0.5
+    for w in stereo_strip.J_BATCH[1:]:
+        ref = stereo_strip.reference("j", w)[2]
+        assert ref["skip"].mean() <= 0.05 and (ref["disparity"] >= 0).mean() > 0.5

@@ -264,14 +264,15 @@ int vg_stereo_aggregate(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, cons
     VG_HIP(hipSetDevice(s->device));
     // scratch for what the caller does not supply: the error volume, step / salient / skip, and the winner if disparity is NULL
     const int64_t np = n_pairs * s->P;
-    if (const int rc = ensure_scratch(s, np * (s->prm.disp_max + 3) + (disparity ? 0 : np * 4))) return rc;
+    const int64_t bytes = np * (s->prm.disp_max + 3), pad = (4 - bytes % 4) % 4;   // pad: aligns the winner behind the byte buffers
+    if (const int rc = ensure_scratch(s, bytes + (disparity ? 0 : pad + np * 4))) return rc;
     Bufs b;
     b.err = static_cast<uint8_t *>(s->d_scratch.get());
     b.step = b.err + np * s->prm.disp_max;
     b.sal = b.step + np;
     b.skip = b.sal + np;
     b.sum = total;
-    b.disp = disparity ? disparity : reinterpret_cast<int32_t *>(b.skip + np + (4 - (np * (s->prm.disp_max + 3)) % 4) % 4);
+    b.disp = disparity ? disparity : reinterpret_cast<int32_t *>(b.skip + np + pad);
     launch_cost(s, n_pairs, img1, img2, b);
     launch_agg(s, n_pairs, b, true);
     VG_HIP(hipGetLastError());
