@@ -2,19 +2,20 @@
 (include/localization/scale_space.h), ScalePhotometric::initPhotometricData and computePose (src/localization/photometric.cpp:46-157),
 PhotometricCostFunction::Evaluate with lossFunction / getUMapgin / getVMapgin (src/localization/local_cost_functions.cpp:35-210),
 CameraJacobian::dfdxi (include/projection/jacobian.h:54-115), the localization OdometryPrior (local_cost_functions.cpp:393-493),
-Ceres' BiCubicInterpolator over the reference's clamping Grid2D (include/ceres.h:48-69), and a trust-region Levenberg-Marquardt
-under the rules DESIGN.md section 5.13 names.  Written from reading the reference, with the deviations of DESIGN.md section 9
+Ceres' BiCubicInterpolator over the reference's clamping Grid2D (include/ceres.h:48-69), and the trust-region Levenberg-Marquardt
+of tests/lm6_ref.py (the rules DESIGN.md section 5.13 names).  Written from reading the reference, with the deviations of DESIGN.md section 9
 ("Photometric localization"); FP64 throughout except the pyramid, which is float32 like the reference's Mat32f."""
 import math
 
 import numpy as np
 
+from tests import lm6_ref
+from tests.lm6_ref import (DIAG_MAX, DIAG_MIN, FTOL, GTOL, MAX_RADIUS, MIN_RADIUS, MIN_REL_DECREASE, PTOL, RADIUS0,  # noqa: F401
+                           TERM_FUNCTION, TERM_GRADIENT, TERM_NO_CONVERGENCE, TERM_PARAMETER, TERM_RADIUS)
+
 GRAD_THRESH, DIST_MAX, GREY_MAX, LOSS_FACTOR, MIN_DEPTH, MARGIN_PIXELS = 250., 50., 240., 3., 0.25, 50.
 COORD_LIMIT = 16777216.
-# Ceres' defaults (the reference sets only the iteration cap) under the calibration LM's rules
-MAX_ITERATIONS, FTOL, GTOL, PTOL, RADIUS0, MAX_RADIUS, MIN_RADIUS = 150, 1e-6, 1e-10, 1e-8, 1e4, 1e16, 1e-32
-MIN_REL_DECREASE, DIAG_MIN, DIAG_MAX = 1e-3, 1e-6, 1e32
-TERM_FUNCTION, TERM_GRADIENT, TERM_PARAMETER, TERM_NO_CONVERGENCE, TERM_RADIUS = 0, 1, 2, 3, 4
+MAX_ITERATIONS = 150   # the reference sets only the iteration cap; Ceres' defaults and the rule are lm6_ref's
 
 
 # ---- geometry (geometry_core.h, quaternion.h, transformation.h) ----------------------------------------------------
@@ -343,50 +344,8 @@ class Localizer:
         return 0.5 * float(r @ r)
 
     def solve_scale(self, scale_idx, xi, target=0, prior=None):
-        """the trust-region loop at one scale under the calibration LM's rules: (xi, dict(iterations, initial_cost,
-        final_cost, termination))"""
-        x = np.asarray(xi, float).copy()
-        cost, JtJ, g = self.normal(scale_idx, x, target, prior)
-        rep = {"iterations": 0, "initial_cost": cost, "termination": TERM_NO_CONVERGENCE}
-        radius, dec = RADIUS0, 2.
-        while rep["iterations"] < MAX_ITERATIONS:
-            rep["iterations"] += 1
-            mu = 1. / radius
-            D = np.clip(np.diag(JtJ), DIAG_MIN, DIAG_MAX)
-            step_ok = True
-            try:
-                L = np.linalg.cholesky(JtJ + mu * np.diag(D))
-                dx = -np.linalg.solve(L.T, np.linalg.solve(L, g))
-                step_ok = bool(np.isfinite(dx).all())
-            except np.linalg.LinAlgError:
-                step_ok = False
-            success = False
-            if step_ok:
-                cost_c, JtJ_c, g_c = self.normal(scale_idx, x + dx, target, prior)
-                model_change = 0.5 * (mu * float(D @ (dx * dx)) - float(g @ dx))
-                rho = (cost - cost_c) / model_change if model_change > 0. else -1.
-                if np.abs(g).max() <= GTOL:
-                    rep["termination"] = TERM_GRADIENT
-                    break
-                if math.sqrt(float(dx @ dx)) <= PTOL * (math.sqrt(float(x @ x)) + PTOL):
-                    rep["termination"] = TERM_PARAMETER
-                    break
-                if model_change > 0. and math.isfinite(cost_c) and abs(cost - cost_c) <= FTOL * cost:
-                    rep["termination"] = TERM_FUNCTION
-                    break
-                success = math.isfinite(cost_c) and rho > MIN_REL_DECREASE
-            if success:
-                x, cost, JtJ, g = x + dx, cost_c, JtJ_c, g_c
-                radius = min(radius / max(1. - (2. * rho - 1.) ** 3, 1. / 3.), MAX_RADIUS)
-                dec = 2.
-            else:
-                radius /= dec
-                dec *= 2.
-                if radius < MIN_RADIUS:
-                    rep["termination"] = TERM_RADIUS
-                    break
-        rep["final_cost"] = cost
-        return x, rep
+        """the trust-region loop of lm6_ref at one scale: (xi, dict(iterations, initial_cost, final_cost, termination))"""
+        return lm6_ref.solve(lambda x: self.normal(scale_idx, x, target, prior), xi, MAX_ITERATIONS)
 
     def compute_pose(self, xi, target=0, xi_prior=None):
         """computePose: coarsest scale first; (xi, [report per scale, index = scale])"""

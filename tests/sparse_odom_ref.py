@@ -1,7 +1,7 @@
 """Plain numpy restatement of the reference's sparse odometry for the sparse odometry tests: harrisCorners / descriptors
 (src/localization/sparse_odom.cpp:161-238) on the exact integer response include/visgeom_amd.h section 13 defines, the
 brute-force L1 matching with cross-check and threshold (:266-300), computeTransfSparse (:440-469) as the trust-region
-Levenberg-Marquardt of tests/photometric_ref.py on the CPU checker's SparseReprojectCost plus photometric_ref's OdometryPrior,
+Levenberg-Marquardt of tests/lm6_ref.py on the CPU checker's SparseReprojectCost plus photometric_ref's OdometryPrior,
 the scoring and selection of ransacNPoints (:511-606), the refinement of feedData (:336-387) and feedData itself.  Written
 from reading the reference, with the deviations of DESIGN.md section 9 ("Sparse visual odometry")."""
 import math
@@ -9,6 +9,7 @@ import math
 import numpy as np
 
 from oracle import vgo
+from tests import lm6_ref
 from tests import photometric_ref as pr
 
 MAX_FEATURES, MATCH_THRESHOLD, NUM_RANSAC_POINTS, RANSAC_ITERATIONS, INLIER_THRESHOLD = 500, 2500., 2, 200, 1.
@@ -122,52 +123,11 @@ def normal(cam, xbc, x1, x2, p2, size, prior, xi):
 
 
 def solve(cam, xbc, x1, x2, p2, size, xi_odom, max_iterations=MAX_LM_ITERATIONS, ftol=FTOL, ptol=PTOL, prior=PRIOR):
-    """the trust-region loop of photometric_ref.Localizer.solve_scale on this problem, from xi_odom: (xi, report dict)"""
+    """the trust-region loop of lm6_ref on this problem, from xi_odom: (xi, report dict)"""
     pri = pr.OdometryPrior(xi_odom, *prior)
     x1, x2, p2, size = (np.ascontiguousarray(a, dtype=np.float64) for a in (x1, x2, p2, size))
     f = lambda x: normal(cam, xbc, x1, x2, p2, size, pri, x)
-    x = np.asarray(xi_odom, float).copy()
-    cost, JtJ, g = f(x)
-    rep = {"iterations": 0, "initial_cost": cost, "termination": pr.TERM_NO_CONVERGENCE}
-    radius, dec = pr.RADIUS0, 2.
-    while rep["iterations"] < max_iterations:
-        rep["iterations"] += 1
-        mu = 1. / radius
-        D = np.clip(np.diag(JtJ), pr.DIAG_MIN, pr.DIAG_MAX)
-        step_ok = True
-        try:
-            L = np.linalg.cholesky(JtJ + mu * np.diag(D))
-            dx = -np.linalg.solve(L.T, np.linalg.solve(L, g))
-            step_ok = bool(np.isfinite(dx).all())
-        except np.linalg.LinAlgError:
-            step_ok = False
-        success = False
-        if step_ok:
-            cost_c, JtJ_c, g_c = f(x + dx)
-            model_change = 0.5 * (mu * float(D @ (dx * dx)) - float(g @ dx))
-            rho = (cost - cost_c) / model_change if model_change > 0. else -1.
-            if np.abs(g).max() <= GTOL:
-                rep["termination"] = pr.TERM_GRADIENT
-                break
-            if math.sqrt(float(dx @ dx)) <= ptol * (math.sqrt(float(x @ x)) + ptol):
-                rep["termination"] = pr.TERM_PARAMETER
-                break
-            if model_change > 0. and math.isfinite(cost_c) and abs(cost - cost_c) <= ftol * cost:
-                rep["termination"] = pr.TERM_FUNCTION
-                break
-            success = math.isfinite(cost_c) and rho > pr.MIN_REL_DECREASE
-        if success:
-            x, cost, JtJ, g = x + dx, cost_c, JtJ_c, g_c
-            radius = min(radius / max(1. - (2. * rho - 1.) ** 3, 1. / 3.), pr.MAX_RADIUS)
-            dec = 2.
-        else:
-            radius /= dec
-            dec *= 2.
-            if radius < pr.MIN_RADIUS:
-                rep["termination"] = pr.TERM_RADIUS
-                break
-    rep["final_cost"] = cost
-    return x, rep
+    return lm6_ref.solve(f, xi_odom, max_iterations, ftol, GTOL, ptol)
 
 
 # ---- scoring ---------------------------------------------------------------------------------------------------------

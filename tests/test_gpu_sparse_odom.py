@@ -205,6 +205,30 @@ def test_solve_block_of_95(torch, points):
     assert rep[0, 2] < rep[0, 1]
 
 
+def test_solve_without_iterations(torch, points):
+    """max_lm_iterations = 0: the start is evaluated and returned"""
+    s = sc.points_set()
+    idx = torch.from_numpy(s["samples2"][0].astype(np.int64)).cuda()
+    args = [points[k][idx].contiguous() for k in ("x1", "x2", "p2", "size")]
+    xi, rep = make(torch, max_lm_iterations=0).solve([0, 2], *args, s["xi_odom"])
+    assert np.array_equal(xi[0], np.asarray(s["xi_odom"], float))
+    assert rep[0, 0] == 0 and rep[0, 2] == rep[0, 1] > 0. and rep[0, 3] == sr.pr.TERM_NO_CONVERGENCE
+
+
+def test_solve_empty_block_between_two(torch, points):
+    """offsets [0, 2, 2, 4]: the middle block has the prior alone, and its neighbours do not notice it"""
+    s = sc.points_set()
+    idx = torch.from_numpy(s["samples2"][:2].ravel().astype(np.int64)).cuda()
+    args = [points[k][idx].contiguous() for k in ("x1", "x2", "p2", "size")]
+    odo = make(torch)
+    xi, rep = odo.solve([0, 2, 2, 4], *args, s["xi_odom"])
+    ref, ref_rep = sr.solve(sc.CAM, sc.XI_BASE_CAM, np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 2)), np.zeros(0), s["xi_odom"])
+    assert np.array_equal(xi[1], ref) and rep[1, 0] == ref_rep["iterations"] and rep[1, 3] == ref_rep["termination"]
+    for b, block in ((0, 0), (1, 2)):
+        one, rep1 = odo.solve([0, 2], *[a[2 * b:2 * b + 2].contiguous() for a in args], s["xi_odom"])
+        assert np.array_equal(one[0], xi[block]) and np.array_equal(rep1[0], rep[block])
+
+
 def test_ransac(torch, points):
     s, r = sc.points_set(), sc.reference_ransac(2)
     xi, mask, rep = make(torch).ransac(points["x1"], points["x2"], points["p2"], points["size"], s["xi_odom"], s["samples2"])

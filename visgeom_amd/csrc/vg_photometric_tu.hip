@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "vg_internal.hpp"
+#include "vg_lm6.hpp"
 #include "vg_local.hpp"
 #include "vg_motion_prior.hpp"
 #include "vg_photometric.hpp"
@@ -56,10 +57,8 @@ using vgsh::blocks_of;
 using vgth::Array6d;
 constexpr int64_t kMaxItems = 65535;   // poses and targets ride on gridDim.y
 constexpr int kMaxIterations = 150;    // photometric.cpp:150
-// Ceres' defaults, which the reference leaves in place (photometric.cpp:148-150), under the rules of the calibration LM
-// (lm_accept of vg_solver_device.hpp: step quality, radius update, the three tolerances)
-constexpr double kFtol = 1e-6, kGtol = 1e-10, kPtol = 1e-8, kRadius0 = 1e4, kMaxRadius = 1e16, kMinRadius = 1e-32;
-constexpr double kMinRelDecrease = 1e-3, kDiagMin = 1e-6, kDiagMax = 1e32;
+// Ceres' defaults, which the reference leaves in place (photometric.cpp:148-150), under the rule of vg_lm6.hpp
+constexpr vglm6::Rule kRule = vglm6::ceres_defaults(kMaxIterations);
 
 int64_t level_pixels(const vg_photometric *s, int i) { return (int64_t)s->w[i] * s->h[i]; }
 
@@ -159,103 +158,12 @@ using vgmp::add_prior;
 using vgmp::MotionPrior;
 MotionPrior make_prior(const double *xi_odom) { return vgmp::make_prior(xi_odom, 0.03, 0.03, 0.01, 0.01); }
 
+// one pose of compute_pose under the rule of vg_lm6.hpp: its state, the step in flight and the 28 sums at s.x
 struct LmPose {
-    double x[6], xc[6], dx[6], G[vgp::kSums];
-    double cost = 0., radius = kRadius0, decrease_factor = 2., mu = 0., gdx = 0., ddx = 0., dx2 = 0., x2 = 0., gmax = 0.;
-    int iterations = 0, term = VG_TERM_NO_CONVERGENCE;
-    bool done = false, step_ok = false;
+    vglm6::State s{};
+    vglm6::Step st{};
+    double G[vgp::kSums];
 };
-
-// (J^T J + mu D) dx = -J^T r, D = clamp(diag(J^T J)): the damped 6 x 6 solve of vg_pose_lm.hpp, on the host
-void lm_step(LmPose &p)
-{
-    double A[6][6], Lc[6][6], g[6], D[6], y[6];
-    int q = 0;
-    for (int i = 0; i < 6; i++)
-        for (int j = i; j < 6; j++, q++) A[i][j] = A[j][i] = p.G[q];
-    p.mu = 1. / p.radius;
-    for (int i = 0; i < 6; i++) {
-        g[i] = p.G[21 + i];
-        D[i] = A[i][i] < kDiagMin ? kDiagMin : (A[i][i] > kDiagMax ? kDiagMax : A[i][i]);
-        A[i][i] += p.mu * D[i];
-    }
-    p.step_ok = true;
-    for (int r = 0; r < 6; r++)
-        for (int c = 0; c <= r; c++) {
-            double s = A[r][c];
-            for (int k = 0; k < c; k++) s -= Lc[r][k] * Lc[c][k];
-            if (r == c) {
-                if (!(s > 0.)) {
-                    p.step_ok = false;
-                    s = 1.;
-                }
-                Lc[r][r] = std::sqrt(s);
-            } else {
-                Lc[r][c] = s / Lc[c][c];
-            }
-        }
-    for (int r = 0; r < 6; r++) {
-        double s = g[r];
-        for (int k = 0; k < r; k++) s -= Lc[r][k] * y[k];
-        y[r] = s / Lc[r][r];
-    }
-    for (int r = 5; r >= 0; r--) {
-        double s = y[r];
-        for (int k = r + 1; k < 6; k++) s -= Lc[k][r] * p.dx[k];
-        p.dx[r] = s / Lc[r][r];
-    }
-    p.gdx = p.ddx = p.dx2 = p.x2 = p.gmax = 0.;
-    for (int k = 0; k < 6; k++) {
-        p.dx[k] = -p.dx[k];
-        p.xc[k] = p.x[k] + p.dx[k];
-        p.gdx += g[k] * p.dx[k];
-        p.ddx += D[k] * p.dx[k] * p.dx[k];
-        p.dx2 += p.dx[k] * p.dx[k];
-        p.x2 += p.x[k] * p.x[k];
-        p.gmax = std::fmax(p.gmax, std::fabs(g[k]));
-        if (!std::isfinite(p.xc[k])) p.step_ok = false;
-    }
-}
-
-// lm_accept of vg_solver_device.hpp for one pose: Gc the sums at the candidate
-void lm_accept(LmPose &p, const double *Gc)
-{
-    p.iterations++;
-    const double cost_c = Gc[27];
-    double rho = 0.;
-    if (p.step_ok) {
-        const double model_change = 0.5 * (p.mu * p.ddx - p.gdx);
-        const double cost_change = p.cost - cost_c;
-        rho = model_change > 0. ? cost_change / model_change : -1.;
-        if (p.gmax <= kGtol) {
-            p.term = VG_TERM_CONVERGENCE_GRADIENT;
-            p.done = true;
-        } else if (std::sqrt(p.dx2) <= kPtol * (std::sqrt(p.x2) + kPtol)) {
-            p.term = VG_TERM_CONVERGENCE_PARAMETER;
-            p.done = true;
-        } else if (model_change > 0. && std::isfinite(cost_c) && std::fabs(p.cost - cost_c) <= kFtol * p.cost) {
-            p.term = VG_TERM_CONVERGENCE_FUNCTION;
-            p.done = true;
-        }
-    }
-    if (p.done) return;
-    if (p.step_ok && std::isfinite(cost_c) && rho > kMinRelDecrease) {
-        for (int k = 0; k < 6; k++) p.x[k] = p.xc[k];
-        std::memcpy(p.G, Gc, sizeof p.G);
-        p.cost = cost_c;
-        const double t = 2. * rho - 1.;
-        p.radius = std::fmin(p.radius / std::fmax(1. - t * t * t, 1. / 3.), kMaxRadius);
-        p.decrease_factor = 2.;
-    } else {
-        p.radius /= p.decrease_factor;
-        p.decrease_factor *= 2.;
-        if (p.radius < kMinRadius) {
-            p.term = VG_TERM_RADIUS_TOO_SMALL;
-            p.done = true;
-        }
-    }
-    if (p.iterations >= kMaxIterations) p.done = true;
-}
 
 // ---- mutual information ------------------------------------------------------------------------------------------------
 
@@ -585,55 +493,50 @@ int vg_photometric_compute_pose(vg_photometric *s, int64_t n, const double *xi_s
     std::vector<LmPose> P((size_t)n);
     std::vector<MotionPrior> prior;
     for (int64_t k = 0; k < n; k++) {
-        std::memcpy(P[k].x, xi_start + 6 * k, sizeof(double) * 6);
+        std::memcpy(P[k].s.x, xi_start + 6 * k, sizeof(double) * 6);
         if (xi_prior) prior.push_back(make_prior(xi_prior + 6 * k));
     }
     for (int scale = s->levels - 1; scale >= 0; scale--) {
-        for (int64_t k = 0; k < n; k++) {
-            const double x[6] = {P[k].x[0], P[k].x[1], P[k].x[2], P[k].x[3], P[k].x[4], P[k].x[5]};
-            P[k] = LmPose();
-            std::memcpy(P[k].x, x, sizeof x);
-            make_frame(s, P[k].x, target[k], true, s->h_frames.get()[k]);
-        }
+        for (int64_t k = 0; k < n; k++) make_frame(s, P[k].s.x, target[k], true, s->h_frames.get()[k]);
         if (const int rc = run_cost(s, scale, n, nullptr, nullptr, true)) return rc;
         for (int64_t k = 0; k < n; k++) {
             std::memcpy(P[k].G, s->h_sums.get() + k * vgp::kSums, sizeof P[k].G);
-            if (xi_prior) add_prior(prior[k], P[k].x, P[k].G);
-            P[k].cost = P[k].G[27];
-            if (report) report[(k * s->levels + scale) * 4 + 1] = P[k].cost;
+            if (xi_prior) add_prior(prior[k], P[k].s.x, P[k].G);
+            vglm6::start(kRule, P[k].s, P[k].G[27]);
+            if (report) report[(k * s->levels + scale) * 4 + 1] = P[k].s.cost;
         }
         for (;;) {
             bool any = false, launch = false;
             for (int64_t k = 0; k < n; k++) {
-                if (!P[k].done) {
-                    lm_step(P[k]);
+                if (!P[k].s.done) {
+                    vglm6::step(kRule, P[k].s, P[k].G, P[k].st);
                     any = true;
                 }
-                const bool active = !P[k].done && P[k].step_ok;   // a pose that has converged is masked
-                make_frame(s, active ? P[k].xc : P[k].x, target[k], active, s->h_frames.get()[k]);
+                const bool active = !P[k].s.done && P[k].st.ok;   // a pose that has converged is masked
+                make_frame(s, active ? P[k].st.xc : P[k].s.x, target[k], active, s->h_frames.get()[k]);
                 launch = launch || active;
             }
             if (!any) break;
             if (launch)
                 if (const int rc = run_cost(s, scale, n, nullptr, nullptr, true)) return rc;
             for (int64_t k = 0; k < n; k++) {
-                if (P[k].done) continue;
+                if (P[k].s.done) continue;
                 double Gc[vgp::kSums] = {0.};
-                if (P[k].step_ok) {
+                if (P[k].st.ok) {
                     std::memcpy(Gc, s->h_sums.get() + k * vgp::kSums, sizeof Gc);
-                    if (xi_prior) add_prior(prior[k], P[k].xc, Gc);
+                    if (xi_prior) add_prior(prior[k], P[k].st.xc, Gc);
                 }
-                lm_accept(P[k], Gc);
+                if (vglm6::accept(kRule, P[k].s, P[k].st, Gc[27])) std::memcpy(P[k].G, Gc, sizeof Gc);
             }
         }
         for (int64_t k = 0; report && k < n; k++) {
             double *r = report + (k * s->levels + scale) * 4;
-            r[0] = P[k].iterations;
-            r[2] = P[k].cost;
-            r[3] = P[k].term;
+            r[0] = P[k].s.iterations;
+            r[2] = P[k].s.cost;
+            r[3] = P[k].s.term;
         }
     }
-    for (int64_t k = 0; k < n; k++) std::memcpy(xi_out + 6 * k, P[k].x, sizeof(double) * 6);
+    for (int64_t k = 0; k < n; k++) std::memcpy(xi_out + 6 * k, P[k].s.x, sizeof(double) * 6);
     return VG_OK;
 }
 

@@ -14,6 +14,7 @@
 
 #include <cstdint>
 
+#include "vg_lm6.hpp"
 #include "vg_local.hpp"
 #include "vg_motion_prior.hpp"
 #include "vg_stereo_device.hpp"
@@ -357,14 +358,13 @@ struct SolveArgs {
     const int32_t *index;     // [offsets[n_blocks]] the point of every block entry, or NULL: entry e is point e
     const int64_t *offsets;   // [n_blocks + 1]
     double *out;              // [n_blocks][kSolveOut]
-    int max_iter;
-    double ftol, gtol, ptol, radius0, max_radius, min_radius, min_rel_decrease, dmin, dmax;
+    vglm6::Rule rule;         // the iteration cap and the trust-region constants
 };
 
 // One wave per problem: the block's frame by lane 0, the points strided over the lanes (residual pair and rows from
 // vg_local.hpp's sparse_point_eval), the 28 sums of the lanes added in lane order, the prior added, and the damped 6 x 6
-// Cholesky step with its acceptance executed by every lane on the same numbers.  What a problem computes does not depend on
-// the launch it is part of.  The rules are those of the photometric solve (lm_step / lm_accept of vg_photometric_tu.hip).
+// Cholesky step with its acceptance (vg_lm6.hpp, the rule the photometric solve runs on the host) executed by every lane on the
+// same numbers.  What a problem computes does not depend on the launch it is part of.
 __global__ __launch_bounds__(64) void solve_kernel(SolveArgs a)
 {
     using d2 = HIP_vector_type<double, 2>;
@@ -424,108 +424,30 @@ __global__ __launch_bounds__(64) void solve_kernel(SolveArgs a)
         __syncthreads();
     };
 
-    double x[6];
+    vglm6::State S;
 #pragma unroll
-    for (int k = 0; k < 6; k++) x[k] = C[kConstOdom + k];
-    int cur = 0, iterations = 0, term = VG_TERM_NO_CONVERGENCE;
-    evaluate(x, Gs[0]);
-    double cost = Gs[0][27], radius = a.radius0, decrease_factor = 2.;
-    const double initial_cost = cost;
-    bool done = a.max_iter < 1;
-    while (!done) {
-        const double *G = Gs[cur];
-        double A[6][6], Lc[6][6], g[6], D[6], y[6], dx[6], xc[6];
-        int q = 0;
-        for (int i = 0; i < 6; i++)
-            for (int j = i; j < 6; j++, q++) A[i][j] = A[j][i] = G[q];
-        const double mu = 1. / radius;
-        for (int i = 0; i < 6; i++) {
-            g[i] = G[21 + i];
-            D[i] = A[i][i] < a.dmin ? a.dmin : (A[i][i] > a.dmax ? a.dmax : A[i][i]);
-            A[i][i] += mu * D[i];
-        }
-        bool step_ok = true;
-        for (int r = 0; r < 6; r++)
-            for (int c = 0; c <= r; c++) {
-                double s = A[r][c];
-                for (int k = 0; k < c; k++) s -= Lc[r][k] * Lc[c][k];
-                if (r == c) {
-                    if (!(s > 0.)) {
-                        step_ok = false;
-                        s = 1.;
-                    }
-                    Lc[r][r] = sqrt(s);
-                } else {
-                    Lc[r][c] = s / Lc[c][c];
-                }
-            }
-        for (int r = 0; r < 6; r++) {
-            double s = g[r];
-            for (int k = 0; k < r; k++) s -= Lc[r][k] * y[k];
-            y[r] = s / Lc[r][r];
-        }
-        for (int r = 5; r >= 0; r--) {
-            double s = y[r];
-            for (int k = r + 1; k < 6; k++) s -= Lc[k][r] * dx[k];
-            dx[r] = s / Lc[r][r];
-        }
-        double gdx = 0., ddx = 0., dx2 = 0., x2 = 0., gmax = 0.;
-        for (int k = 0; k < 6; k++) {
-            dx[k] = -dx[k];
-            xc[k] = x[k] + dx[k];
-            gdx += g[k] * dx[k];
-            ddx += D[k] * dx[k] * dx[k];
-            dx2 += dx[k] * dx[k];
-            x2 += x[k] * x[k];
-            gmax = fmax(gmax, fabs(g[k]));
-            if (!isfinite(xc[k])) step_ok = false;
-        }
+    for (int k = 0; k < 6; k++) S.x[k] = C[kConstOdom + k];
+    int cur = 0;
+    evaluate(S.x, Gs[0]);
+    vglm6::start(a.rule, S, Gs[0][27]);
+    const double initial_cost = S.cost;
+    while (!S.done) {
+        vglm6::Step st;
+        vglm6::step(a.rule, S, Gs[cur], st);
         double cost_c = 0.;
-        if (step_ok) {   // the same decision in every lane
-            evaluate(xc, Gs[1 - cur]);
+        if (st.ok) {   // the same decision in every lane
+            evaluate(st.xc, Gs[1 - cur]);
             cost_c = Gs[1 - cur][27];
         }
-        iterations++;
-        double rho = 0.;
-        if (step_ok) {
-            const double model_change = 0.5 * (mu * ddx - gdx);
-            rho = model_change > 0. ? (cost - cost_c) / model_change : -1.;
-            if (gmax <= a.gtol) {
-                term = VG_TERM_CONVERGENCE_GRADIENT;
-                done = true;
-            } else if (sqrt(dx2) <= a.ptol * (sqrt(x2) + a.ptol)) {
-                term = VG_TERM_CONVERGENCE_PARAMETER;
-                done = true;
-            } else if (model_change > 0. && isfinite(cost_c) && fabs(cost - cost_c) <= a.ftol * cost) {
-                term = VG_TERM_CONVERGENCE_FUNCTION;
-                done = true;
-            }
-        }
-        if (done) break;
-        if (step_ok && isfinite(cost_c) && rho > a.min_rel_decrease) {
-            for (int k = 0; k < 6; k++) x[k] = xc[k];
-            cur = 1 - cur;
-            cost = cost_c;
-            const double t = 2. * rho - 1.;
-            radius = fmin(radius / fmax(1. - t * t * t, 1. / 3.), a.max_radius);
-            decrease_factor = 2.;
-        } else {
-            radius /= decrease_factor;
-            decrease_factor *= 2.;
-            if (radius < a.min_radius) {
-                term = VG_TERM_RADIUS_TOO_SMALL;
-                done = true;
-            }
-        }
-        if (iterations >= a.max_iter) done = true;
+        if (vglm6::accept(a.rule, S, st, cost_c)) cur = 1 - cur;
     }
     if (lane == 0) {
         double *o = a.out + (int64_t)blockIdx.x * kSolveOut;
-        for (int k = 0; k < 6; k++) o[k] = x[k];
-        o[6] = iterations;
+        for (int k = 0; k < 6; k++) o[k] = S.x[k];
+        o[6] = S.iterations;
         o[7] = initial_cost;
-        o[8] = cost;
-        o[9] = term;
+        o[8] = S.cost;
+        o[9] = S.term;
     }
 }
 

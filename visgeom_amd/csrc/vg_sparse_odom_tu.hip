@@ -57,9 +57,6 @@ struct HostBuf {
 
 constexpr int64_t kMaxItems = 65535;          // images, pairs and hypotheses ride on a grid dimension
 constexpr int64_t kMaxPoints = 1 << 20;       // matches of a ransac / score call, entries of a solve call
-// Ceres' defaults, which computeTransfSparse leaves in place but for the iteration cap
-constexpr double kFtol = 1e-6, kGtol = 1e-10, kPtol = 1e-8, kRadius0 = 1e4, kMaxRadius = 1e16, kMinRadius = 1e-32;
-constexpr double kMinRelDecrease = 1e-3, kDiagMin = 1e-6, kDiagMax = 1e32;
 
 }  // namespace
 
@@ -272,16 +269,7 @@ int run_solve(vg_sparse_odom *s, int64_t n_blocks, const int64_t *offsets, const
     a.index = index ? s->d_index.get() : nullptr;
     a.offsets = s->d_offsets.get();
     a.out = s->d_out.get();
-    a.max_iter = s->prm.max_lm_iterations;
-    a.ftol = kFtol;
-    a.gtol = kGtol;
-    a.ptol = kPtol;
-    a.radius0 = kRadius0;
-    a.max_radius = kMaxRadius;
-    a.min_radius = kMinRadius;
-    a.min_rel_decrease = kMinRelDecrease;
-    a.dmin = kDiagMin;
-    a.dmax = kDiagMax;
+    a.rule = vglm6::ceres_defaults(s->prm.max_lm_iterations);   // computeTransfSparse leaves Ceres' defaults in place but for the cap
     hipLaunchKernelGGL(vgso::solve_kernel, dim3((unsigned)n_blocks), dim3(64), 0, s->stream, a);
     VG_HIP(hipGetLastError());
     VG_HIP(hipMemcpyAsync(s->h_out.get(), s->d_out.get(), (size_t)n_blocks * vgso::kSolveOut * sizeof(double), hipMemcpyDeviceToHost, s->stream));
