@@ -2,8 +2,9 @@
 // Built with hipcc for gfx950 only; compiled on its own so that an edit of one subsystem does not rebuild the others.
 //
 // A vg_depth_fusion handle owns the scratch of its three operations: the warp's z-buffer and winner buffer (12 bytes per
-// depth pixel and item, all ones between calls: the gather kernel restores what it read), the per-item poses and counters in
-// one pinned and one device array, and the copy the noise filter reads when it runs in place.  Buffers only grow.
+// depth pixel and item, all ones between calls: the gather kernel restores what it read), the per-item poses with the warp's
+// counters in one pinned and one device array, the counters of merge and the noise filter, and the copy the noise filter
+// reads when it runs in place.  Buffers only grow.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -11,29 +12,24 @@
 #include <new>
 
 #include "vg_depth.hpp"
-#include "vg_internal.hpp"
+#include "vg_handle.hpp"
 #include "vg_stereo_host.hpp"
 #include "vg_transf_host.hpp"
 
-struct vg_depth_fusion {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vg_depth_fusion : vgi::HandleBase {
     double cam[6];
     vgd::Grid g;
     int64_t P = 0;
-    int64_t cap_items = 0;    // items d_item / h_item / d_counts / h_counts hold
-    int64_t cap_warp = 0;     // items the z-buffer and the winner buffer hold
-    int64_t cap_filter = 0;   // items the filter's copy holds
     bool warp_clean = false;  // the z-buffer and the winner buffer are all ones
-    vgi::DeviceMem<vgd::WarpItem> d_item;
-    vgi::PinnedMem<vgd::WarpItem> h_item;
-    vgi::DeviceMem<unsigned long long> d_counts, d_zbuf;
-    vgi::PinnedMem<unsigned long long> h_counts;
-    vgi::DeviceMem<unsigned> d_winner;
-    vgi::DeviceMem<double> d_copy;   // [2][n][P]
+    vgi::Grow<vgd::WarpItem> d_item;
+    vgi::GrowPinned<vgd::WarpItem> h_item;
+    vgi::Counters counters;   // of merge and filter_noise; the warp's travel in its items
+    vgi::Grow<unsigned long long> d_zbuf;   // [n][P], like the winner buffer
+    vgi::Grow<unsigned> d_winner;
+    vgi::Grow<double> d_copy;   // [2][n][P]
 #ifdef VG_DEPTH_WARP_STORE
-    vgi::DeviceMem<int> d_src_target;
-    vgi::DeviceMem<double> d_src_dist;
+    vgi::Grow<int> d_src_target;
+    vgi::Grow<double> d_src_dist;
 #endif
 };
 
@@ -41,21 +37,6 @@ namespace {
 
 using vgi::fail;
 using vgsh::blocks_of;
-constexpr int64_t kMaxItems = 65535;   // items ride on gridDim.y
-constexpr int kMaxCounters = 6;
-
-int ensure_items(vg_depth_fusion *s, int64_t n)
-{
-    if (n <= s->cap_items) return VG_OK;
-    s->cap_items = 0;
-    const size_t items = (size_t)n * sizeof(vgd::WarpItem), counts = (size_t)n * kMaxCounters * sizeof(unsigned long long);
-    if (s->d_item.alloc(items) != hipSuccess || s->d_counts.alloc(counts) != hipSuccess)
-        return fail(VG_ERR_ALLOC, "device allocation of the depth fusion items failed");
-    if (s->h_item.alloc(items, hipHostMallocDefault) != hipSuccess || s->h_counts.alloc(counts, hipHostMallocDefault) != hipSuccess)
-        return fail(VG_ERR_ALLOC, "pinned allocation of the depth fusion staging failed");
-    s->cap_items = n;
-    return VG_OK;
-}
 
 bool overlap(const void *a, const void *b, size_t bytes)
 {
@@ -75,29 +56,7 @@ bool any_overlap(const void *const *p, int k, size_t bytes)
 int check_call(const vg_depth_fusion *s, int64_t n)
 {
     if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "depth fusion handle is NULL");
-    if (n < 0 || n > kMaxItems) return fail(VG_ERR_INVALID_ARGUMENT, "the item count must be in [0, 65535]");
-    return VG_OK;
-}
-
-// an elementwise call's counters: zeroed before the launch, read back after it
-int counts_begin(vg_depth_fusion *s, int64_t n, int k, int64_t *counts, unsigned long long **dev)
-{
-    *dev = nullptr;
-    if (!counts) return VG_OK;
-    if (const int rc = ensure_items(s, n)) return rc;
-    VG_HIP(hipMemsetAsync(s->d_counts, 0, (size_t)n * k * sizeof(unsigned long long), s->stream));
-    *dev = s->d_counts.get();
-    return VG_OK;
-}
-
-int counts_end(vg_depth_fusion *s, int64_t n, int k, int64_t *counts, vgi::StreamDrain &drain)
-{
-    if (counts) VG_HIP(hipMemcpyAsync(s->h_counts, s->d_counts, (size_t)n * k * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
-    if (counts)
-        for (int64_t i = 0; i < n * k; i++) counts[i] = (int64_t)s->h_counts.get()[i];
-    return VG_OK;
+    return vgi::check_items(n, 0, "item");
 }
 
 }  // namespace
@@ -127,20 +86,12 @@ int vg_depth_fusion_create(vg_depth_fusion **out, int device, void *hip_stream, 
     for (int i = 0; i < 6; i++) s->cam[i] = eucm[i];
     s->g = vgd::Grid{p.scale, p.u0, p.v0, x_max, y_max};
     s->P = (int64_t)x_max * y_max;
-    if (const int rc = vgi::check_device(device, "depth fusion")) return rc;
-    s->device = device;
-    s->stream = reinterpret_cast<hipStream_t>(hip_stream);
+    if (const int rc = s->open(device, hip_stream, "depth fusion")) return rc;
     *out = s.release();
     return VG_OK;
 }
 
-void vg_depth_fusion_destroy(vg_depth_fusion *s)
-{
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    (void)hipStreamSynchronize(s->stream);
-    delete s;
-}
+void vg_depth_fusion_destroy(vg_depth_fusion *s) { vgi::destroy(s); }
 
 int vg_depth_fusion_size(const vg_depth_fusion *s, int *x_max, int *y_max)
 {
@@ -163,20 +114,18 @@ int vg_depth_warp(vg_depth_fusion *s, int64_t n, const double *xi12, const doubl
             if (overlap(out[i], in[j], bytes)) return fail(VG_ERR_INVALID_ARGUMENT, "the warp is a scatter: its outputs must not alias its inputs");
     if (any_overlap(out, 3, bytes)) return fail(VG_ERR_INVALID_ARGUMENT, "the outputs overlap each other");
     if (!vgsh::finite_n(xi12, 6 * (int)n)) return fail(VG_ERR_INVALID_ARGUMENT, "the transformations must be finite");
-    VG_HIP(hipSetDevice(s->device));
-    if (const int rc = ensure_items(s, n)) return rc;
-    if (n > s->cap_warp) {
-        s->cap_warp = 0;
-        s->warp_clean = false;
-        if (s->d_zbuf.alloc((size_t)(n * s->P) * sizeof(unsigned long long)) != hipSuccess ||
-            s->d_winner.alloc((size_t)(n * s->P) * sizeof(unsigned)) != hipSuccess)
-            return fail(VG_ERR_ALLOC, "device allocation of the warp's z-buffer failed");
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    if (const int rc = s->d_item.grow((size_t)n, "the depth fusion items")) return rc;
+    if (const int rc = s->h_item.grow((size_t)n, "the depth fusion staging")) return rc;
+    const size_t np = (size_t)(n * s->P);
+    if (np > s->d_zbuf.capacity() || np > s->d_winner.capacity()) s->warp_clean = false;   // a new block is not all ones
+    if (const int rc = s->d_zbuf.grow(np, "the warp's z-buffer")) return rc;
+    if (const int rc = s->d_winner.grow(np, "the warp's z-buffer")) return rc;
 #ifdef VG_DEPTH_WARP_STORE
-        if (s->d_src_target.alloc((size_t)(n * s->P) * sizeof(int)) != hipSuccess || s->d_src_dist.alloc(bytes) != hipSuccess)
-            return fail(VG_ERR_ALLOC, "device allocation of the warp's source records failed");
+    if (const int rc = s->d_src_target.grow(np, "the warp's source records")) return rc;
+    if (const int rc = s->d_src_dist.grow(np, "the warp's source records")) return rc;
 #endif
-        s->cap_warp = n;
-    }
     for (int64_t k = 0; k < n; k++) {   // R^T and t in FP64, with the rotation code of vg_stereo_host.hpp's build_geometry
         vgd::WarpItem &it = s->h_item.get()[k];
         const double *xi = xi12 + 6 * k;
@@ -185,10 +134,9 @@ int vg_depth_warp(vg_depth_fusion *s, int64_t n, const double *xi12, const doubl
         for (int i = 0; i < 3; i++) it.t[i] = xi[i];
         for (int i = 0; i < 6; i++) it.counts[i] = 0;
     }
-    vgi::StreamDrain drain{s->stream};
-    if (!s->warp_clean) {
-        VG_HIP(hipMemsetAsync(s->d_zbuf, 0xff, (size_t)(s->cap_warp * s->P) * sizeof(unsigned long long), s->stream));
-        VG_HIP(hipMemsetAsync(s->d_winner, 0xff, (size_t)(s->cap_warp * s->P) * sizeof(unsigned), s->stream));
+    if (!s->warp_clean) {   // the whole blocks: a later call of fewer items relies on it
+        VG_HIP(hipMemsetAsync(s->d_zbuf, 0xff, s->d_zbuf.capacity() * sizeof(unsigned long long), s->stream));
+        VG_HIP(hipMemsetAsync(s->d_winner, 0xff, s->d_winner.capacity() * sizeof(unsigned), s->stream));
     }
     s->warp_clean = false;
     VG_HIP(hipMemcpyAsync(s->d_item, s->h_item, (size_t)n * sizeof(vgd::WarpItem), hipMemcpyHostToDevice, s->stream));
@@ -216,8 +164,7 @@ int vg_depth_warp(vg_depth_fusion *s, int64_t n, const double *xi12, const doubl
     hipLaunchKernelGGL(vgd::depth_warp_gather_kernel, grid, block, 0, s->stream, a);
     VG_HIP(hipGetLastError());
     if (counts) VG_HIP(hipMemcpyAsync(s->h_item, s->d_item, (size_t)n * sizeof(vgd::WarpItem), hipMemcpyDeviceToHost, s->stream));
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
+    if (const int rc = call.finish()) return rc;
     s->warp_clean = true;
     if (counts)
         for (int64_t k = 0; k < n; k++) {
@@ -236,14 +183,14 @@ int vg_depth_merge(vg_depth_fusion *s, int64_t n, double *depth, double *sigma, 
     if (!depth || !sigma || !depth2 || !sigma2) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
     const void *const p[4] = {depth, sigma, depth2, sigma2};
     if (any_overlap(p, 4, (size_t)(n * s->P) * sizeof(double))) return fail(VG_ERR_INVALID_ARGUMENT, "the four maps of a merge must not overlap");
-    VG_HIP(hipSetDevice(s->device));
-    vgi::StreamDrain drain{s->stream};
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
     unsigned long long *dc = nullptr;
-    if (const int rc = counts_begin(s, n, 5, counts, &dc)) return rc;
+    if (const int rc = s->counters.begin(call, n, 5, counts, &dc)) return rc;
     hipLaunchKernelGGL(vgd::depth_merge_kernel, dim3(blocks_of(s->P, vgd::kLanes), (unsigned)n), dim3(vgd::kLanes), 0, s->stream, depth, sigma,
                        depth2, sigma2, s->P, dc);
     VG_HIP(hipGetLastError());
-    return counts_end(s, n, 5, counts, drain);
+    return s->counters.end(call, n, 5, counts);
 }
 
 int vg_depth_filter_noise(vg_depth_fusion *s, int64_t n, const double *depth_in, const double *sigma_in, double *depth, double *sigma,
@@ -257,13 +204,10 @@ int vg_depth_filter_noise(vg_depth_fusion *s, int64_t n, const double *depth_in,
     if (overlap(depth, sigma, bytes) || (!alias_d && overlap(depth, depth_in, bytes)) || overlap(depth, sigma_in, bytes) ||
         overlap(sigma, depth_in, bytes) || (!alias_s && overlap(sigma, sigma_in, bytes)))
         return fail(VG_ERR_INVALID_ARGUMENT, "an output of the noise filter must be its own input or overlap no input");
-    VG_HIP(hipSetDevice(s->device));
-    if ((alias_d || alias_s) && n > s->cap_filter) {
-        s->cap_filter = 0;
-        if (s->d_copy.alloc(2 * bytes) != hipSuccess) return fail(VG_ERR_ALLOC, "device allocation of the noise filter's copy failed");
-        s->cap_filter = n;
-    }
-    vgi::StreamDrain drain{s->stream};
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    if (alias_d || alias_s)
+        if (const int rc = s->d_copy.grow(2 * (size_t)(n * s->P), "the noise filter's copy")) return rc;
     if (alias_d) {   // the reference's myCopy
         VG_HIP(hipMemcpyAsync(s->d_copy, depth_in, bytes, hipMemcpyDeviceToDevice, s->stream));
         depth_in = s->d_copy;
@@ -273,11 +217,11 @@ int vg_depth_filter_noise(vg_depth_fusion *s, int64_t n, const double *depth_in,
         sigma_in = s->d_copy.get() + n * s->P;
     }
     unsigned long long *dc = nullptr;
-    if (const int rc = counts_begin(s, n, 3, counts, &dc)) return rc;
+    if (const int rc = s->counters.begin(call, n, 3, counts, &dc)) return rc;
     hipLaunchKernelGGL(vgd::depth_filter_noise_kernel, dim3(blocks_of(s->P, vgd::kLanes), (unsigned)n), dim3(vgd::kLanes), 0, s->stream, depth_in,
                        sigma_in, depth, sigma, s->g, s->P, dc);
     VG_HIP(hipGetLastError());
-    return counts_end(s, n, 3, counts, drain);
+    return s->counters.end(call, n, 3, counts);
 }
 
 int vg_transform_inverse(const double *xi, double *out6)

@@ -15,7 +15,7 @@
 #include <new>
 #include <vector>
 
-#include "vg_internal.hpp"
+#include "vg_handle.hpp"
 #include "vg_lm6.hpp"
 #include "vg_local.hpp"
 #include "vg_motion_prior.hpp"
@@ -24,30 +24,27 @@
 #include "vg_stereo_host.hpp"
 #include "vg_transf_host.hpp"
 
-struct vg_photometric {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vg_photometric : vgi::HandleBase {
     double cam[6], xbc[6];
     vgp::Grid g;
     int levels = 0, w[vgp::kMaxLevels], h[vgp::kMaxLevels];
     int64_t off[vgp::kMaxLevels + 1];   // pixel offset of a level inside one pyramid; off[levels] = pixels of a pyramid
     bool has_base = false;
-    int64_t n_targets = 0, cap_targets = 0, cap_poses = 0, cap_partials = 0;
+    int64_t n_targets = 0;
     int64_t m[vgp::kMaxLevels];         // points of the pack per scale
-    vgi::DeviceMem<float> d_base, d_targets, d_grad;   // [3][total]: img | gu | gv; [n][total]; [2][level 0] for vg_photometric_level
-    vgi::DeviceMem<int32_t> d_idx;                     // the packs: level i at off[i], room for every pixel
-    vgi::DeviceMem<double> d_val, d_cloud;
-    vgi::DeviceMem<unsigned> d_counts, d_offsets, d_total;
-    vgi::PinnedMem<unsigned> h_total;
-    vgi::DeviceMem<vgp::PoseFrame> d_frames;
-    vgi::PinnedMem<vgp::PoseFrame> h_frames;
-    vgi::DeviceMem<double> d_partials, d_sums;
-    vgi::PinnedMem<double> h_sums;
+    vgi::Grow<float> d_base, d_targets, d_grad;   // [3][total]: img | gu | gv; [n][total]; [2][level 0] for vg_photometric_level
+    vgi::Grow<int32_t> d_idx;                     // the packs: level i at off[i], room for every pixel
+    vgi::Grow<double> d_val, d_cloud;
+    vgi::Grow<unsigned> d_counts, d_offsets, d_total;
+    vgi::GrowPinned<unsigned> h_total;
+    vgi::Grow<vgp::PoseFrame> d_frames;
+    vgi::GrowPinned<vgp::PoseFrame> h_frames;
+    vgi::Grow<double> d_partials, d_sums;         // [n][blocks][kSums]; [n][kSums]
+    vgi::GrowPinned<double> h_sums;
     // the mutual-information cost: _hist1 per scale, and the staging of an evaluation
-    int64_t cap_mi_poses = 0, cap_mi_partials = 0;
-    vgi::DeviceMem<double> d_hist1, d_hist1_partials;   // [kMaxLevels][8]; [workgroups of level 0][8]
-    vgi::DeviceMem<double> d_mi_hist, d_mi_grad, d_mi_log, d_mi_out;   // [n][blocks][64], [n][blocks][6], [n][64], [n][kMiOut]
-    vgi::PinnedMem<double> h_mi_out;
+    vgi::Grow<double> d_hist1, d_hist1_partials;   // [kMaxLevels][8]; [workgroups of level 0][8]
+    vgi::Grow<double> d_mi_hist, d_mi_grad, d_mi_log, d_mi_out;   // [n][blocks][64], [n][blocks][6], [n][64], [n][kMiOut]
+    vgi::GrowPinned<double> h_mi_out;
 };
 
 namespace {
@@ -55,7 +52,6 @@ namespace {
 using vgi::fail;
 using vgsh::blocks_of;
 using vgth::Array6d;
-constexpr int64_t kMaxItems = 65535;   // poses and targets ride on gridDim.y
 constexpr int kMaxIterations = 150;    // photometric.cpp:150
 // Ceres' defaults, which the reference leaves in place (photometric.cpp:148-150), under the rule of vg_lm6.hpp
 constexpr vglm6::Rule kRule = vglm6::ceres_defaults(kMaxIterations);
@@ -79,15 +75,10 @@ void make_frame(const vg_photometric *s, const double *xi, int target, bool acti
 
 int ensure_poses(vg_photometric *s, int64_t n)
 {
-    if (n <= s->cap_poses) return VG_OK;
-    s->cap_poses = 0;
-    if (s->d_frames.alloc((size_t)n * sizeof(vgp::PoseFrame)) != hipSuccess || s->d_sums.alloc((size_t)n * vgp::kSums * sizeof(double)) != hipSuccess)
-        return fail(VG_ERR_ALLOC, "device allocation of the photometric poses failed");
-    if (s->h_frames.alloc((size_t)n * sizeof(vgp::PoseFrame), hipHostMallocDefault) != hipSuccess ||
-        s->h_sums.alloc((size_t)n * vgp::kSums * sizeof(double), hipHostMallocDefault) != hipSuccess)
-        return fail(VG_ERR_ALLOC, "pinned allocation of the photometric staging failed");
-    s->cap_poses = n;
-    return VG_OK;
+    if (const int rc = s->d_frames.grow((size_t)n, "the photometric poses")) return rc;
+    if (const int rc = s->d_sums.grow((size_t)n * vgp::kSums, "the photometric poses")) return rc;
+    if (const int rc = s->h_frames.grow((size_t)n, "the photometric staging")) return rc;
+    return s->h_sums.grow((size_t)n * vgp::kSums, "the photometric staging");
 }
 
 // the cost of the n frames in h_frames at one scale: residuals / rows to res / jac (DEVICE, may be NULL), the 28 sums per
@@ -100,13 +91,10 @@ int run_cost(vg_photometric *s, int scale, int64_t n, double *res, double *jac, 
         return VG_OK;
     }
     const unsigned blocks = blocks_of(m, vgp::kLanes);
-    if (sums && n * blocks > s->cap_partials) {
-        s->cap_partials = 0;
-        if (s->d_partials.alloc((size_t)(n * blocks) * vgp::kSums * sizeof(double)) != hipSuccess)
-            return fail(VG_ERR_ALLOC, "device allocation of the photometric partial sums failed");
-        s->cap_partials = n * blocks;
-    }
-    vgi::StreamDrain drain{s->stream};
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    if (sums)
+        if (const int rc = s->d_partials.grow((size_t)(n * blocks) * vgp::kSums, "the photometric partial sums")) return rc;
     VG_HIP(hipMemcpyAsync(s->d_frames, s->h_frames, (size_t)n * sizeof(vgp::PoseFrame), hipMemcpyHostToDevice, s->stream));
     vgp::EvalArgs a;
     a.frames = s->d_frames;
@@ -135,9 +123,7 @@ int run_cost(vg_photometric *s, int scale, int64_t n, double *res, double *jac, 
     } else {
         VG_HIP(hipGetLastError());
     }
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
-    return VG_OK;
+    return call.finish();
 }
 
 int check_poses(const vg_photometric *s, int64_t n, const double *xi, const int32_t *target)
@@ -145,7 +131,7 @@ int check_poses(const vg_photometric *s, int64_t n, const double *xi, const int3
     if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "photometric handle is NULL");
     if (!s->has_base) return fail(VG_ERR_INVALID_ARGUMENT, "no key frame: call vg_photometric_set_base first");
     if (s->n_targets == 0) return fail(VG_ERR_INVALID_ARGUMENT, "no target image: call vg_photometric_set_targets first");
-    if (n < 1 || n > kMaxItems) return fail(VG_ERR_INVALID_ARGUMENT, "the pose count must be in [1, 65535]");
+    if (const int rc = vgi::check_items(n, 1, "pose")) return rc;
     if (!xi || !target) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (!vgsh::finite_n(xi, 6 * (int)n)) return fail(VG_ERR_INVALID_ARGUMENT, "the poses must be finite");
     for (int64_t k = 0; k < n; k++)
@@ -169,22 +155,11 @@ struct LmPose {
 
 int ensure_mi(vg_photometric *s, int64_t n, unsigned blocks)
 {
-    if (n > s->cap_mi_poses) {
-        s->cap_mi_poses = 0;
-        if (s->d_mi_log.alloc((size_t)n * vgp::kMiCells * sizeof(double)) != hipSuccess || s->d_mi_out.alloc((size_t)n * vgp::kMiOut * sizeof(double)) != hipSuccess)
-            return fail(VG_ERR_ALLOC, "device allocation of the mutual-information results failed");
-        if (s->h_mi_out.alloc((size_t)n * vgp::kMiOut * sizeof(double), hipHostMallocDefault) != hipSuccess)
-            return fail(VG_ERR_ALLOC, "pinned allocation of the mutual-information staging failed");
-        s->cap_mi_poses = n;
-    }
-    if (n * blocks > s->cap_mi_partials) {
-        s->cap_mi_partials = 0;
-        if (s->d_mi_hist.alloc((size_t)(n * blocks) * vgp::kMiCells * sizeof(double)) != hipSuccess ||
-            s->d_mi_grad.alloc((size_t)(n * blocks) * 6 * sizeof(double)) != hipSuccess)
-            return fail(VG_ERR_ALLOC, "device allocation of the mutual-information partial sums failed");
-        s->cap_mi_partials = n * blocks;
-    }
-    return VG_OK;
+    if (const int rc = s->d_mi_log.grow((size_t)n * vgp::kMiCells, "the mutual-information results")) return rc;
+    if (const int rc = s->d_mi_out.grow((size_t)n * vgp::kMiOut, "the mutual-information results")) return rc;
+    if (const int rc = s->h_mi_out.grow((size_t)n * vgp::kMiOut, "the mutual-information staging")) return rc;
+    if (const int rc = s->d_mi_hist.grow((size_t)(n * blocks) * vgp::kMiCells, "the mutual-information partial sums")) return rc;
+    return s->d_mi_grad.grow((size_t)(n * blocks) * 6, "the mutual-information partial sums");
 }
 
 // MutualInformation::Evaluate of the n frames in h_frames at one scale (its pack is not empty): valVec2 to values (DEVICE, may
@@ -193,8 +168,9 @@ int run_mi(vg_photometric *s, int scale, int64_t n, double *values, bool grad)
 {
     const int64_t m = s->m[scale];
     const unsigned blocks = blocks_of(m, vgp::kLanes);
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
     if (const int rc = ensure_mi(s, n, blocks)) return rc;
-    vgi::StreamDrain drain{s->stream};
     VG_HIP(hipMemcpyAsync(s->d_frames, s->h_frames, (size_t)n * sizeof(vgp::PoseFrame), hipMemcpyHostToDevice, s->stream));
     vgp::MiArgs a;
     a.frames = s->d_frames;
@@ -224,9 +200,7 @@ int run_mi(vg_photometric *s, int scale, int64_t n, double *values, bool grad)
     }
     VG_HIP(hipGetLastError());
     VG_HIP(hipMemcpyAsync(s->h_mi_out, s->d_mi_out, (size_t)n * vgp::kMiOut * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
-    return VG_OK;
+    return call.finish();
 }
 
 // MutualInformationOdom's constructor for xiOdom and xiPrior
@@ -291,20 +265,12 @@ int vg_photometric_create(vg_photometric **out, int device, void *hip_stream, co
         s->off[i + 1] = s->off[i] + (int64_t)s->w[i] * s->h[i];
         s->m[i] = 0;
     }
-    if (const int rc = vgi::check_device(device, "photometric localization")) return rc;
-    s->device = device;
-    s->stream = reinterpret_cast<hipStream_t>(hip_stream);
+    if (const int rc = s->open(device, hip_stream, "photometric localization")) return rc;
     *out = s.release();
     return VG_OK;
 }
 
-void vg_photometric_destroy(vg_photometric *s)
-{
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    (void)hipStreamSynchronize(s->stream);
-    delete s;
-}
+void vg_photometric_destroy(vg_photometric *s) { vgi::destroy(s); }
 
 int vg_photometric_level_size(const vg_photometric *s, int scale_idx, int *width, int *height)
 {
@@ -332,22 +298,24 @@ int vg_photometric_set_base(vg_photometric *s, const uint8_t *img, const double 
 {
     if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "photometric handle is NULL");
     if (!img || !depth) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    VG_HIP(hipSetDevice(s->device));
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
     const int64_t total = s->off[s->levels];
     s->has_base = false;
-    if (!s->d_base.get()) {
-        const unsigned nb = blocks_of(level_pixels(s, 0), vgp::kLanes);
-        if (s->d_base.alloc((size_t)(3 * total) * sizeof(float)) != hipSuccess || s->d_idx.alloc((size_t)total * sizeof(int32_t)) != hipSuccess ||
-            s->d_val.alloc((size_t)total * sizeof(double)) != hipSuccess || s->d_cloud.alloc((size_t)(3 * total) * sizeof(double)) != hipSuccess ||
-            s->d_counts.alloc((size_t)nb * sizeof(unsigned)) != hipSuccess || s->d_offsets.alloc((size_t)nb * sizeof(unsigned)) != hipSuccess ||
-            s->d_total.alloc(vgp::kMaxLevels * sizeof(unsigned)) != hipSuccess ||
-            s->d_hist1.alloc(vgp::kMaxLevels * vgp::kMiBins * sizeof(double)) != hipSuccess ||
-            s->d_hist1_partials.alloc((size_t)nb * vgp::kMiBins * sizeof(double)) != hipSuccess)
-            return fail(VG_ERR_ALLOC, "device allocation of the key frame's pyramid and data packs failed");
-        if (s->h_total.alloc(vgp::kMaxLevels * sizeof(unsigned), hipHostMallocDefault) != hipSuccess)
-            return fail(VG_ERR_ALLOC, "pinned allocation of the pack counts failed");
+    {   // fixed sizes: allocated by the first call
+        const size_t nb = blocks_of(level_pixels(s, 0), vgp::kLanes);
+        const char *what = "the key frame's pyramid and data packs";
+        if (const int rc = s->d_base.grow((size_t)(3 * total), what)) return rc;
+        if (const int rc = s->d_idx.grow((size_t)total, what)) return rc;
+        if (const int rc = s->d_val.grow((size_t)total, what)) return rc;
+        if (const int rc = s->d_cloud.grow((size_t)(3 * total), what)) return rc;
+        if (const int rc = s->d_counts.grow(nb, what)) return rc;
+        if (const int rc = s->d_offsets.grow(nb, what)) return rc;
+        if (const int rc = s->d_total.grow(vgp::kMaxLevels, what)) return rc;
+        if (const int rc = s->d_hist1.grow((size_t)vgp::kMaxLevels * vgp::kMiBins, what)) return rc;
+        if (const int rc = s->d_hist1_partials.grow(nb * vgp::kMiBins, what)) return rc;
+        if (const int rc = s->h_total.grow(vgp::kMaxLevels, "the pack counts")) return rc;
     }
-    vgi::StreamDrain drain{s->stream};
     float *base = s->d_base.get();
     if (const int rc = build_pyramids(s, 1, img, base)) return rc;
     vgp::SelectArgs a;
@@ -384,8 +352,7 @@ int vg_photometric_set_base(vg_photometric *s, const uint8_t *img, const double 
     }
     VG_HIP(hipGetLastError());
     VG_HIP(hipMemcpyAsync(s->h_total, s->d_total, vgp::kMaxLevels * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
+    if (const int rc = call.finish()) return rc;
     for (int i = 0; i < s->levels; i++) s->m[i] = s->h_total.get()[i];
     s->has_base = true;
     return VG_OK;
@@ -394,20 +361,14 @@ int vg_photometric_set_base(vg_photometric *s, const uint8_t *img, const double 
 int vg_photometric_set_targets(vg_photometric *s, int64_t n, const uint8_t *imgs)
 {
     if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "photometric handle is NULL");
-    if (n < 1 || n > kMaxItems) return fail(VG_ERR_INVALID_ARGUMENT, "the target count must be in [1, 65535]");
+    if (const int rc = vgi::check_items(n, 1, "target")) return rc;
     if (!imgs) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    VG_HIP(hipSetDevice(s->device));
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
     s->n_targets = 0;
-    if (n > s->cap_targets) {
-        s->cap_targets = 0;
-        if (s->d_targets.alloc((size_t)(n * s->off[s->levels]) * sizeof(float)) != hipSuccess)
-            return fail(VG_ERR_ALLOC, "device allocation of the target pyramids failed");
-        s->cap_targets = n;
-    }
-    vgi::StreamDrain drain{s->stream};
+    if (const int rc = s->d_targets.grow((size_t)(n * s->off[s->levels]), "the target pyramids")) return rc;
     if (const int rc = build_pyramids(s, n, imgs, s->d_targets)) return rc;
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
+    if (const int rc = call.finish()) return rc;
     s->n_targets = n;
     return VG_OK;
 }
@@ -417,11 +378,11 @@ int vg_photometric_level(vg_photometric *s, int64_t target, int scale_idx, float
     if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "photometric handle is NULL");
     if (scale_idx < 0 || scale_idx >= s->levels) return fail(VG_ERR_INVALID_ARGUMENT, "scale index out of range");
     if (target < 0 ? !s->has_base : target >= s->n_targets) return fail(VG_ERR_INVALID_ARGUMENT, "no such pyramid: set_base / set_targets first");
-    VG_HIP(hipSetDevice(s->device));
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
     const int64_t total = s->off[s->levels], P = level_pixels(s, scale_idx);
     const size_t bytes = (size_t)P * sizeof(float);
     const float *src = (target < 0 ? s->d_base.get() : s->d_targets.get() + target * total) + s->off[scale_idx];
-    vgi::StreamDrain drain{s->stream};
     if (img) VG_HIP(hipMemcpyAsync(img, src, bytes, hipMemcpyDeviceToDevice, s->stream));
     if (grad_u || grad_v) {
         const float *gu = nullptr, *gv = nullptr;
@@ -429,8 +390,7 @@ int vg_photometric_level(vg_photometric *s, int64_t target, int scale_idx, float
             gu = s->d_base.get() + total + s->off[scale_idx];
             gv = s->d_base.get() + 2 * total + s->off[scale_idx];
         } else {   // a target keeps no gradients (scaleSpace2 has none): made here, for the caller
-            if (!s->d_grad.get() && s->d_grad.alloc((size_t)(2 * level_pixels(s, 0)) * sizeof(float)) != hipSuccess)
-                return fail(VG_ERR_ALLOC, "device allocation of the gradient scratch failed");
+            if (const int rc = s->d_grad.grow((size_t)(2 * level_pixels(s, 0)), "the gradient scratch")) return rc;
             hipLaunchKernelGGL(vgp::photo_sobel_kernel, dim3(blocks_of(P, vgp::kLanes), 1), dim3(vgp::kLanes), 0, s->stream, src, s->d_grad.get(),
                                s->d_grad.get() + P, (int64_t)0, s->w[scale_idx], s->h[scale_idx]);
             VG_HIP(hipGetLastError());
@@ -440,9 +400,7 @@ int vg_photometric_level(vg_photometric *s, int64_t target, int scale_idx, float
         if (grad_u) VG_HIP(hipMemcpyAsync(grad_u, gu, bytes, hipMemcpyDeviceToDevice, s->stream));
         if (grad_v) VG_HIP(hipMemcpyAsync(grad_v, gv, bytes, hipMemcpyDeviceToDevice, s->stream));
     }
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
-    return VG_OK;
+    return call.finish();
 }
 
 int vg_photometric_pack(vg_photometric *s, int scale_idx, int64_t *count, int32_t *indices, double *values, double *cloud)
@@ -453,14 +411,12 @@ int vg_photometric_pack(vg_photometric *s, int scale_idx, int64_t *count, int32_
     const int64_t m = s->m[scale_idx], o = s->off[scale_idx];
     if (count) *count = m;
     if (m == 0 || (!indices && !values && !cloud)) return VG_OK;
-    VG_HIP(hipSetDevice(s->device));
-    vgi::StreamDrain drain{s->stream};
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
     if (indices) VG_HIP(hipMemcpyAsync(indices, s->d_idx.get() + o, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToDevice, s->stream));
     if (values) VG_HIP(hipMemcpyAsync(values, s->d_val.get() + o, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
     if (cloud) VG_HIP(hipMemcpyAsync(cloud, s->d_cloud.get() + 3 * o, (size_t)(3 * m) * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
-    return VG_OK;
+    return call.finish();
 }
 
 int vg_photometric_evaluate(vg_photometric *s, int scale_idx, int64_t n, const double *xi, const int32_t *target, double *residuals,

@@ -12,7 +12,7 @@
 #include <new>
 #include <vector>
 
-#include "vg_internal.hpp"
+#include "vg_handle.hpp"
 #include "vg_local.hpp"
 #include "vg_motion_prior.hpp"
 #include "vg_sparse_odom.hpp"
@@ -25,68 +25,35 @@ using vgi::fail;
 using vgsh::blocks_of;
 using vgth::Array6d;
 
-template <class T>
-struct Buf {
-    vgi::DeviceMem<T> m;
-    size_t cap = 0;
-    T *get() const { return m.get(); }
-    int grow(size_t n)
-    {
-        if (n <= cap) return VG_OK;
-        cap = 0;
-        if (m.alloc(n * sizeof(T)) != hipSuccess) return fail(VG_ERR_ALLOC, "device allocation of the sparse odometry scratch failed");
-        cap = n;
-        return VG_OK;
-    }
-};
-
-template <class T>
-struct HostBuf {
-    vgi::PinnedMem<T> m;
-    size_t cap = 0;
-    T *get() const { return m.get(); }
-    int grow(size_t n)
-    {
-        if (n <= cap) return VG_OK;
-        cap = 0;
-        if (m.alloc(n * sizeof(T), hipHostMallocDefault) != hipSuccess) return fail(VG_ERR_ALLOC, "pinned allocation of the sparse odometry staging failed");
-        cap = n;
-        return VG_OK;
-    }
-};
-
-constexpr int64_t kMaxItems = 65535;          // images, pairs and hypotheses ride on a grid dimension
-constexpr int64_t kMaxPoints = 1 << 20;       // matches of a ransac / score call, entries of a solve call
+constexpr int64_t kMaxPoints = 1 << 20;   // matches of a ransac / score call, entries of a solve call
 
 }  // namespace
 
-struct vg_sparse_odom {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vg_sparse_odom : vgi::HandleBase {
     double cam[6], xbc[6];
     int w = 0, h = 0;
     vg_sparse_odom_params prm;
     int64_t cand_cap = 0;   // strict 3 x 3 maxima of the interior: no two are neighbours
-    Buf<double> d_static;   // [81 weights | 6 intrinsics]
+    vgi::Grow<double> d_static;   // [81 weights | 6 intrinsics]
     // detect
-    Buf<int32_t> d_grad, d_sums, d_cand_i, d_count;
-    Buf<int64_t> d_resp, d_cand_r;
-    Buf<unsigned int> d_cand_n;
-    HostBuf<int32_t> h_count;
+    vgi::Grow<int32_t> d_grad, d_sums, d_cand_i, d_count;
+    vgi::Grow<int64_t> d_resp, d_cand_r;
+    vgi::Grow<unsigned int> d_cand_n;
+    vgi::GrowPinned<int32_t> h_count;
     // match
-    Buf<double> d_dist;
-    Buf<int32_t> d_nn, d_cnt;
+    vgi::Grow<double> d_dist;
+    vgi::Grow<int32_t> d_nn, d_cnt;
     // solve / score
-    Buf<double> d_consts, d_out, d_frames, d_res;
-    Buf<int64_t> d_offsets;
-    Buf<int32_t> d_index, d_inliers;
-    HostBuf<double> h_out, h_res;
-    HostBuf<int32_t> h_inliers;
+    vgi::Grow<double> d_consts, d_out, d_frames, d_res;
+    vgi::Grow<int64_t> d_offsets;
+    vgi::Grow<int32_t> d_index, d_inliers;
+    vgi::GrowPinned<double> h_out, h_res;
+    vgi::GrowPinned<int32_t> h_inliers;
     // feed: two frame slots, the matches and rays of the current pair
-    Buf<int32_t> d_kp[2], d_matches;
-    Buf<float> d_desc[2];
-    Buf<double> d_distance, d_rays;   // rays: x1 (3) | x2 (3) | p2 (2) | size (1) planes of max_features
-    Buf<uint8_t> d_mask;
+    vgi::Grow<int32_t> d_kp[2], d_matches;
+    vgi::Grow<float> d_desc[2];
+    vgi::Grow<double> d_distance, d_rays;   // rays: x1 (3) | x2 (3) | p2 (2) | size (1) planes of max_features
+    vgi::Grow<uint8_t> d_mask;
     int n_kp[2] = {0, 0}, cur = 0;
     bool has_prev = false;
     double odom_prev[6], xi_local[6], xi_incr[6];
@@ -131,8 +98,8 @@ void draw_samples(vg_sparse_odom *s, int64_t m, int32_t *samples)
 int launch_response(vg_sparse_odom *s, int64_t n, const uint8_t *img, int64_t *resp)
 {
     const int64_t P = (int64_t)s->w * s->h;
-    if (const int rc = s->d_grad.grow((size_t)(n * P))) return rc;
-    if (const int rc = s->d_sums.grow((size_t)(3 * n * P))) return rc;
+    if (const int rc = s->d_grad.grow((size_t)(n * P), "the sparse odometry scratch")) return rc;
+    if (const int rc = s->d_sums.grow((size_t)(3 * n * P), "the sparse odometry scratch")) return rc;
     const dim3 grid(blocks_of(P, vgso::kThreads), (unsigned)n);
     hipLaunchKernelGGL(vgso::gradient_kernel, grid, dim3(vgso::kThreads), 0, s->stream, img, s->w, s->h, s->d_grad.get());
     hipLaunchKernelGGL(vgso::row_sum_kernel, grid, dim3(vgso::kThreads), 0, s->stream, (const int32_t *)s->d_grad.get(), s->w, s->h, n * P, s->d_sums.get());
@@ -145,13 +112,14 @@ int launch_response(vg_sparse_odom *s, int64_t n, const uint8_t *img, int64_t *r
 int run_detect(vg_sparse_odom *s, int64_t n, const uint8_t *img, int32_t *count, int32_t *keypoints, float *descriptors)
 {
     const int64_t P = (int64_t)s->w * s->h;
-    if (const int rc = s->d_resp.grow((size_t)(n * P))) return rc;
-    if (const int rc = s->d_cand_r.grow((size_t)(n * s->cand_cap))) return rc;
-    if (const int rc = s->d_cand_i.grow((size_t)(n * s->cand_cap))) return rc;
-    if (const int rc = s->d_cand_n.grow((size_t)n)) return rc;
-    if (const int rc = s->d_count.grow((size_t)n)) return rc;
-    if (const int rc = s->h_count.grow((size_t)n)) return rc;
-    vgi::StreamDrain drain{s->stream};
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    if (const int rc = s->d_resp.grow((size_t)(n * P), "the sparse odometry scratch")) return rc;
+    if (const int rc = s->d_cand_r.grow((size_t)(n * s->cand_cap), "the sparse odometry scratch")) return rc;
+    if (const int rc = s->d_cand_i.grow((size_t)(n * s->cand_cap), "the sparse odometry scratch")) return rc;
+    if (const int rc = s->d_cand_n.grow((size_t)n, "the sparse odometry scratch")) return rc;
+    if (const int rc = s->d_count.grow((size_t)n, "the sparse odometry scratch")) return rc;
+    if (const int rc = s->h_count.grow((size_t)n, "the sparse odometry staging")) return rc;
     if (const int rc = launch_response(s, n, img, s->d_resp.get())) return rc;
     VG_HIP(hipMemsetAsync(s->d_cand_n.get(), 0, (size_t)n * sizeof(unsigned int), s->stream));
     const int64_t interior = (int64_t)(s->w - 2 * vgso::kBorder) * (s->h - 2 * vgso::kBorder);
@@ -173,8 +141,7 @@ int run_detect(vg_sparse_odom *s, int64_t n, const uint8_t *img, int32_t *count,
     hipLaunchKernelGGL(vgso::select_kernel, dim3((unsigned)n), dim3(vgso::kSelectThreads), 0, s->stream, a);
     VG_HIP(hipGetLastError());
     VG_HIP(hipMemcpyAsync(s->h_count.get(), s->d_count.get(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
+    if (const int rc = call.finish()) return rc;
     std::memcpy(count, s->h_count.get(), (size_t)n * sizeof(int32_t));
     return VG_OK;
 }
@@ -193,13 +160,14 @@ int run_match(vg_sparse_odom *s, int64_t n, const int32_t *count1, const float *
         for (int64_t i = 0; i < n; i++) match_count[i] = 0;
         return VG_OK;
     }
-    if (const int rc = s->d_dist.grow((size_t)(2 * n) * F * F)) return rc;
-    if (const int rc = s->d_nn.grow((size_t)(2 * n) * F)) return rc;
-    if (const int rc = s->d_cnt.grow((size_t)(3 * n))) return rc;
-    if (const int rc = s->h_count.grow((size_t)(3 * n))) return rc;
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    if (const int rc = s->d_dist.grow((size_t)(2 * n) * F * F, "the sparse odometry scratch")) return rc;
+    if (const int rc = s->d_nn.grow((size_t)(2 * n) * F, "the sparse odometry scratch")) return rc;
+    if (const int rc = s->d_cnt.grow((size_t)(3 * n), "the sparse odometry scratch")) return rc;
+    if (const int rc = s->h_count.grow((size_t)(3 * n), "the sparse odometry staging")) return rc;
     std::memcpy(s->h_count.get(), count1, (size_t)n * sizeof(int32_t));
     std::memcpy(s->h_count.get() + n, count2, (size_t)n * sizeof(int32_t));
-    vgi::StreamDrain drain{s->stream};
     VG_HIP(hipMemcpyAsync(s->d_cnt.get(), s->h_count.get(), (size_t)(2 * n) * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
     vgso::MatchArgs a;
     a.desc1 = desc1;
@@ -221,8 +189,7 @@ int run_match(vg_sparse_odom *s, int64_t n, const int32_t *count1, const float *
     hipLaunchKernelGGL(vgso::cross_check_kernel, dim3((unsigned)n), dim3(64), 0, s->stream, a);
     VG_HIP(hipGetLastError());
     VG_HIP(hipMemcpyAsync(s->h_count.get() + 2 * n, s->d_cnt.get() + 2 * n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
+    if (const int rc = call.finish()) return rc;
     std::memcpy(match_count, s->h_count.get() + 2 * n, (size_t)n * sizeof(int32_t));
     return VG_OK;
 }
@@ -230,8 +197,10 @@ int run_match(vg_sparse_odom *s, int64_t n, const int32_t *count1, const float *
 // what every problem of a call shares: the prior's A and J, the camera, xi_base_cam with its constants, the odometry increment
 int upload_consts(vg_sparse_odom *s, const double *xi_odom)
 {
-    if (const int rc = s->d_consts.grow(vgso::kConstDoubles)) return rc;
-    if (const int rc = s->h_out.grow(vgso::kConstDoubles)) return rc;
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    if (const int rc = s->d_consts.grow(vgso::kConstDoubles, "the sparse odometry scratch")) return rc;
+    if (const int rc = s->h_out.grow(vgso::kConstDoubles, "the sparse odometry staging")) return rc;
     const vg_sparse_odom_params &p = s->prm;
     const vgmp::MotionPrior prior = vgmp::make_prior(xi_odom, p.prior_err_v, p.prior_err_w, p.prior_lambda_t, p.prior_lambda_r);
     double *c = s->h_out.get();
@@ -242,8 +211,7 @@ int upload_consts(vg_sparse_odom *s, const double *xi_odom)
     vg::base_const(s->xbc, c + vgso::kConstBase);
     std::memcpy(c + vgso::kConstOdom, xi_odom, sizeof(double) * 6);
     VG_HIP(hipMemcpyAsync(s->d_consts.get(), c, vgso::kConstDoubles * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    VG_HIP(hipStreamSynchronize(s->stream));   // the staging block is reused by the solve's results
-    return VG_OK;
+    return call.finish();   // the staging block is reused by the solve's results
 }
 
 // n_blocks problems in one launch; offsets HOST, index HOST (may be NULL), the points DEVICE.  Results in h_out
@@ -251,13 +219,14 @@ int upload_consts(vg_sparse_odom *s, const double *xi_odom)
 int run_solve(vg_sparse_odom *s, int64_t n_blocks, const int64_t *offsets, const int32_t *index, const double *x1, const double *x2, const double *p2,
               const double *size)
 {
-    if (const int rc = s->d_offsets.grow((size_t)n_blocks + 1)) return rc;
-    if (const int rc = s->d_out.grow((size_t)n_blocks * vgso::kSolveOut)) return rc;
-    if (const int rc = s->h_out.grow(std::max<size_t>((size_t)n_blocks * vgso::kSolveOut, vgso::kConstDoubles))) return rc;
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    if (const int rc = s->d_offsets.grow((size_t)n_blocks + 1, "the sparse odometry scratch")) return rc;
+    if (const int rc = s->d_out.grow((size_t)n_blocks * vgso::kSolveOut, "the sparse odometry scratch")) return rc;
+    if (const int rc = s->h_out.grow(std::max<size_t>((size_t)n_blocks * vgso::kSolveOut, vgso::kConstDoubles), "the sparse odometry staging")) return rc;
     const int64_t entries = offsets[n_blocks];
     if (index)
-        if (const int rc = s->d_index.grow((size_t)std::max<int64_t>(entries, 1))) return rc;
-    vgi::StreamDrain drain{s->stream};
+        if (const int rc = s->d_index.grow((size_t)std::max<int64_t>(entries, 1), "the sparse odometry scratch")) return rc;
     VG_HIP(hipMemcpyAsync(s->d_offsets.get(), offsets, (size_t)(n_blocks + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
     if (index && entries > 0) VG_HIP(hipMemcpyAsync(s->d_index.get(), index, (size_t)entries * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
     vgso::SolveArgs a;
@@ -273,9 +242,7 @@ int run_solve(vg_sparse_odom *s, int64_t n_blocks, const int64_t *offsets, const
     hipLaunchKernelGGL(vgso::solve_kernel, dim3((unsigned)n_blocks), dim3(64), 0, s->stream, a);
     VG_HIP(hipGetLastError());
     VG_HIP(hipMemcpyAsync(s->h_out.get(), s->d_out.get(), (size_t)n_blocks * vgso::kSolveOut * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
-    return VG_OK;
+    return call.finish();
 }
 
 // the camera motion xi_c = xi_base_cam^-1 o xi o xi_base_cam
@@ -292,12 +259,14 @@ Array6d camera_motion(const vg_sparse_odom *s, const double *xi)
 int run_score(vg_sparse_odom *s, int64_t n_hyp, const double *xi, int64_t m, const int32_t *index, const double *x1, const double *x2, const double *p2,
               double *residual)
 {
-    if (const int rc = s->d_frames.grow((size_t)n_hyp * vgso::kScoreFrame)) return rc;
-    if (const int rc = s->d_inliers.grow((size_t)n_hyp)) return rc;
-    if (const int rc = s->h_inliers.grow((size_t)n_hyp)) return rc;
-    if (const int rc = s->h_res.grow((size_t)n_hyp * vgso::kScoreFrame)) return rc;
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    if (const int rc = s->d_frames.grow((size_t)n_hyp * vgso::kScoreFrame, "the sparse odometry scratch")) return rc;
+    if (const int rc = s->d_inliers.grow((size_t)n_hyp, "the sparse odometry scratch")) return rc;
+    if (const int rc = s->h_inliers.grow((size_t)n_hyp, "the sparse odometry staging")) return rc;
+    if (const int rc = s->h_res.grow((size_t)n_hyp * vgso::kScoreFrame, "the sparse odometry staging")) return rc;
     if (index)
-        if (const int rc = s->d_index.grow((size_t)m)) return rc;
+        if (const int rc = s->d_index.grow((size_t)m, "the sparse odometry scratch")) return rc;
     double *f = s->h_res.get();
     for (int64_t k = 0; k < n_hyp; k++, f += vgso::kScoreFrame) {
         const Array6d c = camera_motion(s, xi + 6 * k);
@@ -306,7 +275,6 @@ int run_score(vg_sparse_odom *s, int64_t n_hyp, const double *xi, int64_t m, con
         vg::rotation_matrix(c.data() + 3, 1., rt, f + 3);
         vg::rotation_matrix(c.data() + 3, -1., rt, f + 12);
     }
-    vgi::StreamDrain drain{s->stream};
     VG_HIP(hipMemcpyAsync(s->d_frames.get(), s->h_res.get(), (size_t)n_hyp * vgso::kScoreFrame * sizeof(double), hipMemcpyHostToDevice, s->stream));
     if (index) VG_HIP(hipMemcpyAsync(s->d_index.get(), index, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
     VG_HIP(hipMemsetAsync(s->d_inliers.get(), 0, (size_t)n_hyp * sizeof(int32_t), s->stream));
@@ -324,18 +292,17 @@ int run_score(vg_sparse_odom *s, int64_t n_hyp, const double *xi, int64_t m, con
     hipLaunchKernelGGL(vgso::score_kernel, dim3(blocks_of(m, vgso::kThreads), (unsigned)n_hyp), dim3(vgso::kThreads), 0, s->stream, a);
     VG_HIP(hipGetLastError());
     VG_HIP(hipMemcpyAsync(s->h_inliers.get(), s->d_inliers.get(), (size_t)n_hyp * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
-    return VG_OK;
+    return call.finish();
 }
 
 // residual row (DEVICE [m]) to h_res.  Synchronous.
 int fetch_residuals(vg_sparse_odom *s, const double *row, int64_t m)
 {
-    if (const int rc = s->h_res.grow((size_t)m)) return rc;
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    if (const int rc = s->h_res.grow((size_t)m, "the sparse odometry staging")) return rc;
     VG_HIP(hipMemcpyAsync(s->h_res.get(), row, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    VG_HIP(hipStreamSynchronize(s->stream));
-    return VG_OK;
+    return call.finish();
 }
 
 // ransacNPoints and the two refinements of feedData on m matches (DEVICE); samples HOST [iterations][points], every index in
@@ -363,7 +330,7 @@ int run_ransac(vg_sparse_odom *s, int64_t m, const double *x1, const double *x2,
     if (const int rc = run_solve(s, iters, offsets.data(), samples, x1, x2, p2, size)) return rc;
     std::vector<double> xi((size_t)iters * 6);
     for (int k = 0; k < iters; k++) std::memcpy(&xi[(size_t)k * 6], s->h_out.get() + (size_t)k * vgso::kSolveOut, sizeof(double) * 6);
-    if (const int rc = s->d_res.grow((size_t)iters * m)) return rc;
+    if (const int rc = s->d_res.grow((size_t)iters * m, "the sparse odometry scratch")) return rc;
     if (const int rc = run_score(s, iters, xi.data(), m, nullptr, x1, x2, p2, s->d_res.get())) return rc;
     int best = -1, count = np;
     for (int k = 0; k < iters; k++)
@@ -391,7 +358,7 @@ int run_ransac(vg_sparse_odom *s, int64_t m, const double *x1, const double *x2,
     if (const int rc = run_solve(s, 1, one, inl.data(), x1, x2, p2, size)) return rc;
     rep[3] = s->h_out.get()[8];
     rep[4] = s->h_out.get()[9];
-    if (const int rc = s->d_res.grow((size_t)std::max<int64_t>((int64_t)iters * m, (int64_t)inl.size()))) return rc;
+    if (const int rc = s->d_res.grow((size_t)std::max<int64_t>((int64_t)iters * m, (int64_t)inl.size()), "the sparse odometry scratch")) return rc;
     if (const int rc = run_score(s, 1, xi_odom, (int64_t)inl.size(), inl.data(), x1, x2, p2, s->d_res.get())) return rc;
     if (const int rc = fetch_residuals(s, s->d_res.get(), (int64_t)inl.size())) return rc;
     double acc = 0.;
@@ -453,7 +420,7 @@ int vg_sparse_odom_create(vg_sparse_odom **out, int device, void *hip_stream, co
         return fail(VG_ERR_INVALID_ARGUMENT, "the image size must be in [15, 16384]");
     if (p.max_features < 1 || p.max_features > vgso::kMaxFeatures) return fail(VG_ERR_INVALID_ARGUMENT, "max_features must be in [1, 1024]");
     if (p.num_ransac_points < 2 || p.num_ransac_points > 16) return fail(VG_ERR_INVALID_ARGUMENT, "num_ransac_points must be in [2, 16]");
-    if (p.ransac_iterations < 1 || p.ransac_iterations > kMaxItems) return fail(VG_ERR_INVALID_ARGUMENT, "ransac_iterations must be in [1, 65535]");
+    if (p.ransac_iterations < 1 || p.ransac_iterations > vgi::kMaxItems) return fail(VG_ERR_INVALID_ARGUMENT, "ransac_iterations must be in [1, 65535]");
     if (p.max_lm_iterations < 0 || p.max_lm_iterations > 10000) return fail(VG_ERR_INVALID_ARGUMENT, "max_lm_iterations must be in [0, 10000]");
     if (!(p.match_threshold >= 0.) || !(p.inlier_threshold > 0.) || !(p.outlier_gate > 0.) || !(p.min_stereo_base >= 0.) || !std::isfinite(p.match_threshold) ||
         !std::isfinite(p.inlier_threshold) || !std::isfinite(p.outlier_gate) || !std::isfinite(p.min_stereo_base))
@@ -474,10 +441,9 @@ int vg_sparse_odom_create(vg_sparse_odom **out, int device, void *hip_stream, co
     s->h = height;
     s->prm = p;
     s->cand_cap = (int64_t)((width - 2 * vgso::kBorder + 1) / 2) * ((height - 2 * vgso::kBorder + 1) / 2);
-    if (const int rc = vgi::check_device(device, "sparse odometry")) return rc;
-    s->device = device;
-    s->stream = reinterpret_cast<hipStream_t>(hip_stream);
-    VG_HIP(hipSetDevice(device));
+    if (const int rc = s->open(device, hip_stream, "sparse odometry")) return rc;
+    vgi::Call call(s.get());   // a failure below drains the stream before s is freed
+    if (const int rc = call.begin()) return rc;
     double st[vgso::kDesc + 6];   // descriptors' kernel (sparse_odom.cpp:211-221): one table of std::exp values
     int q = 0;
     for (int v = -vgso::kPatch; v <= vgso::kPatch; v++) {
@@ -488,40 +454,31 @@ int vg_sparse_odom_create(vg_sparse_odom **out, int device, void *hip_stream, co
         }
     }
     for (int i = 0; i < 6; i++) st[vgso::kDesc + i] = eucm[i];
-    if (const int rc = s->d_static.grow(vgso::kDesc + 6)) return rc;
+    if (const int rc = s->d_static.grow(vgso::kDesc + 6, "the sparse odometry scratch")) return rc;
     VG_HIP(hipMemcpyAsync(s->d_static.get(), st, sizeof st, hipMemcpyHostToDevice, s->stream));
-    VG_HIP(hipStreamSynchronize(s->stream));
+    if (const int rc = call.finish()) return rc;
     *out = s.release();
     return VG_OK;
 }
 
-void vg_sparse_odom_destroy(vg_sparse_odom *s)
-{
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    (void)hipStreamSynchronize(s->stream);
-    delete s;
-}
+void vg_sparse_odom_destroy(vg_sparse_odom *s) { vgi::destroy(s); }
 
 int vg_sparse_odom_response(vg_sparse_odom *s, int64_t n, const uint8_t *img, int64_t *response)
 {
     if (const int rc = check_handle(s)) return rc;
-    if (n < 1 || n > kMaxItems) return fail(VG_ERR_INVALID_ARGUMENT, "the image count must be in [1, 65535]");
+    if (const int rc = vgi::check_items(n, 1, "image")) return rc;
     if (!img || !response) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    VG_HIP(hipSetDevice(s->device));
-    vgi::StreamDrain drain{s->stream};
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
     if (const int rc = launch_response(s, n, img, response)) return rc;
-    drain.armed = false;
-    VG_HIP(hipStreamSynchronize(s->stream));
-    return VG_OK;
+    return call.finish();
 }
 
 int vg_sparse_odom_detect(vg_sparse_odom *s, int64_t n, const uint8_t *img, int32_t *count, int32_t *keypoints, float *descriptors)
 {
     if (const int rc = check_handle(s)) return rc;
-    if (n < 1 || n > kMaxItems) return fail(VG_ERR_INVALID_ARGUMENT, "the image count must be in [1, 65535]");
+    if (const int rc = vgi::check_items(n, 1, "image")) return rc;
     if (!img || !count || !keypoints || !descriptors) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    VG_HIP(hipSetDevice(s->device));
     return run_detect(s, n, img, count, keypoints, descriptors);
 }
 
@@ -529,12 +486,11 @@ int vg_sparse_odom_match(vg_sparse_odom *s, int64_t n, const int32_t *count1, co
                          const float *descriptors2, int32_t *match_count, int32_t *matches, double *distance)
 {
     if (const int rc = check_handle(s)) return rc;
-    if (n < 1 || n > kMaxItems) return fail(VG_ERR_INVALID_ARGUMENT, "the pair count must be in [1, 65535]");
+    if (const int rc = vgi::check_items(n, 1, "pair")) return rc;
     if (!count1 || !descriptors1 || !count2 || !descriptors2 || !match_count || !matches || !distance) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
     for (int64_t i = 0; i < n; i++)
         if (count1[i] < 0 || count1[i] > s->prm.max_features || count2[i] < 0 || count2[i] > s->prm.max_features)
             return fail(VG_ERR_INVALID_ARGUMENT, "a feature count must be in [0, max_features]");
-    VG_HIP(hipSetDevice(s->device));
     return run_match(s, n, count1, descriptors1, count2, descriptors2, match_count, matches, distance);
 }
 
@@ -550,7 +506,6 @@ int vg_sparse_odom_solve(vg_sparse_odom *s, int64_t n_blocks, const int64_t *off
     if (offsets[n_blocks] > kMaxPoints) return fail(VG_ERR_INVALID_ARGUMENT, "at most 2^20 points in one call");
     if (offsets[n_blocks] > 0 && (!x1 || !x2 || !p2 || !size)) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (!vgsh::finite_n(xi_odom, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "the odometry increment must be finite");
-    VG_HIP(hipSetDevice(s->device));
     if (const int rc = upload_consts(s, xi_odom)) return rc;
     if (const int rc = run_solve(s, n_blocks, offsets, nullptr, x1, x2, p2, size)) return rc;
     for (int64_t b = 0; b < n_blocks; b++) {
@@ -565,7 +520,7 @@ int vg_sparse_odom_score(vg_sparse_odom *s, int64_t n_hyp, const double *xi, int
                          double *residual, int32_t *inliers)
 {
     if (const int rc = check_handle(s)) return rc;
-    if (n_hyp < 1 || n_hyp > kMaxItems) return fail(VG_ERR_INVALID_ARGUMENT, "the hypothesis count must be in [1, 65535]");
+    if (const int rc = vgi::check_items(n_hyp, 1, "hypothesis")) return rc;
     if (m < 0 || m > kMaxPoints) return fail(VG_ERR_INVALID_ARGUMENT, "the match count must be in [0, 2^20]");
     if (!xi || !inliers || (m > 0 && (!x1 || !x2 || !p2))) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (!vgsh::finite_n(xi, 6 * (int)n_hyp)) return fail(VG_ERR_INVALID_ARGUMENT, "the poses must be finite");
@@ -573,7 +528,6 @@ int vg_sparse_odom_score(vg_sparse_odom *s, int64_t n_hyp, const double *xi, int
         for (int64_t k = 0; k < n_hyp; k++) inliers[k] = 0;
         return VG_OK;
     }
-    VG_HIP(hipSetDevice(s->device));
     if (const int rc = run_score(s, n_hyp, xi, m, nullptr, x1, x2, p2, residual)) return rc;
     std::memcpy(inliers, s->h_inliers.get(), (size_t)n_hyp * sizeof(int32_t));
     return VG_OK;
@@ -634,8 +588,8 @@ int vg_sparse_odom_feed(vg_sparse_odom *s, const uint8_t *img, const double *xi_
     }
     VG_HIP(hipSetDevice(s->device));
     const int nxt = 1 - s->cur;
-    if (const int rc = s->d_kp[nxt].grow((size_t)F * 2)) return rc;
-    if (const int rc = s->d_desc[nxt].grow((size_t)F * vgso::kDesc)) return rc;
+    if (const int rc = s->d_kp[nxt].grow((size_t)F * 2, "the sparse odometry scratch")) return rc;
+    if (const int rc = s->d_desc[nxt].grow((size_t)F * vgso::kDesc, "the sparse odometry scratch")) return rc;
     int32_t n_new = 0;
     if (const int rc = run_detect(s, 1, img, &n_new, s->d_kp[nxt].get(), s->d_desc[nxt].get())) return rc;
     s->n_kp[nxt] = n_new;
@@ -643,10 +597,10 @@ int vg_sparse_odom_feed(vg_sparse_odom *s, const uint8_t *img, const double *xi_
     int state = VG_SPARSE_ODOM_FIRST;
     if (s->has_prev && s->n_kp[s->cur] > 0) {
         state = VG_SPARSE_ODOM_ESTIMATED;
-        if (const int rc = s->d_matches.grow((size_t)F * 2)) return rc;
-        if (const int rc = s->d_distance.grow((size_t)F)) return rc;
-        if (const int rc = s->d_rays.grow((size_t)F * 9)) return rc;
-        if (const int rc = s->d_mask.grow((size_t)F)) return rc;
+        if (const int rc = s->d_matches.grow((size_t)F * 2, "the sparse odometry scratch")) return rc;
+        if (const int rc = s->d_distance.grow((size_t)F, "the sparse odometry scratch")) return rc;
+        if (const int rc = s->d_rays.grow((size_t)F * 9, "the sparse odometry scratch")) return rc;
+        if (const int rc = s->d_mask.grow((size_t)F, "the sparse odometry scratch")) return rc;
         int32_t m = 0, n_old = s->n_kp[s->cur];
         if (const int rc = run_match(s, 1, &n_old, s->d_desc[s->cur].get(), &n_new, s->d_desc[nxt].get(), &m, s->d_matches.get(), s->d_distance.get()))
             return rc;

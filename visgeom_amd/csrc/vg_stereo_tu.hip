@@ -13,7 +13,7 @@
 #include <vector>
 
 #include "vg_geometry.hpp"
-#include "vg_internal.hpp"
+#include "vg_handle.hpp"
 #include "vg_stereo.hpp"
 #include "vg_stereo_host.hpp"
 
@@ -27,15 +27,12 @@ using namespace vgsh;
 
 }  // namespace
 
-struct vg_stereo {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct vg_stereo : vgi::HandleBase {
     vg_stereo_params prm;
     vgs::StereoGeom g;
-    vgi::DeviceMem<vgs::Poly2> d_table;
-    vgi::DeviceMem<vgs::GeomEntry> d_geom;
-    vgi::DeviceMem<void> d_scratch;
-    int64_t scratch_bytes = 0;
+    vgi::Grow<vgs::Poly2> d_table;
+    vgi::Grow<vgs::GeomEntry> d_geom;
+    vgi::Grow<uint8_t> d_scratch;   // bytes
     int64_t P = 0;
 
     int64_t per_pair() const { return P * (5 * (int64_t)prm.disp_max + 7); }
@@ -50,33 +47,23 @@ struct Bufs {
     int32_t *sum = nullptr, *disp = nullptr;
 };
 
-int ensure_scratch(vg_stereo *s, int64_t bytes)
-{
-    if (bytes <= s->scratch_bytes) return VG_OK;
-    s->scratch_bytes = 0;
-    VG_HIP(s->d_scratch.release());
-    VG_HIP(s->d_scratch.alloc((size_t)bytes));
-    s->scratch_bytes = bytes;
-    return VG_OK;
-}
-
 // carve n pairs' err / step / salient / skip / sum / disparity out of the handle's scratch
 int scratch_bufs(vg_stereo *s, int64_t n, Bufs &b)
 {
     const int64_t P = s->P, D = s->prm.disp_max;
-    if (const int rc = ensure_scratch(s, n * s->per_pair())) return rc;
-    char *p = static_cast<char *>(s->d_scratch.get());
+    if (const int rc = s->d_scratch.grow((size_t)(n * s->per_pair()), "the stereo scratch")) return rc;
+    uint8_t *p = s->d_scratch.get();
     b.sum = reinterpret_cast<int32_t *>(p);
     p += n * P * D * 4;
     b.disp = reinterpret_cast<int32_t *>(p);
     p += n * P * 4;
-    b.err = reinterpret_cast<uint8_t *>(p);
+    b.err = p;
     p += n * P * D;
-    b.step = reinterpret_cast<uint8_t *>(p);
+    b.step = p;
     p += n * P;
-    b.sal = reinterpret_cast<uint8_t *>(p);
+    b.sal = p;
     p += n * P;
-    b.skip = reinterpret_cast<uint8_t *>(p);
+    b.skip = p;
     return VG_OK;
 }
 
@@ -189,30 +176,21 @@ int vg_stereo_create(vg_stereo **out, int device, void *hip_stream, const double
     s->P = (int64_t)x_max * y_max;
     std::vector<vgs::Poly2> table(2 * (size_t)(params->num_epipolar_planes + 1));
     if (const int rc = build_geometry(s->g, s->prm, eucm1, eucm2, xi12, table.data())) return rc;
-    if (const int rc = vgi::check_device(device, "stereo")) return rc;
-    s->device = device;
-    s->stream = reinterpret_cast<hipStream_t>(hip_stream);
-    if (hipSetDevice(device) != hipSuccess) return fail(VG_ERR_HIP, "hipSetDevice failed");
-    vgi::StreamDrain drain{s->stream};   // a failure below drains the stream before s is freed
-    if (s->d_table.alloc(table.size() * sizeof(vgs::Poly2)) != hipSuccess || s->d_geom.alloc((size_t)s->P * sizeof(vgs::GeomEntry)) != hipSuccess)
-        return fail(VG_ERR_ALLOC, "device allocation of the stereo geometry failed");
+    if (const int rc = s->open(device, hip_stream, "stereo")) return rc;
+    vgi::Call call(s.get());   // a failure below drains the stream before s is freed
+    if (call.begin() != VG_OK) return fail(VG_ERR_HIP, "hipSetDevice failed");
+    if (const int rc = s->d_table.grow(table.size(), "the stereo geometry")) return rc;
+    if (const int rc = s->d_geom.grow((size_t)s->P, "the stereo geometry")) return rc;
     if (hipMemcpyAsync(s->d_table, table.data(), table.size() * sizeof(vgs::Poly2), hipMemcpyHostToDevice, s->stream) != hipSuccess)
         return fail(VG_ERR_HIP, "curve table upload failed");
     s->g.table = s->d_table;
     hipLaunchKernelGGL(vgs::stereo_geometry_kernel, dim3(blocks_of(s->P, 256)), dim3(256), 0, s->stream, s->g, s->d_geom);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess) return fail(VG_ERR_HIP, "stereo geometry kernel failed");
-    drain.armed = false;
+    if (hipGetLastError() != hipSuccess || call.finish() != VG_OK) return fail(VG_ERR_HIP, "stereo geometry kernel failed");
     *out = s.release();
     return VG_OK;
 }
 
-void vg_stereo_destroy(vg_stereo *s)
-{
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    (void)hipStreamSynchronize(s->stream);
-    delete s;
-}
+void vg_stereo_destroy(vg_stereo *s) { vgi::destroy(s); }
 
 int vg_stereo_size(const vg_stereo *s, int *x_max, int *y_max)
 {
@@ -232,10 +210,10 @@ int vg_stereo_chunk(const vg_stereo *s, int64_t *pairs)
 int vg_stereo_geometry(vg_stereo *s, int32_t *geometry)
 {
     if (!s || !geometry) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    VG_HIP(hipSetDevice(s->device));
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
     VG_HIP(hipMemcpyAsync(geometry, s->d_geom, (size_t)s->P * sizeof(vgs::GeomEntry), hipMemcpyDeviceToDevice, s->stream));
-    VG_HIP(hipStreamSynchronize(s->stream));
-    return VG_OK;
+    return call.finish();
 }
 
 int vg_stereo_curve_cost(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const uint8_t *img2, uint8_t *err, uint8_t *step,
@@ -244,7 +222,8 @@ int vg_stereo_curve_cost(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, con
     if (const int rc = check_call(s, n_pairs, img1, img2)) return rc;
     if (n_pairs > 0 && (!err || !step || !salient || !skip)) return fail(VG_ERR_INVALID_ARGUMENT, "NULL output");
     if (n_pairs == 0) return VG_OK;
-    VG_HIP(hipSetDevice(s->device));
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
     Bufs b;
     b.err = err;
     b.step = step;
@@ -252,8 +231,7 @@ int vg_stereo_curve_cost(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, con
     b.skip = skip;
     launch_cost(s, n_pairs, img1, img2, b);
     VG_HIP(hipGetLastError());
-    VG_HIP(hipStreamSynchronize(s->stream));
-    return VG_OK;
+    return call.finish();
 }
 
 int vg_stereo_aggregate(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const uint8_t *img2, int32_t *total, int32_t *disparity)
@@ -261,13 +239,14 @@ int vg_stereo_aggregate(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, cons
     if (const int rc = check_call(s, n_pairs, img1, img2)) return rc;
     if (n_pairs > 0 && !total) return fail(VG_ERR_INVALID_ARGUMENT, "NULL output");
     if (n_pairs == 0) return VG_OK;
-    VG_HIP(hipSetDevice(s->device));
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
     // scratch for what the caller does not supply: the error volume, step / salient / skip, and the winner if disparity is NULL
     const int64_t np = n_pairs * s->P;
     const int64_t bytes = np * (s->prm.disp_max + 3), pad = (4 - bytes % 4) % 4;   // pad: aligns the winner behind the byte buffers
-    if (const int rc = ensure_scratch(s, bytes + (disparity ? 0 : pad + np * 4))) return rc;
+    if (const int rc = s->d_scratch.grow((size_t)(bytes + (disparity ? 0 : pad + np * 4)), "the stereo scratch")) return rc;
     Bufs b;
-    b.err = static_cast<uint8_t *>(s->d_scratch.get());
+    b.err = s->d_scratch.get();
     b.step = b.err + np * s->prm.disp_max;
     b.sal = b.step + np;
     b.skip = b.sal + np;
@@ -276,8 +255,7 @@ int vg_stereo_aggregate(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, cons
     launch_cost(s, n_pairs, img1, img2, b);
     launch_agg(s, n_pairs, b, true);
     VG_HIP(hipGetLastError());
-    VG_HIP(hipStreamSynchronize(s->stream));
-    return VG_OK;
+    return call.finish();
 }
 
 int vg_stereo_compute(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const uint8_t *img2, double *depth, double *sigma,
@@ -285,7 +263,8 @@ int vg_stereo_compute(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const 
 {
     if (const int rc = check_call(s, n_pairs, img1, img2)) return rc;
     if (n_pairs == 0) return VG_OK;
-    VG_HIP(hipSetDevice(s->device));
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
     const int64_t chunk = std::min<int64_t>(s->chunk(), n_pairs);
     const int64_t P = s->P, img = (int64_t)s->prm.u_max * s->prm.v_max;
     Bufs b;
@@ -299,8 +278,7 @@ int vg_stereo_compute(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const 
         launch_depth(s, n, c, depth ? depth + first * P : nullptr, sigma ? sigma + first * P : nullptr, cost ? cost + first * P : nullptr);
         VG_HIP(hipGetLastError());
     }
-    VG_HIP(hipStreamSynchronize(s->stream));
-    return VG_OK;
+    return call.finish();
 }
 
 int vg_stereo_curve_walk(const double *poly6, int u, int v, int eu, int ev, int step_mult, int steps, int32_t *uv)

@@ -7,7 +7,7 @@ import ctypes
 import numpy as np
 
 from . import capi
-from . import stereo as _stereo
+from ._handle import Handle, _is_cuda, _vec
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -18,54 +18,41 @@ FILTER_COUNTS = ("examined", "cleared", "smoothed")
 
 def pose_inverse(xi):
     """Transformation::inverse of [t, rotvec], with the library's arithmetic"""
-    a, out = _stereo._vec(xi, 6, "xi"), np.zeros(6)
+    a, out = _vec(xi, 6, "xi"), np.zeros(6)
     capi.check(capi.load().vg_transform_inverse(a.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
     return out
 
 
 def pose_in_frame(base, xi):
     """Transformation::inverseCompose: the pose xi re-expressed in the frame `base` (both given in one common frame)"""
-    a, b, out = _stereo._vec(base, 6, "base"), _stereo._vec(xi, 6, "xi"), np.zeros(6)
+    a, b, out = _vec(base, 6, "base"), _vec(xi, 6, "xi"), np.zeros(6)
     capi.check(capi.load().vg_transform_inverse_compose(a.ctypes.data_as(_dp), b.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
     return out
 
 
-class DepthFusion:
+class DepthFusion(Handle):
     """A vg_depth_fusion handle on one device, for the maps of one EUCM camera and one ScaleParameters (`params`: a
     vg_stereo_params or vg_motion_stereo_params; only the scale fields are read).  Maps are (depth, sigma, cost) float64 CUDA
     tensors, one [y_max, x_max] map or a batch [n, y_max, x_max].  The handle's stream is torch's current stream of the device
     at creation; each call first makes it wait for the caller's current stream and is complete when it returns.  The counters
     of the last call are left in self.counts (int64 [n, 6], [n, 5] or [n, 3]: WARP_COUNTS, MERGE_COUNTS, FILTER_COUNTS)."""
 
+    _destroy = "vg_depth_fusion_destroy"
+
     def __init__(self, eucm, params, device=0):
         import torch
 
-        self._c = _stereo._vec(eucm, 6, "eucm")
+        self._c = _vec(eucm, 6, "eucm")
         self.device = torch.device("cuda", device)
         self.params = params.stereo if isinstance(params, capi.MotionStereoParams) else params
         if not isinstance(self.params, capi.StereoParams):
             raise ValueError("params must be a vg_stereo_params or a vg_motion_stereo_params")
         self.counts = None
         L = capi.load()
-        h = ctypes.c_void_p()
-        self._stream = torch.cuda.current_stream(self.device)
-        capi.check(L.vg_depth_fusion_create(ctypes.byref(h), self.device.index, ctypes.c_void_p(self._stream.cuda_stream),
-                                            self._c.ctypes.data_as(_dp), ctypes.byref(self.params)))
-        self._h = h
+        self._open(L.vg_depth_fusion_create, self._c.ctypes.data_as(_dp), ctypes.byref(self.params))
         xm, ym = ctypes.c_int(), ctypes.c_int()
-        capi.check(L.vg_depth_fusion_size(h, ctypes.byref(xm), ctypes.byref(ym)))
+        capi.check(L.vg_depth_fusion_size(self._h, ctypes.byref(xm), ctypes.byref(ym)))
         self.x_max, self.y_max = xm.value, ym.value
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            capi.load().vg_depth_fusion_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _maps(self, maps, k, what, contiguous=False):
         """k tensors as [n, y_max, x_max]: (list, single).  contiguous: refuse instead of copying (arrays written in place)"""
@@ -75,7 +62,7 @@ class DepthFusion:
             raise ValueError("%s must be (%s)" % (what, ", ".join(("depth", "sigma", "cost")[:k])))
         out, single = [], None
         for t in list(maps)[:k]:
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64:
+            if not _is_cuda(t, torch.float64):
                 raise ValueError("%s must be float64 CUDA tensors" % what)
             one = t.dim() == 2
             if single is not None and one != single:
@@ -89,9 +76,6 @@ class DepthFusion:
             if contiguous and not t.is_contiguous():
                 raise ValueError("%s must be contiguous (it is written in place)" % what)
             out.append(t.contiguous())
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self._stream:
-            self._stream.wait_stream(cur)
         return out, single
 
     def warp(self, xi12, maps):
@@ -108,8 +92,10 @@ class DepthFusion:
             raise ValueError("the transformations must be finite")
         res = [torch.empty_like(src[0]) for _ in range(3)]
         counts = np.zeros((n, 6), dtype=np.int64)
+        self._enter()
         capi.check(capi.load().vg_depth_warp(self._h, n, xi.ctypes.data_as(_dp), *[t.data_ptr() for t in src],
                                              *[t.data_ptr() for t in res], counts.ctypes.data_as(_i64p)))
+        self._leave(*res, *src)
         self.counts = counts
         return tuple(t[0] for t in res) if single else tuple(res)
 
@@ -121,8 +107,10 @@ class DepthFusion:
             raise ValueError("maps and maps2 differ in shape")
         n = a[0].shape[0]
         counts = np.zeros((n, 5), dtype=np.int64)
+        self._enter()
         capi.check(capi.load().vg_depth_merge(self._h, n, a[0].data_ptr(), a[1].data_ptr(), b[0].data_ptr(), b[1].data_ptr(),
                                               counts.ctypes.data_as(_i64p)))
+        self._leave(*a, *b)
         self.counts = counts
         return maps
 
@@ -140,8 +128,10 @@ class DepthFusion:
             if single_out != single or res[0].shape != src[0].shape:
                 raise ValueError("out and maps differ in shape")
         counts = np.zeros((n, 3), dtype=np.int64)
+        self._enter()
         capi.check(capi.load().vg_depth_filter_noise(self._h, n, src[0].data_ptr(), src[1].data_ptr(), res[0].data_ptr(),
                                                      res[1].data_ptr(), counts.ctypes.data_as(_i64p)))
+        self._leave(*res, *src)
         self.counts = counts
         got = tuple(t[0] for t in res) if single else tuple(res)
         return got + tuple(maps[2:]) if out is None else tuple(out)

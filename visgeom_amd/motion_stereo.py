@@ -7,6 +7,7 @@ import numpy as np
 
 from . import capi
 from . import stereo as _stereo
+from ._handle import Handle, _is_cuda, _u8_images, _vec
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _STEREO_FIELDS = {n for n, _ in capi.StereoParams._fields_}
@@ -49,59 +50,36 @@ def make_params(**kw):
     return p
 
 
-class MotionStereo:
+class MotionStereo(Handle):
     """A vg_motion_stereo handle on one device.  set_base() takes the key frame(s); compute() pairs key frame k with img2[k]
     under the pose xi12[k] and returns the new (depth, sigma, cost).  The handle's stream is torch's current stream of the
     device at creation; each call first makes it wait for the caller's current stream and is complete when it returns."""
 
+    _destroy = "vg_motion_stereo_destroy"
+
     def __init__(self, eucm1, eucm2, params, device=0):
         import torch
 
-        self._c = [_stereo._vec(eucm1, 6, "eucm1"), _stereo._vec(eucm2, 6, "eucm2")]
+        self._c = [_vec(eucm1, 6, "eucm1"), _vec(eucm2, 6, "eucm2")]
         self.device = torch.device("cuda", device)
         self.params = params
         self.counts = None
         self.n_base = 0
         L = capi.load()
-        h = ctypes.c_void_p()
-        self._stream = torch.cuda.current_stream(self.device)
-        capi.check(L.vg_motion_stereo_create(ctypes.byref(h), self.device.index, ctypes.c_void_p(self._stream.cuda_stream),
-                                             *[c.ctypes.data_as(_dp) for c in self._c], ctypes.byref(params)))
-        self._h = h
+        self._open(L.vg_motion_stereo_create, *[c.ctypes.data_as(_dp) for c in self._c], ctypes.byref(params))
         xm, ym = ctypes.c_int(), ctypes.c_int()
-        capi.check(L.vg_motion_stereo_size(h, ctypes.byref(xm), ctypes.byref(ym)))
+        capi.check(L.vg_motion_stereo_size(self._h, ctypes.byref(xm), ctypes.byref(ym)))
         self.x_max, self.y_max = xm.value, ym.value
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            capi.load().vg_motion_stereo_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _images(self, img):
-        import torch
-
-        if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.uint8:
-            raise ValueError("images must be uint8 CUDA tensors")
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self._stream:
-            self._stream.wait_stream(cur)
-        single = img.dim() == 2
-        a = img[None] if single else img
-        sp = self.params.stereo
-        if a.dim() != 3 or a.shape[1] != sp.v_max or a.shape[2] != sp.u_max:
-            raise ValueError("images must be [vMax, uMax] or [n, vMax, uMax] = [%d, %d]" % (sp.v_max, sp.u_max))
-        return a.contiguous(), single
+        return _u8_images(img, self.params.stereo.v_max, self.params.stereo.u_max, "images")
 
     def set_base(self, img1):
         """setBaseImage of one key frame [vMax, uMax] or n key frames [n, vMax, uMax]"""
         a, _ = self._images(img1)
+        self._enter()
         capi.check(capi.load().vg_motion_stereo_set_base(self._h, a.shape[0], a.data_ptr()))
+        self._leave(a)
         self.n_base = a.shape[0]
 
     def _call(self, xi12, img2, prior):
@@ -118,7 +96,7 @@ class MotionStereo:
                 raise ValueError("prior must be (depth, sigma, cost)")
             pr = []
             for t in prior:
-                if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64:
+                if not _is_cuda(t, torch.float64):
                     raise ValueError("the prior must be float64 CUDA tensors")
                 t = t[None] if single and t.dim() == 2 else t
                 if tuple(t.shape) != (n, self.y_max, self.x_max):
@@ -141,9 +119,11 @@ class MotionStereo:
                 if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (n, self.y_max, self.x_max):
                     raise ValueError("out must be contiguous float64 CUDA tensors [n, y_max, x_max]")
         counts = np.zeros((n, 6), dtype=np.int64)
+        self._enter()
         capi.check(capi.load().vg_motion_stereo_compute(
             self._h, n, xi.ctypes.data_as(_dp), b.data_ptr(), *[t.data_ptr() if t is not None else None for t in pr],
             *[t.data_ptr() for t in res], counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        self._leave(*res, b, *pr)
         self.counts = counts
         return tuple(t[0] for t in res) if single else tuple(res)
 
@@ -153,8 +133,9 @@ class MotionStereo:
 
         sp = self.params.stereo
         m = torch.empty((self.n_base, sp.v_max, sp.u_max), dtype=torch.uint8, device=self.device)
+        self._enter()
         capi.check(capi.load().vg_motion_stereo_mask(self._h, m.data_ptr()))
-        return m
+        return self._leave(m)
 
     def select(self, xi12, img2, prior=None):
         """the per-pixel stage record, int32 [n, y_max, x_max, 16] (fields: RECORD)"""
@@ -162,6 +143,8 @@ class MotionStereo:
 
         b, single, n, xi, pr = self._call(xi12, img2, prior)
         rec = torch.empty((n, self.y_max, self.x_max, 16), dtype=torch.int32, device=self.device)
+        self._enter()
         capi.check(capi.load().vg_motion_stereo_select(self._h, n, xi.ctypes.data_as(_dp), b.data_ptr(),
                                                        *[t.data_ptr() if t is not None else None for t in pr], rec.data_ptr()))
+        self._leave(rec, b, *pr)
         return rec[0] if single else rec

@@ -9,25 +9,27 @@ import ctypes
 import numpy as np
 
 from . import capi
-from . import stereo as _stereo
+from ._handle import Handle, _is_cuda, _u8_images, _vec
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _i32p = ctypes.POINTER(ctypes.c_int32)
 REPORT = ("iterations", "initial_cost", "final_cost", "termination")
 
 
-class Photometric:
+class Photometric(Handle):
     """A vg_photometric handle on one device: one EUCM camera, the depth map geometry of `params` (a vg_stereo_params or
     vg_motion_stereo_params; only the scale fields are read), xi_base_cam, the image size and num_scales pyramid levels.
     Images are uint8 CUDA tensors [height, width] (targets: [n, height, width]), the depth map a float64 CUDA tensor [y_max,
     x_max].  The handle's stream is torch's current stream of the device at creation; each call first makes it wait for the
     caller's current stream (where the inputs were produced and the outputs are allocated) and is complete when it returns."""
 
+    _destroy = "vg_photometric_destroy"
+
     def __init__(self, eucm, params, xi_base_cam, width, height, num_scales=5, device=0):
         import torch
 
-        self._c = _stereo._vec(eucm, 6, "eucm")
-        self._xbc = _stereo._vec(xi_base_cam, 6, "xi_base_cam")
+        self._c = _vec(eucm, 6, "eucm")
+        self._xbc = _vec(xi_base_cam, 6, "xi_base_cam")
         self.device = torch.device("cuda", device)
         self.params = params.stereo if isinstance(params, capi.MotionStereoParams) else params
         if not isinstance(self.params, capi.StereoParams):
@@ -35,60 +37,22 @@ class Photometric:
         self.width, self.height, self.num_scales = int(width), int(height), int(num_scales)
         self.n_targets = 0
         L = capi.load()
-        h = ctypes.c_void_p()
-        self._stream = torch.cuda.current_stream(self.device)
-        capi.check(L.vg_photometric_create(ctypes.byref(h), self.device.index, ctypes.c_void_p(self._stream.cuda_stream),
-                                           self._c.ctypes.data_as(_dp), ctypes.byref(self.params), self._xbc.ctypes.data_as(_dp),
-                                           self.width, self.height, self.num_scales))
-        self._h = h
+        self._open(L.vg_photometric_create, self._c.ctypes.data_as(_dp), ctypes.byref(self.params), self._xbc.ctypes.data_as(_dp),
+                   self.width, self.height, self.num_scales)
         self.sizes = []   # (width, height) per level
         for i in range(self.num_scales):
             w, hh = ctypes.c_int(), ctypes.c_int()
-            capi.check(L.vg_photometric_level_size(h, i, ctypes.byref(w), ctypes.byref(hh)))
+            capi.check(L.vg_photometric_level_size(self._h, i, ctypes.byref(w), ctypes.byref(hh)))
             self.sizes.append((w.value, hh.value))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            capi.load().vg_photometric_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _enter(self):
-        import torch
-
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self._stream:
-            self._stream.wait_stream(cur)
-
-    def _leave(self, *tensors):
-        import torch
-
-        if torch.cuda.current_stream(self.device) != self._stream:
-            for t in tensors:
-                if t is not None:
-                    t.record_stream(self._stream)
-        return tensors[0] if len(tensors) == 1 else tensors
-
-    def _image(self, img, what):
-        import torch
-
-        if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.uint8 or tuple(img.shape[-2:]) != (self.height, self.width):
-            raise ValueError("%s must be a uint8 CUDA tensor [..., %d, %d]" % (what, self.height, self.width))
-        return img.contiguous()
 
     def set_base(self, img, depth):
         """the key frame: its image and its depth map; builds the pyramid with gradients and the data pack of every scale"""
         import torch
 
-        img = self._image(img, "img")
-        if img.dim() != 2:
+        img, single = _u8_images(img, self.height, self.width, "img")
+        if not single:
             raise ValueError("img must be [height, width]")
-        if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dtype != torch.float64 or depth.dim() != 2:
+        if not _is_cuda(depth, torch.float64) or depth.dim() != 2:
             raise ValueError("depth must be a float64 CUDA tensor [y_max, x_max]")
         p = self.params
         x_max = (p.u_max - 2 * p.u0) // p.scale + 1 if p.equal_margins else p.x_max
@@ -102,10 +66,7 @@ class Photometric:
 
     def set_targets(self, imgs):
         """the images the poses are estimated for: [n, height, width] or one [height, width]"""
-        imgs = self._image(imgs, "imgs")
-        imgs = imgs[None] if imgs.dim() == 2 else imgs
-        if imgs.dim() != 3:
-            raise ValueError("imgs must be [n, height, width]")
+        imgs, _ = _u8_images(imgs, self.height, self.width, "imgs")
         self._enter()
         capi.check(capi.load().vg_photometric_set_targets(self._h, imgs.shape[0], imgs.data_ptr()))
         self.n_targets = imgs.shape[0]
@@ -241,7 +202,7 @@ class Photometric:
 
 def mi_odometry(xi_odom, xi_prior, xi):
     """the odometry term of MutualInformationOdom at the pose xi, host arithmetic: (cost, gradient [6])"""
-    a, p, x = (_stereo._vec(v, 6, name) for v, name in ((xi_odom, "xi_odom"), (xi_prior, "xi_prior"), (xi, "xi")))
+    a, p, x = (_vec(v, 6, name) for v, name in ((xi_odom, "xi_odom"), (xi_prior, "xi_prior"), (xi, "xi")))
     cost, grad = ctypes.c_double(), np.zeros(6)
     capi.check(capi.load().vg_mi_odometry(a.ctypes.data_as(_dp), p.ctypes.data_as(_dp), x.ctypes.data_as(_dp), ctypes.byref(cost),
                                                       grad.ctypes.data_as(_dp)))

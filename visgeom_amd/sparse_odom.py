@@ -8,7 +8,7 @@ import ctypes
 import numpy as np
 
 from . import capi
-from . import stereo as _stereo
+from ._handle import Handle, _f64_cuda, _is_cuda, _u8_images, _vec
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -30,78 +30,36 @@ def default_params(**changes):
     return p
 
 
-class SparseOdometry:
+class SparseOdometry(Handle):
     """A vg_sparse_odom handle on one device: one EUCM camera, xi_base_cam and one image size.  Images are uint8 CUDA tensors
     [height, width] or [n, height, width]; rays, pixels and sizes float64 CUDA tensors; poses numpy [6] = [t, rotvec].  The
     handle's stream is torch's current stream of the device at creation; each call first makes it wait for the caller's
     current stream and is complete when it returns."""
 
+    _destroy = "vg_sparse_odom_destroy"
+
     def __init__(self, eucm, xi_base_cam, width, height, params=None, device=0):
         import torch
 
-        self._c = _stereo._vec(eucm, 6, "eucm")
-        self._xbc = _stereo._vec(xi_base_cam, 6, "xi_base_cam")
+        self._c = _vec(eucm, 6, "eucm")
+        self._xbc = _vec(xi_base_cam, 6, "xi_base_cam")
         self.device = torch.device("cuda", device)
         self.params = params if params is not None else default_params()
         if not isinstance(self.params, capi.SparseOdomParams):
             raise ValueError("params must be a vg_sparse_odom_params (default_params())")
         self.width, self.height = int(width), int(height)
         self.max_features = self.params.max_features
-        h = ctypes.c_void_p()
-        self._stream = torch.cuda.current_stream(self.device)
-        capi.check(capi.load().vg_sparse_odom_create(ctypes.byref(h), self.device.index, ctypes.c_void_p(self._stream.cuda_stream),
-                                                     self._c.ctypes.data_as(_dp), self._xbc.ctypes.data_as(_dp), self.width, self.height,
-                                                     ctypes.byref(self.params)))
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            capi.load().vg_sparse_odom_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _enter(self):
-        import torch
-
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self._stream:
-            self._stream.wait_stream(cur)
-
-    def _leave(self, *tensors):
-        import torch
-
-        if torch.cuda.current_stream(self.device) != self._stream:
-            for t in tensors:
-                if t is not None:
-                    t.record_stream(self._stream)
-        return tensors[0] if len(tensors) == 1 else tensors
+        self._open(capi.load().vg_sparse_odom_create, self._c.ctypes.data_as(_dp), self._xbc.ctypes.data_as(_dp), self.width, self.height,
+                   ctypes.byref(self.params))
 
     def _images(self, img):
-        import torch
-
-        if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.uint8 or img.dim() not in (2, 3) or \
-                tuple(img.shape[-2:]) != (self.height, self.width):
-            raise ValueError("img must be a uint8 CUDA tensor [n, %d, %d] or [%d, %d]" % (self.height, self.width, self.height, self.width))
-        return (img[None] if img.dim() == 2 else img).contiguous()
-
-    def _f64(self, t, cols, what):
-        import torch
-
-        shape = (cols,) if cols else ()
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or tuple(t.shape[1:]) != shape:
-            raise ValueError("%s must be a float64 CUDA tensor [m%s]" % (what, ", %d" % cols if cols else ""))
-        return t.contiguous()
+        return _u8_images(img, self.height, self.width, "img")[0]
 
     def _points(self, x1, x2, p2, size=None):
-        x1, x2, p2 = self._f64(x1, 3, "x1"), self._f64(x2, 3, "x2"), self._f64(p2, 2, "p2")
+        x1, x2, p2 = _f64_cuda(x1, (3,), "x1"), _f64_cuda(x2, (3,), "x2"), _f64_cuda(p2, (2,), "p2")
         m = x1.shape[0]
         if size is not None:
-            size = self._f64(size, 0, "size")
+            size = _f64_cuda(size, (), "size")
         if x2.shape[0] != m or p2.shape[0] != m or (size is not None and size.shape[0] != m):
             raise ValueError("x1, x2, p2 and size must have the same length")
         return x1, x2, p2, size, m
@@ -144,8 +102,7 @@ class SparseOdometry:
         import torch
 
         for d in (desc1, desc2):
-            if not isinstance(d, torch.Tensor) or not d.is_cuda or d.dtype != torch.float32 or d.dim() != 3 or \
-                    tuple(d.shape[1:]) != (self.max_features, DESC):
+            if not _is_cuda(d, torch.float32) or d.dim() != 3 or tuple(d.shape[1:]) != (self.max_features, DESC):
                 raise ValueError("descriptors must be float32 CUDA tensors [n, %d, %d]" % (self.max_features, DESC))
         desc1, desc2 = desc1.contiguous(), desc2.contiguous()
         n = desc1.shape[0]
@@ -168,7 +125,7 @@ class SparseOdometry:
         off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
         if off.shape[0] < 2 or off[0] != 0 or off[-1] > m or (np.diff(off) < 0).any():
             raise ValueError("offsets must rise from 0 to at most the number of points")
-        xo = _stereo._vec(xi_odom, 6, "xi_odom")
+        xo = _vec(xi_odom, 6, "xi_odom")
         nb = off.shape[0] - 1
         out, rep = np.zeros((nb, 6)), np.zeros((nb, 4))
         self._enter()
@@ -203,7 +160,7 @@ class SparseOdometry:
         import torch
 
         x1, x2, p2, size, m = self._points(x1, x2, p2, size)
-        xo = _stereo._vec(xi_odom, 6, "xi_odom")
+        xo = _vec(xi_odom, 6, "xi_odom")
         s = self._samples(samples)
         out, rep = np.zeros(6), np.zeros(capi.SPARSE_ODOM_REPORT)
         mask = torch.zeros((m,), dtype=torch.uint8, device=self.device)
@@ -219,7 +176,7 @@ class SparseOdometry:
         img = self._images(img)
         if img.shape[0] != 1:
             raise ValueError("feed takes one image")
-        xo = _stereo._vec(xi_odom_new, 6, "xi_odom_new")
+        xo = _vec(xi_odom_new, 6, "xi_odom_new")
         s = self._samples(samples)
         out, rep = np.zeros(6), np.zeros(capi.SPARSE_ODOM_FEED_REPORT)
         self._enter()

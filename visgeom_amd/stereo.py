@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 
 from . import capi
+from ._handle import Handle, _u8_images, _vec   # _vec: other modules and tests take it from here
 
 _dp = ctypes.POINTER(ctypes.c_double)
 
@@ -72,19 +73,14 @@ def make_params(**kw):
     return p
 
 
-def _vec(a, n, what):
-    a = np.ascontiguousarray(a, dtype=np.float64).ravel()
-    if a.size != n:
-        raise ValueError("%s must have %d values" % (what, n))
-    return a
-
-
-class Stereo:
+class Stereo(Handle):
     """A vg_stereo handle on one device: create once per calibrated pair, then compute any number of image batches.
 
     The handle's stream is torch's current stream of the device when the handle is created, and every later call runs on it.
     Each call first makes that stream wait for the caller's current stream, so images produced there are ready; the outputs
     are complete when a call returns (the library synchronises its stream)."""
+
+    _destroy = "vg_stereo_destroy"
 
     def __init__(self, eucm1, eucm2, xi12, params, device=0):
         import torch
@@ -93,43 +89,16 @@ class Stereo:
         self.device = torch.device("cuda", device)
         self.params = params
         L = capi.load()
-        h = ctypes.c_void_p()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        capi.check(L.vg_stereo_create(ctypes.byref(h), self.device.index, ctypes.c_void_p(stream),
-                                      *[c.ctypes.data_as(_dp) for c in self._c], ctypes.byref(params)))
-        self._h = h
-        self._stream = torch.cuda.current_stream(self.device)
+        self._open(L.vg_stereo_create, *[c.ctypes.data_as(_dp) for c in self._c], ctypes.byref(params))
         xm, ym = ctypes.c_int(), ctypes.c_int()
-        capi.check(L.vg_stereo_size(h, ctypes.byref(xm), ctypes.byref(ym)))
+        capi.check(L.vg_stereo_size(self._h, ctypes.byref(xm), ctypes.byref(ym)))
         self.x_max, self.y_max = xm.value, ym.value
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            capi.load().vg_stereo_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _images(self, img1, img2):
-        import torch
-
-        for im in (img1, img2):
-            if not isinstance(im, torch.Tensor) or not im.is_cuda or im.dtype != torch.uint8:
-                raise ValueError("images must be uint8 CUDA tensors")
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self._stream:
-            self._stream.wait_stream(cur)
+        (a, single), (b, _) = (_u8_images(im, self.params.v_max, self.params.u_max, "images") for im in (img1, img2))
         if img1.shape != img2.shape:
             raise ValueError("the two image batches differ in shape")
-        single = img1.dim() == 2
-        a, b = (img1[None], img2[None]) if single else (img1, img2)
-        if a.dim() != 3 or a.shape[1] != self.params.v_max or a.shape[2] != self.params.u_max:
-            raise ValueError("images must be [vMax, uMax] or [n, vMax, uMax] = [%d, %d]" % (self.params.v_max, self.params.u_max))
-        return a.contiguous(), b.contiguous(), single
+        return a, b, single
 
     def _empty(self, n, *tail, dtype):
         import torch
@@ -145,9 +114,11 @@ class Stereo:
         n = a.shape[0]
         depth, sigma, cost = (self._empty(n, dtype=torch.float64) for _ in range(3))
         disp = self._empty(n, dtype=torch.int32)
+        self._enter()
         capi.check(capi.load().vg_stereo_compute(self._h, n, a.data_ptr(), b.data_ptr(), depth.data_ptr(), sigma.data_ptr(),
                                                  cost.data_ptr(), disp.data_ptr()))
         out = (depth, sigma, cost, disp)
+        self._leave(*out, a, b)
         return tuple(t[0] for t in out) if single else out
 
     def geometry(self):
@@ -155,8 +126,9 @@ class Stereo:
         import torch
 
         g = torch.empty((self.y_max, self.x_max, 8), dtype=torch.int32, device=self.device)
+        self._enter()
         capi.check(capi.load().vg_stereo_geometry(self._h, g.data_ptr()))
-        return g
+        return self._leave(g)
 
     def curve_cost(self, img1, img2):
         """computeCurveCost: err uint8 [n, y, x, disp_max], step, salient, skip uint8 [n, y, x]"""
@@ -166,8 +138,10 @@ class Stereo:
         n = a.shape[0]
         err = self._empty(n, self.params.disp_max, dtype=torch.uint8)
         step, sal, skip = (self._empty(n, dtype=torch.uint8) for _ in range(3))
+        self._enter()
         capi.check(capi.load().vg_stereo_curve_cost(self._h, n, a.data_ptr(), b.data_ptr(), err.data_ptr(), step.data_ptr(),
                                                     sal.data_ptr(), skip.data_ptr()))
+        self._leave(err, step, sal, skip, a, b)
         return err, step, sal, skip
 
     def aggregate(self, img1, img2):
@@ -178,7 +152,9 @@ class Stereo:
         n = a.shape[0]
         tot = self._empty(n, self.params.disp_max, dtype=torch.int32)
         disp = self._empty(n, dtype=torch.int32)
+        self._enter()
         capi.check(capi.load().vg_stereo_aggregate(self._h, n, a.data_ptr(), b.data_ptr(), tot.data_ptr(), disp.data_ptr()))
+        self._leave(tot, disp, a, b)
         return tot, disp
 
     def chunk(self):
