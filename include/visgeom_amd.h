@@ -946,6 +946,55 @@ int vg_sparse_odom_feed(vg_sparse_odom *h, const uint8_t *img, const double *xi_
 int vg_sparse_odom_increment(const vg_sparse_odom *h, double *xi6);
 int vg_sparse_odom_integrated(const vg_sparse_odom *h, double *xi6);
 
+/* =====================================================================================
+ * 14. Synthetic scene renderer: the reference's RenderDevice (src/render/render.cpp) -- the source of images with exact poses
+ *     and exact depth its stereo, mapping and odometry tests are fed and scored from.  The world is textured rectangles in
+ *     front of a panoramic background (src/render/plane.cpp, background.cpp); a view is the EUCM image of it at a camera pose,
+ *     with the hit buffers behind it: per pixel the object index, the texture coordinates and the range along the ray
+ *     (getDepthBuffer, the ground truth).  fillBuffers tests every object per pixel in the order given and keeps the nearest;
+ *     fillImage takes the texture-space footprint of a pixel from its neighbours on the same object and filters the texture over
+ *     it with Texture::sample (texture.cpp:28-70): one bicubic sample where the footprint is below a texel, else up to 24 x 24
+ *     bilinear taps weighted by the separable kernels of LookupFilter (aa_filter_lt.cpp).  All arithmetic is FP64 in the
+ *     reference's order and the buffers are its narrow types (int16 index, float u, v, depth): a view is bit-identical from run
+ *     to run and does not depend on the batch it is part of.  Every call is synchronous on the handle's stream and checks its
+ *     arguments before HIP is touched.  Deviations: DESIGN.md section 9, "Scene renderer".
+ * ===================================================================================== */
+#define VG_RENDER_BACKGROUND 0
+#define VG_RENDER_PLANE 1
+#define VG_RENDER_MAX_PLANES 64
+#define VG_RENDER_MIN_SIDE 2             /* of the image and of every texture, in pixels */
+#define VG_RENDER_MAX_SIDE 16384
+#define VG_RENDER_COUNTS 5               /* pixels not reconstructed, covered by nothing, background, plane; single bicubic tap */
+typedef struct vg_render vg_render;
+typedef struct vg_render_object {
+    int kind;               /* VG_RENDER_BACKGROUND or VG_RENDER_PLANE */
+    const uint8_t *texture; /* HOST [rows][cols], 8-bit grey; copied at creation */
+    int cols, rows;
+    double pose[6];         /* plane: [t, rotvec] of the plane in the world; its x and y axes span it, the centre is at t */
+    double width, height;   /* plane: its extent in metres along x and y; the texture covers it */
+} vg_render_object;
+/* A world seen by one EUCM camera (eucm: HOST 6 intrinsics) in images of width x height pixels.  objects[0] must be the
+ * background (its texture is the panorama: yaw across, pitch down, 2 pi each; range 150 everywhere), objects[1 ..] planes, at
+ * most VG_RENDER_MAX_PLANES.  Image and texture sides are in [VG_RENDER_MIN_SIDE, VG_RENDER_MAX_SIDE]; poses are finite, plane
+ * extents positive.  The handle keeps the textures on the device and owns the scratch of its calls. */
+int vg_render_create(vg_render **out, int device, void *hip_stream, const double *eucm, int width, int height, int n_objects,
+                     const vg_render_object *objects);
+void vg_render_destroy(vg_render *h);
+int vg_render_size(const vg_render *h, int *width, int *height);
+/* setCamera: later views use these intrinsics; the image size stays. */
+int vg_render_set_camera(vg_render *h, const double *eucm);
+/* render() of n views, n in [0, 65535]: xi_cam HOST [n][6], the camera's pose in the world as [t, rotvec], every entry finite.
+ * image DEVICE u8 [n][height][width].  Optional DEVICE outputs, each may be NULL: depth float [n][height][width] (the range of
+ * the nearest hit; 1e6 where there is none), index int16 (-1 where there is none; 0 the background, k plane k), u and v float
+ * (texture coordinates of the hit, 0 where there is none).  A pixel no object covers, or that does not reconstruct, is written
+ * as 0.  counts (HOST int64 [n][VG_RENDER_COUNTS], may be NULL): pixels that do not reconstruct, pixels covered by nothing,
+ * background pixels, plane pixels, and covered pixels sampled with the single bicubic tap. */
+int vg_render_views(vg_render *h, int64_t n, const double *xi_cam, uint8_t *image, float *depth, int16_t *index, float *u, float *v,
+                    int64_t *counts);
+/* Host only: the anti-aliasing kernel of `length` taps, length in [1, 24], out HOST [length] -- one row of LookupFilter's table
+ * (sigma 0.55, 600 integral samples) as the device reads it. */
+int vg_render_filter_kernel(int length, double *out);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",
  * "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop", "solver_no_fold_frames",

@@ -243,6 +243,12 @@ SIGNATURES = {
     "vg_sparse_odom_feed": (ctypes.c_int, [_vp, _vp, _dp, _i32p, _dp, _dp]),
     "vg_sparse_odom_increment": (ctypes.c_int, [_vp, _dp]),
     "vg_sparse_odom_integrated": (ctypes.c_int, [_vp, _dp]),
+    "vg_render_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "vg_render_destroy": (None, [_vp]),
+    "vg_render_size": (ctypes.c_int, [_vp, _ip, _ip]),
+    "vg_render_set_camera": (ctypes.c_int, [_vp, _dp]),
+    "vg_render_views": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _vp, _vp, _vp, _vp, _vp, _i64p]),
+    "vg_render_filter_kernel": (ctypes.c_int, [ctypes.c_int, _dp]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),
@@ -279,6 +285,13 @@ class SparseOdomParams(ctypes.Structure):
                 ("prior_lambda_r", ctypes.c_double), ("outlier_gate", ctypes.c_double), ("min_stereo_base", ctypes.c_double)]
 
 
+class RenderObject(ctypes.Structure):
+    """struct vg_render_object"""
+    _fields_ = [("kind", ctypes.c_int), ("texture", ctypes.c_void_p), ("cols", ctypes.c_int), ("rows", ctypes.c_int),
+                ("pose", ctypes.c_double * 6), ("width", ctypes.c_double), ("height", ctypes.c_double)]
+
+
+RENDER_BACKGROUND, RENDER_PLANE, RENDER_MAX_PLANES, RENDER_MIN_SIDE, RENDER_MAX_SIDE, RENDER_COUNTS = 0, 1, 64, 2, 16384, 5
 SPARSE_ODOM_REPORT, SPARSE_ODOM_FEED_REPORT = 8, 12
 SPARSE_ODOM_OK, SPARSE_ODOM_TOO_FEW_MATCHES, SPARSE_ODOM_NO_HYPOTHESIS = 0, 1, 2
 SPARSE_ODOM_FIRST, SPARSE_ODOM_SKIPPED, SPARSE_ODOM_ESTIMATED = 0, 1, 2

@@ -8,6 +8,7 @@
 // DESIGN.md section 5.13.
 #pragma once
 
+#include "vg_bicubic.hpp"
 #include "vg_camera.hpp"
 #include "vg_stereo_device.hpp"
 
@@ -187,38 +188,6 @@ struct EvalArgs {
     double *res, *jac;         // [n][m], [n][m][6] or NULL
     double *partials;          // [n][blocks][kSums]
 };
-
-VGS_HD int clamp_index(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }   // Grid2D::GetValue (include/ceres.h:55-64)
-
-// ceres::CubicHermiteSpline<1>
-VGS_HD void cubic(double p0, double p1, double p2, double p3, double x, double &f, double &dfdx)
-{
-    const double a = 0.5 * (-p0 + 3.0 * p1 - 3.0 * p2 + p3);
-    const double b = 0.5 * (2.0 * p0 - 5.0 * p1 + 4.0 * p2 - p3);
-    const double c = 0.5 * (-p0 + p2);
-    const double d = p1;
-    f = d + x * (c + x * (b + x * a));
-    dfdx = c + x * (2.0 * b + 3.0 * a * x);
-}
-
-// ceres::BiCubicInterpolator<Grid2D<float>>::Evaluate(r, c): the four rows row - 1 .. row + 2 along the columns, then those
-// four values and their column derivatives along r; the grid clamps its indices (include/ceres.h:55-64)
-VGS_HD void bicubic(const float *img, int w, int h, double r, double c, double &f, double &dfdr, double &dfdc)
-{
-    const int row = (int)floor(r), col = (int)floor(c);
-    double fk[4], dk[4];
-    int cc[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) cc[j] = clamp_index(col - 1 + j, w);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float *p = img + (int64_t)clamp_index(row - 1 + k, h) * w;
-        cubic((double)p[cc[0]], (double)p[cc[1]], (double)p[cc[2]], (double)p[cc[3]], c - col, fk[k], dk[k]);
-    }
-    double unused;
-    cubic(fk[0], fk[1], fk[2], fk[3], r - row, f, dfdr);
-    cubic(dk[0], dk[1], dk[2], dk[3], r - row, dfdc, unused);
-}
 
 // getUMapgin / getVMapgin (local_cost_functions.cpp:66-92)
 VGS_HD double margin_of(double x, double inv_scale, double margin, int size)
