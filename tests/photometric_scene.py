@@ -1,7 +1,9 @@
 """The scene of the photometric tests: tests/stereo_scene.py's textured planes seen by a 256 x 192 EUCM camera, the key
 frame's depth map on a scale-2 grid (the true range, with holes and a few far values so that every depth test of the
 selection is reached), three target views at known poses, and the poses the tests evaluate at.  256 x 192 with three scales
-is the smallest shape at which the 50 / scale margin leaves an interior at every scale (39 x 23 pixels at scale 4)."""
+is the smallest shape at which the 50 / scale margin leaves an interior at every scale (39 x 23 pixels at scale 4).  It is
+one size per level: the sizes at which the kernels' launches change shape (more workgroups than scan threads, packs of exactly a
+wave or a workgroup, eight levels, points outside the target) live in tests/localization_shapes.py."""
 import numpy as np
 
 from tests import photometric_ref as pr
