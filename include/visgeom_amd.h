@@ -995,6 +995,96 @@ int vg_render_views(vg_render *h, int64_t n, const double *xi_cam, uint8_t *imag
  * (sigma 0.55, 600 integral samples) as the device reads it. */
 int vg_render_filter_kernel(int length, double *out);
 
+/* =====================================================================================
+ * 15. Monocular visual odometry: the reference's MonoOdometry (include/localization/mono_odom.h, src/localization/mono_odom.cpp)
+ *     -- wheel-odometry poses and camera images in, one after the other; the pose of the base frame and a key frame depth map
+ *     that improves with every frame out.  The handle owns one each of the pipelines of sections 10 to 13 and builds one
+ *     section 9 object per key frame; images and maps stay on the device between the stages of a frame.  Images are DEVICE u8
+ *     [height][width] with width = u_max and height = v_max of the stereo parameters, maps DEVICE FP64 [y_max][x_max], poses
+ *     HOST [t, rotvec] of the base frame.  Every call is synchronous on the handle's stream and checks its arguments before
+ *     HIP is touched.  Deviations: DESIGN.md section 9, "Monocular odometry".
+ * ===================================================================================== */
+#define VG_MONO_ODOM_BEGIN 0             /* states: no image yet */
+#define VG_MONO_ODOM_SPARSE_INIT 1       /* a first key image, no depth map: waiting for min_init_dist of odometry */
+#define VG_MONO_ODOM_READY 2             /* a key frame with a depth map */
+#define VG_MONO_ODOM_FIRST 0             /* actions of a feed_image call: the first image was kept */
+#define VG_MONO_ODOM_WAITING 1           /* SPARSE_INIT, the odometry has not moved far enough: nothing done */
+#define VG_MONO_ODOM_SPARSE_INIT_KEYFRAME 2 /* sparse odometry gave the motion, SGM the first map */
+#define VG_MONO_ODOM_REFINED 3           /* pose from the photometric solve, map refined by motion stereo and filtered */
+#define VG_MONO_ODOM_KEYFRAME 4          /* pose from the photometric solve, then a new key frame */
+#define VG_MONO_ODOM_DISCARDED 5         /* the photometric pose disagreed with the odometry's scale: the odometry is kept */
+#define VG_MONO_ODOM_REPORT 16           /* state before, state after, action, K, length, length_prior; of the photometric solve the
+                                            iterations over all scales and the finest scale's final cost and vg_termination; six
+                                            counters: of vg_motion_stereo_compute on REFINED (zeros when the refinement was skipped),
+                                            of vg_depth_merge (five) on KEYFRAME, zeros otherwise; the number of key frames */
+typedef struct vg_mono_odom vg_mono_odom;
+typedef struct vg_mono_odom_params {
+    double min_init_dist;      /* MIN_INIT_DIST 0.25: odometry translation that ends SPARSE_INIT */
+    double max_dist;           /* MAX_DIST 0.4: |t(xi_local)| above it asks for a key frame */
+    double max_angle;          /* MAX_ANGLE pi / 4: |rot(xi_local)| above it asks for a key frame */
+    double min_scale_length;   /* 1e-2: the scale of a shorter photometric step is not touched */
+    double max_scale_ratio;    /* 1.2: a step K times shorter than the odometry's, K above it, is discarded */
+    int num_scales;            /* 5: pyramid levels of the photometric solve */
+    vg_motion_stereo_params motion;   /* "stereo_parameters": SGM reads motion.stereo, motion stereo all of it */
+    vg_sparse_odom_params sparse;
+} vg_mono_odom_params;
+void vg_mono_odom_params_default(vg_mono_odom_params *p);
+/* MonoOdometry(ptree): eucm HOST 6 intrinsics, xi_base_cam HOST [6] the camera in the base frame, width x height the image size
+ * (equal to u_max x v_max of params->motion.stereo).  The thresholds must be finite, the distances and the angle not negative,
+ * max_scale_ratio positive; everything else is checked by the creation of the four pipelines, all of them before the device
+ * is asked for.  Allocates the key image and three map triples; later calls allocate only what the pipelines' first calls
+ * and the per-key-frame vg_stereo object need. */
+int vg_mono_odom_create(vg_mono_odom **out, int device, void *hip_stream, const double *eucm, const double *xi_base_cam, int width,
+                        int height, const vg_mono_odom_params *params);
+void vg_mono_odom_destroy(vg_mono_odom *h);
+int vg_mono_odom_size(const vg_mono_odom *h, int *width, int *height, int *x_max, int *y_max);
+/* feedWheelOdometry (:54-61): xi_local = xi_local o xi_odom^-1 o xi_odom_new, xi_odom = xi_odom_new.  The first call only
+ * records xi_odom_new. */
+int vg_mono_odom_feed_wheel_odometry(vg_mono_odom *h, const double *xi_odom_new);
+/* feedImage (:81-173) with pushKeyFrame (:175-216): img DEVICE u8 [height][width]; samples as for vg_sparse_odom_feed (HOST
+ * int32 [ransac_iterations][num_ransac_points] or NULL for the library's draw), passed on in BEGIN and SPARSE_INIT; report HOST
+ * [VG_MONO_ODOM_REPORT] or NULL.  A call in which a stage fails leaves the poses, the state and the map as they were (a frame
+ * writes its maps into scratch and commits last; only the copy of a new key image and motion stereo's set_base, the first
+ * steps of that commit, can still fail, and are not undone). */
+int vg_mono_odom_feed_image(vg_mono_odom *h, const uint8_t *img, const int32_t *samples, double *report);
+/* setDepth (:63-79): depth_image DEVICE float [height][width] (the renderer's depth buffer); map(x, y) = image(v0 + y scale, u0 +
+ * x scale), sigma 0.1 everywhere, the cost left as it is (5 in a map that did not exist).  A cell whose pixel lies outside the
+ * image holds 0.  In SPARSE_INIT the map is replaced by the first key frame's SGM map all the same. */
+int vg_mono_odom_set_depth(vg_mono_odom *h, const float *depth_image);
+/* ScalePhotometric::wrapImage (photometric.cpp:387-415): dst(i, j) = src at the rounded projection of key frame pixel (j, i)'s
+ * point -- the ray of the pixel at the depth of its nearest map cell -- seen from the pose xi (HOST [6] of the base frame in
+ * the key frame's; NULL: the current xi_local); 0 where the cell lies outside the map, its depth is below MIN_DEPTH, the pixel
+ * does not reconstruct, the point does not project or lands outside src.  depth DEVICE FP64 [y_max][x_max], NULL: the
+ * handle's map.  src, dst DEVICE u8 [height][width], not overlapping.  One thread per pixel, a pure gather: bit-identical
+ * from run to run. */
+int vg_mono_odom_warp_image(vg_mono_odom *h, const uint8_t *src, const double *xi, const double *depth, uint8_t *dst);
+int vg_mono_odom_state(const vg_mono_odom *h, int *state);
+int vg_mono_odom_xi_local(const vg_mono_odom *h, double *xi6);
+int vg_mono_odom_xi_global(const vg_mono_odom *h, double *xi6);
+int vg_mono_odom_xi_composed(const vg_mono_odom *h, double *xi6);   /* xi_global o xi_local */
+/* transfVec: the number of key frames so far and the pose of key frame k in key frame k - 1 (zero for k = 0) */
+int vg_mono_odom_num_keyframes(const vg_mono_odom *h, int64_t *count);
+int vg_mono_odom_keyframe_increment(const vg_mono_odom *h, int64_t k, double *xi6);
+/* The current map: copied device to device into the caller's arrays (each may be NULL), or as borrowed DEVICE pointers that
+ * stay valid until the next feed_image or set_depth.  VG_ERR_STATE while there is no map. */
+int vg_mono_odom_get_map(vg_mono_odom *h, double *depth, double *sigma, double *cost);
+int vg_mono_odom_map(const vg_mono_odom *h, const double **depth, const double **sigma, const double **cost);
+/* Host only -- the state machine's arithmetic, the code the feed calls run:
+ *   integrate        xi_local o xi_odom_old^-1 o xi_odom_new
+ *   normalize_scale  zetaPrior = old^-1 o prior, zeta = old^-1 o vo, K = |t(zetaPrior)| / |t(zeta)| (*K, may be NULL; not finite
+ *                    for a pure rotation).  |t(zeta)| > min_scale_length and K > max_scale_ratio: out = old o zetaPrior and
+ *                    *discarded = 1.  Otherwise *discarded = 0 and out = old o zeta, t(zeta) times K first when |t(zeta)| >
+ *                    min_scale_length.
+ *   needs_keyframe   *needed = |t| > max_dist or |rot| > max_angle
+ *   camera_motion    xi_base_cam^-1 o xi o xi_base_cam
+ *   compose          a o b */
+int vg_mono_odom_integrate(const double *xi_local, const double *xi_odom_old, const double *xi_odom_new, double *out6);
+int vg_mono_odom_normalize_scale(const vg_mono_odom_params *params, const double *xi_local_old, const double *xi_local_prior,
+                                 const double *xi_local_vo, double *out6, double *K, int *discarded);
+int vg_mono_odom_needs_keyframe(const vg_mono_odom_params *params, const double *xi_local, int *needed);
+int vg_mono_odom_camera_motion(const double *xi_base_cam, const double *xi, double *out6);
+int vg_mono_odom_compose(const double *a6, const double *b6, double *out6);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",
  * "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop", "solver_no_fold_frames",

@@ -249,6 +249,27 @@ SIGNATURES = {
     "vg_render_set_camera": (ctypes.c_int, [_vp, _dp]),
     "vg_render_views": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _vp, _vp, _vp, _vp, _vp, _i64p]),
     "vg_render_filter_kernel": (ctypes.c_int, [ctypes.c_int, _dp]),
+    "vg_mono_odom_params_default": (None, [_vp]),
+    "vg_mono_odom_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, _dp, _dp, ctypes.c_int, ctypes.c_int, _vp]),
+    "vg_mono_odom_destroy": (None, [_vp]),
+    "vg_mono_odom_size": (ctypes.c_int, [_vp, _ip, _ip, _ip, _ip]),
+    "vg_mono_odom_feed_wheel_odometry": (ctypes.c_int, [_vp, _dp]),
+    "vg_mono_odom_feed_image": (ctypes.c_int, [_vp, _vp, _i32p, _dp]),
+    "vg_mono_odom_set_depth": (ctypes.c_int, [_vp, _vp]),
+    "vg_mono_odom_warp_image": (ctypes.c_int, [_vp, _vp, _dp, _vp, _vp]),
+    "vg_mono_odom_state": (ctypes.c_int, [_vp, _ip]),
+    "vg_mono_odom_xi_local": (ctypes.c_int, [_vp, _dp]),
+    "vg_mono_odom_xi_global": (ctypes.c_int, [_vp, _dp]),
+    "vg_mono_odom_xi_composed": (ctypes.c_int, [_vp, _dp]),
+    "vg_mono_odom_num_keyframes": (ctypes.c_int, [_vp, _i64p]),
+    "vg_mono_odom_keyframe_increment": (ctypes.c_int, [_vp, ctypes.c_int64, _dp]),
+    "vg_mono_odom_get_map": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "vg_mono_odom_map": (ctypes.c_int, [_vp, _vpp, _vpp, _vpp]),
+    "vg_mono_odom_integrate": (ctypes.c_int, [_dp, _dp, _dp, _dp]),
+    "vg_mono_odom_normalize_scale": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "vg_mono_odom_needs_keyframe": (ctypes.c_int, [_vp, _dp, _ip]),
+    "vg_mono_odom_camera_motion": (ctypes.c_int, [_dp, _dp, _dp]),
+    "vg_mono_odom_compose": (ctypes.c_int, [_dp, _dp, _dp]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),
@@ -285,6 +306,12 @@ class SparseOdomParams(ctypes.Structure):
                 ("prior_lambda_r", ctypes.c_double), ("outlier_gate", ctypes.c_double), ("min_stereo_base", ctypes.c_double)]
 
 
+class MonoOdomParams(ctypes.Structure):
+    """struct vg_mono_odom_params"""
+    _fields_ = [(n, ctypes.c_double) for n in ("min_init_dist", "max_dist", "max_angle", "min_scale_length", "max_scale_ratio")] + \
+               [("num_scales", ctypes.c_int), ("motion", MotionStereoParams), ("sparse", SparseOdomParams)]
+
+
 class RenderObject(ctypes.Structure):
     """struct vg_render_object"""
     _fields_ = [("kind", ctypes.c_int), ("texture", ctypes.c_void_p), ("cols", ctypes.c_int), ("rows", ctypes.c_int),
@@ -295,6 +322,9 @@ RENDER_BACKGROUND, RENDER_PLANE, RENDER_MAX_PLANES, RENDER_MIN_SIDE, RENDER_MAX_
 SPARSE_ODOM_REPORT, SPARSE_ODOM_FEED_REPORT = 8, 12
 SPARSE_ODOM_OK, SPARSE_ODOM_TOO_FEW_MATCHES, SPARSE_ODOM_NO_HYPOTHESIS = 0, 1, 2
 SPARSE_ODOM_FIRST, SPARSE_ODOM_SKIPPED, SPARSE_ODOM_ESTIMATED = 0, 1, 2
+MONO_ODOM_BEGIN, MONO_ODOM_SPARSE_INIT, MONO_ODOM_READY = 0, 1, 2
+MONO_ODOM_FIRST, MONO_ODOM_WAITING, MONO_ODOM_SPARSE_INIT_KEYFRAME, MONO_ODOM_REFINED, MONO_ODOM_KEYFRAME, MONO_ODOM_DISCARDED = range(6)
+MONO_ODOM_REPORT = 16
 MI_NUM_BINS, MI_VALUE_MAX, MI_ODOMETRY_DAMPING = 8, 255., 0.0002
 MI_DEFAULTS = {"function_tolerance": 1e-2, "gradient_tolerance": 1e-3, "max_iterations": 50}
 
