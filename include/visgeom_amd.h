@@ -780,6 +780,12 @@ int vg_photometric_level_size(const vg_photometric *h, int scale_idx, int *width
  * is neither 0 nor above 50, whose grey is at most 240 and which reconstruct, in raster order: packed index v * cols + u, grey
  * value, and the point at its depth moved by xi_base_cam.  The depth map is read during the call only. */
 int vg_photometric_set_base(vg_photometric *h, const uint8_t *img, const double *depth);
+/* setDepth on a handle whose key frame image is set: the data pack and the mutual-information histogram of every scale again,
+ * from the resident pyramid and gradients and the new depth map -- the select / scan / select / histogram launches of set_base
+ * without its pyramid and Sobel launches; counts, indices, values, clouds and histograms are bit-identical to
+ * set_base(the same image, depth).  VG_ERR_STATE before a key frame exists.  A call that fails leaves no key frame.  Like the
+ * vg_mi_ entries it works on a vg_photometric handle under a prefix of its own. */
+int vg_photo_set_depth(vg_photometric *h, const double *depth);
 /* setTargetImage of n images (DEVICE u8 [n][height][width], n in [1, 65535]): n pyramids, one launch per level; they replace
  * the earlier targets. */
 int vg_photometric_set_targets(vg_photometric *h, int64_t n, const uint8_t *imgs);
@@ -1084,6 +1090,127 @@ int vg_mono_odom_normalize_scale(const vg_mono_odom_params *params, const double
 int vg_mono_odom_needs_keyframe(const vg_mono_odom_params *params, const double *xi_local, int *needed);
 int vg_mono_odom_camera_motion(const double *xi_base_cam, const double *xi, double *out6);
 int vg_mono_odom_compose(const double *a6, const double *b6, double *out6);
+
+/* =====================================================================================
+ * 16. Photometric mapping: the reference's PhotometricMapping (include/localization/mapping.h, src/localization/mapping.cpp) --
+ *     a persistent map of key frames (image + global pose of the base frame), an inter frame with a depth map that is localized
+ *     against the nearest map frame by mutual information (section 12, vg_mi_compute_pose with its odometry term), and the
+ *     current frame localized photometrically against the inter frame.  Where the map has no frame near enough the loop runs
+ *     as SLAM and the inter frames it leaves behind become the map.  The handle owns one each of the pipelines of sections 10
+ *     to 13, builds one section 9 object per inter frame, and keeps the map's images on the device in a pool that grows by
+ *     whole chunks (a stored image never moves); the map's poses are host data.  Images are DEVICE u8 [height][width] with
+ *     width = u_max and height = v_max of the stereo parameters, maps DEVICE FP64 [y_max][x_max], poses HOST [t, rotvec] of the
+ *     base frame.  Every call is synchronous on the handle's stream and checks its arguments before HIP is touched.
+ *     ODOM_MODE (false in the reference) is not built.  Deviations: DESIGN.md section 9, "Photometric mapping".
+ * ===================================================================================== */
+#define VG_MAPPING_BEGIN 0               /* states: no image since creation / reinit */
+#define VG_MAPPING_INIT 1                /* an inter image, no depth map: waiting for min_init_dist of odometry */
+#define VG_MAPPING_LOCALIZE 2            /* the inter frame is tied to map frame map_index */
+#define VG_MAPPING_SLAM 3                /* no map frame near: the inter frames are pushed into the map */
+#define VG_MAPPING_WARNING_NONE 0
+#define VG_MAPPING_WARNING_SCALE 1       /* the photometric step's length disagreed with the odometry's: the odometry is kept */
+#define VG_MAPPING_WARNING_ROTATION 2    /* its rotation component 2 disagreed: the odometry is kept */
+#define VG_MAPPING_FIRST 0               /* actions of a feed_image call.  BEGIN: the image was kept */
+#define VG_MAPPING_WAITING 1             /* INIT, the odometry has not moved far enough: nothing done */
+#define VG_MAPPING_INIT_SLAM 2           /* INIT: sparse odometry, first inter frame, no map frame near -> SLAM */
+#define VG_MAPPING_INIT_LOCALIZE 3       /* INIT: the same, a map frame near -> LOCALIZE, MI */
+#define VG_MAPPING_LOCALIZE_REFINED 4    /* LOCALIZE, both distances hold: improveStereo */
+#define VG_MAPPING_LOCALIZE_INTER_FRAME 5 /* LOCALIZE, only the inter distance fails: new inter frame, MI against the same map frame */
+#define VG_MAPPING_LOCALIZE_MAP_FRAME_CHANGED 6 /* LOCALIZE, the map distance fails: new inter frame, another map frame, MI */
+#define VG_MAPPING_LOCALIZE_MAP_FRAME_KEPT 7 /* the same, but the selection returns the old index: no MI (as the reference) */
+#define VG_MAPPING_LOCALIZE_LEFT_MAP 8   /* the same, no map frame near -> SLAM */
+#define VG_MAPPING_SLAM_REFINED 9        /* SLAM, the inter distance holds: improveStereo */
+#define VG_MAPPING_SLAM_INTER_FRAME 10   /* SLAM, it fails: the old inter frame into the map, new inter frame, no map frame near */
+#define VG_MAPPING_SLAM_ENTERED_MAP 11   /* the same, a map frame near (with K = 4 normally the one just pushed) -> LOCALIZE, MI */
+#define VG_MAPPING_REPORT 32             /* [0] state before, state after, action, warning, [4] map index before, after, [6] K, length,
+                                            length_prior, |rot2(zeta) - rot2(zetaPrior)| (zeros when no photometric solve ran or
+                                            normalize_scale is off); [10] of the photometric solve the iterations over all scales and
+                                            the finest scale's final cost and vg_termination; [13] of the MI solve the iterations over all
+                                            scales and the finest non-empty scale's initial cost, final cost and vg_termination (zeros when
+                                            no MI ran); [17] 1 when SGM ran, [18] 1 when motion stereo refined the map; [19] the six
+                                            counters of vg_motion_stereo_compute; [25] the five of vg_depth_merge; [30] frames in the map;
+                                            [31] 0 */
+typedef struct vg_mapping vg_mapping;
+typedef struct vg_mapping_params {
+    double new_kf_distance_thresh; /* STORED SQUARED (distThreshSq 0.03): t0^2 / 5 + t1^2 + t2^2 below it (times K) is near */
+    double new_kf_angular_thresh;  /* STORED SQUARED (angularThreshSq 0.25): |rot|^2 below it is near; not scaled by K */
+    double min_init_dist;          /* 0.1: odometry translation that ends INIT */
+    double min_stereo_base;        /* 0.07: below this camera translation neither SGM nor motion stereo runs */
+    double dist_thresh;            /* 5: parsed and unused, as in the reference (maxDistance) */
+    int normalize_scale;           /* 1 */
+    double rotation_tolerance;     /* 0.005: on component 2 of the rotation vector of the step (localizePhoto's literal) */
+    double min_scale_length;       /* 1e-2: the scale of a shorter photometric step is not touched */
+    double min_scale_ratio;        /* 0.8 */
+    double max_scale_ratio;        /* 1.2: K = |t(odometry step)| / |t(photometric step)| outside the two keeps the odometry */
+    int num_scales;                /* 5: pyramid levels of both solves */
+    vg_motion_stereo_params motion;   /* "stereo_parameters": SGM reads motion.stereo, motion stereo all of it */
+    vg_sparse_odom_params sparse;
+} vg_mapping_params;
+void vg_mapping_params_default(vg_mapping_params *p);
+/* PhotometricMapping(ptree): arguments as vg_mono_odom_create.  The thresholds must be finite and not negative, the scale ratios
+ * positive with min <= max.  Allocates the inter image and three map triples; the frame store allocates a chunk when the one
+ * before it is full. */
+int vg_mapping_create(vg_mapping **out, int device, void *hip_stream, const double *eucm, const double *xi_base_cam, int width, int height,
+                      const vg_mapping_params *params);
+void vg_mapping_destroy(vg_mapping *h);
+int vg_mapping_size(const vg_mapping *h, int *width, int *height, int *x_max, int *y_max);
+/* feedOdometry (:62-74): xi_local = xi_local o xi_odom^-1 o xi_odom_new; the first call (and the first after reinit) only records. */
+int vg_mapping_feed_odometry(vg_mapping *h, const double *xi_odom_new);
+/* reInit (:262-273): in SLAM the inter frame is pushed into the map first; the state becomes BEGIN, xi_local = xi_local_old = xi
+ * (HOST [6], the global pose of the base frame the next pass starts at), the odometry is forgotten. */
+int vg_mapping_reinit(vg_mapping *h, const double *xi);
+/* feedImage (:78-179) with pushInterFrame, improveStereo, localizePhoto and localizeMI: img DEVICE u8 [height][width]; samples as
+ * for vg_sparse_odom_feed, passed on in BEGIN and INIT; report HOST [VG_MAPPING_REPORT] or NULL.  A frame works on copies of the
+ * poses, writes its maps into scratch and commits state, poses, map, inter image and frame store last: a call in which a stage
+ * fails leaves them as they were (only the copies of the commit itself and motion stereo's set_base can still fail, and are not
+ * undone).  In INIT a camera translation of the sparse increment not above min_stereo_base -- where the reference executes a
+ * bare throw -- fails with VG_ERR_STATE and commits nothing: the caller re-initialises with vg_mapping_reinit.  The photometric
+ * solve starts at xi_local with xi_local as the prior's pose; the key frame's packs are rebuilt from the map by
+ * vg_photo_set_depth.  One vg_photometric handle serves the photometric and the MI solve. */
+int vg_mapping_feed_image(vg_mapping *h, const uint8_t *img, const int32_t *samples, double *report);
+/* The frame store.  get_frame: pose to xi6 (HOST [6], may be NULL), image to img (DEVICE u8, may be NULL).  add_frame: an
+ * unconditional insert (reloading a saved map).  construct_map is constructMap (:45-60): inserts when select_frame(xi, K = 1)
+ * finds nothing; *inserted 1 or 0.  select_frame is selectMapFrame on the store (*idx -1: none). */
+int vg_mapping_num_frames(const vg_mapping *h, int64_t *count);
+int vg_mapping_get_frame(vg_mapping *h, int64_t k, double *xi6, uint8_t *img);
+int vg_mapping_add_frame(vg_mapping *h, const double *xi, const uint8_t *img);
+int vg_mapping_construct_map(vg_mapping *h, const double *xi, const uint8_t *img, int *inserted);
+int vg_mapping_select_frame(const vg_mapping *h, const double *xi, double K, int *idx);
+/* The alignment signal both reference programs look at, in one launch: wrapImage of img (DEVICE u8) at the pose xi (HOST [6],
+ * NULL: xi_local) through depth (DEVICE FP64 [y_max][x_max], NULL: the handle's map), exactly the values
+ * vg_mono_odom_warp_image writes; computeErr against base (DEVICE u8, NULL: the inter image): err (DEVICE u8 [height][width], may
+ * be NULL, must not overlap img) is 0 where either pixel is 0, else 127 + base - warped SATURATED to [0, 255] (the reference's
+ * conversion wraps); sums HOST int64 [3]: compared pixels, sum |base - warped|, sum (base - warped)^2.  Integer sums: bit-identical
+ * from run to run.  VG_ERR_STATE when a default is asked for that does not exist yet. */
+int vg_mapping_alignment(vg_mapping *h, const uint8_t *base, const uint8_t *img, const double *xi, const double *depth, uint8_t *err,
+                         int64_t *sums);
+int vg_mapping_state(const vg_mapping *h, int *state);
+int vg_mapping_map_index(const vg_mapping *h, int *idx);      /* -1 until a selection has run */
+int vg_mapping_warning(const vg_mapping *h, int *warning);    /* of the last photometric solve */
+int vg_mapping_xi_local(const vg_mapping *h, double *xi6);
+int vg_mapping_xi_inter(const vg_mapping *h, double *xi6);    /* the inter frame's global pose */
+int vg_mapping_xi_composed(const vg_mapping *h, double *xi6); /* xi_inter o xi_local, what both programs log */
+/* The inter frame's depth map, as vg_mono_odom_get_map / vg_mono_odom_map; VG_ERR_STATE while there is none. */
+int vg_mapping_get_map(vg_mapping *h, double *depth, double *sigma, double *cost);
+int vg_mapping_map(const vg_mapping *h, const double **depth, const double **sigma, const double **cost);
+/* Host only -- the state machine's arithmetic, the code the feed calls run:
+ *   check_distance     *ok = |rot|^2 < new_kf_angular_thresh and t0^2 / 5 + t1^2 + t2^2 < new_kf_distance_thresh K
+ *   select_frame_host  over poses HOST [n][6]: delta = xi^-1 o pose; among those that pass check_distance(delta, K) the smallest
+ *                      |rot|^2 + |t|^2 (isotropic), the first on a tie; *idx -1 when none.  selectMapFrame's default K is 4.
+ *   normalize_scale    zetaPrior = old^-1 o prior, zeta = old^-1 o vo.  |rot2(zeta) - rot2(zetaPrior)| > rotation_tolerance: out =
+ *                      old o zetaPrior, ROTATION.  Else with |t(zeta)| > min_scale_length: K = |t(zetaPrior)| / |t(zeta)| outside
+ *                      [min_scale_ratio, max_scale_ratio]: out = old o zetaPrior, SCALE; inside: out = old o zeta with t(zeta)
+ *                      times K.  A shorter step: out = vo.  The caller sets xi_local_old = out in every one of these branches.
+ *                      normalize_scale 0: out = vo, the numbers are zero, xi_local_old is left alone.  K, length, length_prior,
+ *                      rot_diff may each be NULL.
+ *   relocalized_pose   localizeMI's last line: the inter frame's global pose xi_map o xi_fr_map^-1 from the map frame's pose and
+ *                      the map frame's pose in the inter frame (composeInverse). */
+int vg_mapping_check_distance(const vg_mapping_params *params, const double *xi, double K, int *ok);
+int vg_mapping_select_frame_host(const vg_mapping_params *params, int64_t n, const double *poses, const double *xi, double K, int *idx);
+int vg_mapping_normalize_scale(const vg_mapping_params *params, const double *xi_local_old, const double *xi_local_prior,
+                               const double *xi_local_vo, double *out6, double *K, double *length, double *length_prior, double *rot_diff,
+                               int *warning);
+int vg_mapping_relocalized_pose(const double *xi_map, const double *xi_fr_map, double *out6);
 
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",

@@ -222,6 +222,7 @@ SIGNATURES = {
     "vg_photometric_destroy": (None, [_vp]),
     "vg_photometric_level_size": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _ip]),
     "vg_photometric_set_base": (ctypes.c_int, [_vp, _vp, _vp]),
+    "vg_photo_set_depth": (ctypes.c_int, [_vp, _vp]),
     "vg_photometric_set_targets": (ctypes.c_int, [_vp, ctypes.c_int64, _vp]),
     "vg_photometric_level": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
     "vg_photometric_pack": (ctypes.c_int, [_vp, ctypes.c_int, _i64p, _vp, _vp, _vp]),
@@ -270,6 +271,31 @@ SIGNATURES = {
     "vg_mono_odom_needs_keyframe": (ctypes.c_int, [_vp, _dp, _ip]),
     "vg_mono_odom_camera_motion": (ctypes.c_int, [_dp, _dp, _dp]),
     "vg_mono_odom_compose": (ctypes.c_int, [_dp, _dp, _dp]),
+    "vg_mapping_params_default": (None, [_vp]),
+    "vg_mapping_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, _dp, _dp, ctypes.c_int, ctypes.c_int, _vp]),
+    "vg_mapping_destroy": (None, [_vp]),
+    "vg_mapping_size": (ctypes.c_int, [_vp, _ip, _ip, _ip, _ip]),
+    "vg_mapping_feed_odometry": (ctypes.c_int, [_vp, _dp]),
+    "vg_mapping_reinit": (ctypes.c_int, [_vp, _dp]),
+    "vg_mapping_feed_image": (ctypes.c_int, [_vp, _vp, _i32p, _dp]),
+    "vg_mapping_num_frames": (ctypes.c_int, [_vp, _i64p]),
+    "vg_mapping_get_frame": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _vp]),
+    "vg_mapping_add_frame": (ctypes.c_int, [_vp, _dp, _vp]),
+    "vg_mapping_construct_map": (ctypes.c_int, [_vp, _dp, _vp, _ip]),
+    "vg_mapping_select_frame": (ctypes.c_int, [_vp, _dp, ctypes.c_double, _ip]),
+    "vg_mapping_alignment": (ctypes.c_int, [_vp, _vp, _vp, _dp, _vp, _vp, _i64p]),
+    "vg_mapping_state": (ctypes.c_int, [_vp, _ip]),
+    "vg_mapping_map_index": (ctypes.c_int, [_vp, _ip]),
+    "vg_mapping_warning": (ctypes.c_int, [_vp, _ip]),
+    "vg_mapping_xi_local": (ctypes.c_int, [_vp, _dp]),
+    "vg_mapping_xi_inter": (ctypes.c_int, [_vp, _dp]),
+    "vg_mapping_xi_composed": (ctypes.c_int, [_vp, _dp]),
+    "vg_mapping_get_map": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "vg_mapping_map": (ctypes.c_int, [_vp, _vpp, _vpp, _vpp]),
+    "vg_mapping_check_distance": (ctypes.c_int, [_vp, _dp, ctypes.c_double, _ip]),
+    "vg_mapping_select_frame_host": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _dp, ctypes.c_double, _ip]),
+    "vg_mapping_normalize_scale": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "vg_mapping_relocalized_pose": (ctypes.c_int, [_dp, _dp, _dp]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),
@@ -312,6 +338,14 @@ class MonoOdomParams(ctypes.Structure):
                [("num_scales", ctypes.c_int), ("motion", MotionStereoParams), ("sparse", SparseOdomParams)]
 
 
+class MappingParams(ctypes.Structure):
+    """struct vg_mapping_params; the two new_kf thresholds hold squares"""
+    _fields_ = [(n, ctypes.c_double) for n in ("new_kf_distance_thresh", "new_kf_angular_thresh", "min_init_dist", "min_stereo_base",
+                                               "dist_thresh")] + [("normalize_scale", ctypes.c_int)] + \
+               [(n, ctypes.c_double) for n in ("rotation_tolerance", "min_scale_length", "min_scale_ratio", "max_scale_ratio")] + \
+               [("num_scales", ctypes.c_int), ("motion", MotionStereoParams), ("sparse", SparseOdomParams)]
+
+
 class RenderObject(ctypes.Structure):
     """struct vg_render_object"""
     _fields_ = [("kind", ctypes.c_int), ("texture", ctypes.c_void_p), ("cols", ctypes.c_int), ("rows", ctypes.c_int),
@@ -325,6 +359,9 @@ SPARSE_ODOM_FIRST, SPARSE_ODOM_SKIPPED, SPARSE_ODOM_ESTIMATED = 0, 1, 2
 MONO_ODOM_BEGIN, MONO_ODOM_SPARSE_INIT, MONO_ODOM_READY = 0, 1, 2
 MONO_ODOM_FIRST, MONO_ODOM_WAITING, MONO_ODOM_SPARSE_INIT_KEYFRAME, MONO_ODOM_REFINED, MONO_ODOM_KEYFRAME, MONO_ODOM_DISCARDED = range(6)
 MONO_ODOM_REPORT = 16
+MAPPING_BEGIN, MAPPING_INIT, MAPPING_LOCALIZE, MAPPING_SLAM = range(4)
+MAPPING_WARNING_NONE, MAPPING_WARNING_SCALE, MAPPING_WARNING_ROTATION = range(3)
+MAPPING_REPORT = 32
 MI_NUM_BINS, MI_VALUE_MAX, MI_ODOMETRY_DAMPING = 8, 255., 0.0002
 MI_DEFAULTS = {"function_tolerance": 1e-2, "gradient_tolerance": 1e-3, "max_iterations": 50}
 

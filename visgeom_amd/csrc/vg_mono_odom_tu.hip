@@ -331,12 +331,9 @@ int vg_mono_odom_warp_image(vg_mono_odom *s, const uint8_t *src, const double *x
     if (!depth && !s->have_map) return fail(VG_ERR_STATE, "no depth map yet: pass one, or call set_depth or feed images first");
     const uintptr_t a = reinterpret_cast<uintptr_t>(src), b = reinterpret_cast<uintptr_t>(dst);
     if (a < b + (size_t)s->img && b < a + (size_t)s->img) return fail(VG_ERR_INVALID_ARGUMENT, "the warp is a gather: dst must not overlap src");
-    const Array6d motion = vgmo::camera_motion(s->xi_base_cam, xi ? load6(xi) : s->xi_local);
     vgmo::WarpImageArgs args;
     args.v = s->view;
-    const vg::RotTrig rt = vg::rot_trig(motion.data() + 3, true, false);
-    vg::rotation_matrix(motion.data() + 3, -1., rt, args.Rinv);   // rotMatInv
-    for (int i = 0; i < 3; i++) args.t[i] = motion[i];
+    vgmo::warp_image_pose(s->xi_base_cam, xi ? load6(xi) : s->xi_local, args);
     args.depth = depth ? depth : s->triple(0);
     args.src = src;
     args.dst = dst;

@@ -294,6 +294,50 @@ static int build_pyramids(vg_photometric *s, int64_t n, const uint8_t *img, floa
     return VG_OK;
 }
 
+// the data pack and _hist1 of every scale from the resident pyramid and the depth map, the counts to h_total; with `sobel` the
+// gradients of the pyramid first (a new image).  Enqueues only.
+static int launch_packs(vg_photometric *s, const double *depth, bool sobel)
+{
+    const int64_t total = s->off[s->levels];
+    float *base = s->d_base.get();
+    vgp::SelectArgs a;
+    for (int i = 0; i < 6; i++) a.cam[i] = s->cam[i];
+    a.g = s->g;
+    a.depth = depth;
+    const vg::RotTrig rt = vg::rot_trig(s->xbc + 3, true, false);
+    vg::rotation_matrix(s->xbc + 3, 1., rt, a.Rb);
+    for (int i = 0; i < 3; i++) a.tb[i] = s->xbc[i];
+    a.block_counts = s->d_counts;
+    a.block_offsets = s->d_offsets;
+    for (int i = 0; i < s->levels; i++) {
+        const unsigned nb = blocks_of(level_pixels(s, i), vgp::kLanes);
+        if (sobel)
+            hipLaunchKernelGGL(vgp::photo_sobel_kernel, dim3(nb, 1), dim3(vgp::kLanes), 0, s->stream, (const float *)(base + s->off[i]),
+                               base + total + s->off[i], base + 2 * total + s->off[i], (int64_t)0, s->w[i], s->h[i]);
+        a.img = base + s->off[i];
+        a.gu = base + total + s->off[i];
+        a.gv = base + 2 * total + s->off[i];
+        a.w = s->w[i];
+        a.h = s->h[i];
+        a.level_scale = 1 << i;
+        a.idx = s->d_idx.get() + s->off[i];
+        a.val = s->d_val.get() + s->off[i];
+        a.cloud = s->d_cloud.get() + 3 * s->off[i];
+        hipLaunchKernelGGL((vgp::photo_select_kernel<false>), dim3(nb), dim3(vgp::kLanes), 0, s->stream, a);
+        hipLaunchKernelGGL(vgp::photo_scan_kernel, dim3(1), dim3(vgp::kLanes), 0, s->stream, (const unsigned *)s->d_counts.get(), s->d_offsets.get(),
+                           (int)nb, s->d_total.get() + i);
+        hipLaunchKernelGGL((vgp::photo_select_kernel<true>), dim3(nb), dim3(vgp::kLanes), 0, s->stream, a);
+        // MutualInformation's _hist1 depends on the pack only
+        hipLaunchKernelGGL(vgp::mi_hist1_kernel, dim3(nb), dim3(vgp::kLanes), 0, s->stream, (const double *)a.val, (const unsigned *)(s->d_total.get() + i),
+                           s->d_hist1_partials.get());
+        hipLaunchKernelGGL(vgp::mi_hist1_reduce_kernel, dim3(1), dim3(64), 0, s->stream, (const double *)s->d_hist1_partials.get(), (int)nb,
+                           s->d_hist1.get() + vgp::kMiBins * i);
+    }
+    VG_HIP(hipGetLastError());
+    VG_HIP(hipMemcpyAsync(s->h_total, s->d_total, vgp::kMaxLevels * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+    return VG_OK;
+}
+
 int vg_photometric_set_base(vg_photometric *s, const uint8_t *img, const double *depth)
 {
     if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "photometric handle is NULL");
@@ -316,42 +360,23 @@ int vg_photometric_set_base(vg_photometric *s, const uint8_t *img, const double 
         if (const int rc = s->d_hist1_partials.grow(nb * vgp::kMiBins, what)) return rc;
         if (const int rc = s->h_total.grow(vgp::kMaxLevels, "the pack counts")) return rc;
     }
-    float *base = s->d_base.get();
-    if (const int rc = build_pyramids(s, 1, img, base)) return rc;
-    vgp::SelectArgs a;
-    for (int i = 0; i < 6; i++) a.cam[i] = s->cam[i];
-    a.g = s->g;
-    a.depth = depth;
-    const vg::RotTrig rt = vg::rot_trig(s->xbc + 3, true, false);
-    vg::rotation_matrix(s->xbc + 3, 1., rt, a.Rb);
-    for (int i = 0; i < 3; i++) a.tb[i] = s->xbc[i];
-    a.block_counts = s->d_counts;
-    a.block_offsets = s->d_offsets;
-    for (int i = 0; i < s->levels; i++) {
-        const unsigned nb = blocks_of(level_pixels(s, i), vgp::kLanes);
-        hipLaunchKernelGGL(vgp::photo_sobel_kernel, dim3(nb, 1), dim3(vgp::kLanes), 0, s->stream, (const float *)(base + s->off[i]),
-                           base + total + s->off[i], base + 2 * total + s->off[i], (int64_t)0, s->w[i], s->h[i]);
-        a.img = base + s->off[i];
-        a.gu = base + total + s->off[i];
-        a.gv = base + 2 * total + s->off[i];
-        a.w = s->w[i];
-        a.h = s->h[i];
-        a.level_scale = 1 << i;
-        a.idx = s->d_idx.get() + s->off[i];
-        a.val = s->d_val.get() + s->off[i];
-        a.cloud = s->d_cloud.get() + 3 * s->off[i];
-        hipLaunchKernelGGL((vgp::photo_select_kernel<false>), dim3(nb), dim3(vgp::kLanes), 0, s->stream, a);
-        hipLaunchKernelGGL(vgp::photo_scan_kernel, dim3(1), dim3(vgp::kLanes), 0, s->stream, (const unsigned *)s->d_counts.get(), s->d_offsets.get(),
-                           (int)nb, s->d_total.get() + i);
-        hipLaunchKernelGGL((vgp::photo_select_kernel<true>), dim3(nb), dim3(vgp::kLanes), 0, s->stream, a);
-        // MutualInformation's _hist1 depends on the pack only
-        hipLaunchKernelGGL(vgp::mi_hist1_kernel, dim3(nb), dim3(vgp::kLanes), 0, s->stream, (const double *)a.val, (const unsigned *)(s->d_total.get() + i),
-                           s->d_hist1_partials.get());
-        hipLaunchKernelGGL(vgp::mi_hist1_reduce_kernel, dim3(1), dim3(64), 0, s->stream, (const double *)s->d_hist1_partials.get(), (int)nb,
-                           s->d_hist1.get() + vgp::kMiBins * i);
-    }
-    VG_HIP(hipGetLastError());
-    VG_HIP(hipMemcpyAsync(s->h_total, s->d_total, vgp::kMaxLevels * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+    if (const int rc = build_pyramids(s, 1, img, s->d_base.get())) return rc;
+    if (const int rc = launch_packs(s, depth, true)) return rc;
+    if (const int rc = call.finish()) return rc;
+    for (int i = 0; i < s->levels; i++) s->m[i] = s->h_total.get()[i];
+    s->has_base = true;
+    return VG_OK;
+}
+
+int vg_photo_set_depth(vg_photometric *s, const double *depth)
+{
+    if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "photometric handle is NULL");
+    if (!depth) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!s->has_base) return fail(VG_ERR_STATE, "no key frame image: call vg_photometric_set_base first");
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    s->has_base = false;   // the packs are rewritten: a failure below leaves no key frame
+    if (const int rc = launch_packs(s, depth, false)) return rc;
     if (const int rc = call.finish()) return rc;
     for (int i = 0; i < s->levels; i++) s->m[i] = s->h_total.get()[i];
     s->has_base = true;

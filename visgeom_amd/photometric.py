@@ -64,6 +64,24 @@ class Photometric(Handle):
         capi.check(capi.load().vg_photometric_set_base(self._h, img.data_ptr(), depth.data_ptr()))
         self._leave(img, depth)
 
+    def set_depth(self, depth):
+        """setDepth: the key frame's image stays, its data packs are rebuilt from another depth map (float64 CUDA tensor [y_max,
+        x_max]) -- the same packs as set_base(the same image, depth), without the pyramid and gradient launches.  The library
+        refuses it (ERR_STATE) before a key frame exists."""
+        import torch
+
+        if not _is_cuda(depth, torch.float64) or depth.dim() != 2:
+            raise ValueError("depth must be a float64 CUDA tensor [y_max, x_max]")
+        p = self.params
+        x_max = (p.u_max - 2 * p.u0) // p.scale + 1 if p.equal_margins else p.x_max
+        y_max = (p.v_max - 2 * p.v0) // p.scale + 1 if p.equal_margins else p.y_max
+        if tuple(depth.shape) != (y_max, x_max):
+            raise ValueError("depth must be [y_max, x_max] = [%d, %d]" % (y_max, x_max))
+        depth = depth.contiguous()
+        self._enter()
+        capi.check(capi.load().vg_photo_set_depth(self._h, depth.data_ptr()))
+        self._leave(depth)
+
     def set_targets(self, imgs):
         """the images the poses are estimated for: [n, height, width] or one [height, width]"""
         imgs, _ = _u8_images(imgs, self.height, self.width, "imgs")
