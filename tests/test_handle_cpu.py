@@ -1,5 +1,5 @@
 """visgeom_amd/_handle.py without a GPU and without the library: the life of a handle against a stub destroy function, and the
-argument checks the five wrappers share."""
+argument checks the wrappers share."""
 import ctypes
 
 import numpy as np
@@ -76,15 +76,21 @@ def test_a_destroy_that_raises_does_not_escape_del_and_is_not_repeated(monkeypat
 
 
 def test_every_wrapper_names_its_destroy_function_and_keeps_none_of_its_own():
-    from visgeom_amd import depth_fusion, motion_stereo, photometric, sparse_odom
+    from visgeom_amd import depth_fusion, mapping, mono_odom, motion_stereo, photometric, sparse_odom
 
     names = {stereo.Stereo: "vg_stereo_destroy", motion_stereo.MotionStereo: "vg_motion_stereo_destroy",
              depth_fusion.DepthFusion: "vg_depth_fusion_destroy", photometric.Photometric: "vg_photometric_destroy",
-             sparse_odom.SparseOdometry: "vg_sparse_odom_destroy"}
+             sparse_odom.SparseOdometry: "vg_sparse_odom_destroy", mono_odom.MonoOdometry: "vg_mono_odom_destroy",
+             mapping.PhotometricMapping: "vg_mapping_destroy"}
     for cls, name in names.items():
         assert issubclass(cls, _handle.Handle) and cls._destroy == name
         for method in ("close", "__del__", "_open", "_enter", "_leave"):
             assert method not in vars(cls), (cls.__name__, method)
+    # the two frame loops keep none of what their base holds either
+    for cls in (mono_odom.MonoOdometry, mapping.PhotometricMapping):
+        assert issubclass(cls, _handle.LoopHandle) and cls._destroy == cls._prefix + "destroy"
+        for method in ("__init__", "_image", "_depth", "_feed_image", "_get6", "_geti", "map"):
+            assert method not in vars(cls) and method not in vars(_handle.Handle), (cls.__name__, method)
 
 
 def test_vec():

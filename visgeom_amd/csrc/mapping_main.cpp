@@ -94,11 +94,6 @@ int load_image(std::vector<Image> &images, const std::string &path, const vg_ste
     return (int)images.size() - 1;
 }
 
-void write_pgm(const std::string &path, int w, int h, const unsigned char *px)
-{
-    write_file(path, "P5\n" + std::to_string(w) + " " + std::to_string(h) + "\n255\n", px, (size_t)w * h);
-}
-
 }  // namespace
 
 int main(int argc, char **argv)
@@ -124,13 +119,7 @@ int main(int argc, char **argv)
         if (root.kind != vgjson::Value::Object) throw std::runtime_error("a JSON object expected");
         cam = vec6(root, "camera_params");
         xbc = pose_of(root.at("xi_base_camera"), "xi_base_camera");
-        const vgjson::Value &sp = root.at("stereo_parameters");
-        read_params(sp, p);
-        if (sp.has("motion_stereo_parameters")) {
-            const vgjson::Value &m = sp.at("motion_stereo_parameters");
-            if (m.kind != vgjson::Value::Object) throw std::runtime_error("motion_stereo_parameters: an object expected");
-            if (m.has("gradient_thresh")) mp.motion.gradient_thresh = as_int(m.at("gradient_thresh"), "gradient_thresh");
-        }
+        read_motion_stereo_parameters(root.at("stereo_parameters"), mp.motion);
         if (root.has("mapping_parameters")) {
             const vgjson::Value &m = root.at("mapping_parameters");
             if (m.kind != vgjson::Value::Object) throw std::runtime_error("mapping_parameters: an object expected");

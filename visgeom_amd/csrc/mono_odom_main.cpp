@@ -46,13 +46,7 @@ int main(int argc, char **argv)
         if (root.kind != vgjson::Value::Object) throw std::runtime_error("a JSON object expected");
         cam = vec6(root, "camera_params");
         xbc = pose_of(root.at("xi_base_camera"), "xi_base_camera");
-        const vgjson::Value &sp = root.at("stereo_parameters");
-        read_params(sp, p);
-        if (sp.has("motion_stereo_parameters")) {
-            const vgjson::Value &m = sp.at("motion_stereo_parameters");
-            if (m.kind != vgjson::Value::Object) throw std::runtime_error("motion_stereo_parameters: an object expected");
-            if (m.has("gradient_thresh")) mp.motion.gradient_thresh = as_int(m.at("gradient_thresh"), "gradient_thresh");
-        }
+        read_motion_stereo_parameters(root.at("stereo_parameters"), mp.motion);
         if (root.has("mono_odom_parameters")) {
             const vgjson::Value &m = root.at("mono_odom_parameters");
             if (m.kind != vgjson::Value::Object) throw std::runtime_error("mono_odom_parameters: an object expected");
@@ -168,7 +162,7 @@ int main(int argc, char **argv)
             VGCHECK(vg_mono_odom_warp_image(d.m, d.img, nullptr, nullptr, d.warped));
             HIPCHECK(hipMemcpy(host.data(), d.warped, img, hipMemcpyDeviceToHost));
             try {
-                write_file(dir + "/warp_" + std::to_string(i) + ".pgm", "P5\n" + std::to_string(W) + " " + std::to_string(H) + "\n255\n", host.data(), img);
+                write_pgm(dir + "/warp_" + std::to_string(i) + ".pgm", W, H, host.data());
             } catch (const std::exception &e) {
                 return die(e.what());
             }

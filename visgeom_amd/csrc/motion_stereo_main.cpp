@@ -43,13 +43,7 @@ int main(int argc, char **argv)
         if (root.kind != vgjson::Value::Object) throw std::runtime_error("a JSON object expected");
         c1 = vec6(root, "camera_params_left");
         c2 = vec6(root, "camera_params_right");
-        const vgjson::Value &sp = root.at("stereo_parameters");
-        read_params(sp, p);
-        if (sp.has("motion_stereo_parameters")) {
-            const vgjson::Value &m = sp.at("motion_stereo_parameters");
-            if (m.kind != vgjson::Value::Object) throw std::runtime_error("motion_stereo_parameters: an object expected");
-            if (m.has("gradient_thresh")) mp.gradient_thresh = as_int(m.at("gradient_thresh"), "gradient_thresh");
-        }
+        read_motion_stereo_parameters(root.at("stereo_parameters"), mp);
         if (root.has("sgm_frames")) sgm_frames = as_int(root.at("sgm_frames"), "sgm_frames");
         if (sgm_frames < 0) throw std::runtime_error("sgm_frames must be >= 0");
         const vgjson::Value &im = root.at("images"), &tr = root.at("transformations");

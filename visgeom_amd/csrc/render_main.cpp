@@ -100,8 +100,7 @@ int main(int argc, char **argv)
     for (size_t k = 0; k < n; k++) {
         for (size_t i = 0; i < P; i++) depth64[i] = depth[k * P + i];
         try {
-            write_file(dir + "/img_" + std::to_string(k) + ".pgm", "P5\n" + std::to_string(width) + " " + std::to_string(height) + "\n255\n",
-                       img.data() + k * P, P);
+            write_pgm(dir + "/img_" + std::to_string(k) + ".pgm", width, height, img.data() + k * P);
             write_pfm(dir + "/depth_" + std::to_string(k) + ".pfm", width, height, depth64);
         } catch (const std::exception &e) {
             return die(e.what());

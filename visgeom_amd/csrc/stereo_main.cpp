@@ -75,7 +75,7 @@ int main(int argc, char **argv)
     try {
         write_pfm(dir + "/depth.pfm", X, Y, depth);
         write_pfm(dir + "/sigma.pfm", X, Y, sigma);
-        write_file(dir + "/inverse_depth.pgm", "P5\n" + std::to_string(X) + " " + std::to_string(Y) + "\n255\n", inv.data(), inv.size());
+        write_pgm(dir + "/inverse_depth.pgm", X, Y, inv.data());
     } catch (const std::exception &e) {
         return die(e.what());
     }

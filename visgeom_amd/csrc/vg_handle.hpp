@@ -1,6 +1,7 @@
-// vg_handle.hpp -- what the image-pipeline handles share on the host (vg_stereo, vg_motion_stereo, vg_depth_fusion,
-// vg_photometric, vg_sparse_odom): the device and stream of a handle, grow-only buffers, the envelope of a synchronous
-// call, the range check of an item count and the staging of per-item counters.  Host only; a new pipeline includes this.
+// vg_handle.hpp -- what the eight image-pipeline handles share on the host (vg_stereo, vg_motion_stereo, vg_depth_fusion,
+// vg_photometric, vg_sparse_odom, vg_render, and through vg_frame_loop.hpp vg_mono_odom and vg_mapping): the device and
+// stream of a handle, grow-only buffers, the envelope of a synchronous call, the range check of an item count and the
+// staging of per-item counters.  Host only; a new pipeline includes this.
 #pragma once
 
 #include <string>

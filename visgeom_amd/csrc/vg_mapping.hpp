@@ -2,7 +2,7 @@
 // machine (src/localization/mapping.cpp: checkDistance :322-332, selectMapFrame :275-300, the scale normalisation of localizePhoto
 // :420-459) and the one kernel the loop adds to the pipelines it calls: wrapImage + computeErr (test/localization/map_test.cpp
 // :17-32) + the sums of the error in one launch.  The warped value comes from vg_warp_image.hpp's device function, which
-// vg_mono_odom_warp_image launches too.
+// vg_mono_odom_warp_image launches too; the host side of the handle that both sections share is vg_frame_loop.hpp.
 #pragma once
 
 #include "vg_warp_image.hpp"

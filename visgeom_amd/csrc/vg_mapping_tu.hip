@@ -1,11 +1,12 @@
 // vg_mapping_tu.hip -- translation unit of libvisgeom_amd.so: photometric mapping (section 16 of the C ABI).
 // Built with hipcc for gfx950 only; compiled on its own so that an edit of one subsystem does not rebuild the others.
 //
-// A vg_mapping handle is the reference's PhotometricMapping: it owns one vg_sparse_odom, vg_motion_stereo, vg_depth_fusion and
-// vg_photometric handle (through their C entries, all on the handle's stream), the inter frame's image, three map triples --
-// the map and two scratch triples -- and the frame store, and builds a vg_stereo object per inter frame.  Between the stages
-// of a frame only poses, counts and reports cross to the host.  A frame works on copies of the poses, writes its maps into
-// the scratch triples, keeps a push into the frame store pending, and commits when its last stage has succeeded.
+// A vg_mapping handle is the reference's PhotometricMapping.  The four pipelines it owns, its three map triples, the stage steps
+// of a frame and the small entries are the frame-loop core it shares with vg_mono_odom (vg_frame_loop.hpp).  Here: the inter
+// frame's image and pose, the frame store, the alignment sums and PhotometricMapping's state machine -- a new inter frame's SGM
+// map is noise-filtered, a base below min_stereo_base only warps the map (and fails in INIT), xi_local is reset at push time, the
+// photometric key frame keeps the inter image while only the map changes.  A frame works on copies of the poses, writes its maps
+// into the scratch triples, keeps a push into the frame store pending, and commits when its last stage has succeeded.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -13,30 +14,18 @@
 #include <new>
 #include <vector>
 
-#include "vg_handle.hpp"
+#include "vg_frame_loop.hpp"
 #include "vg_mapping.hpp"
-#include "vg_stereo_host.hpp"
 
 using vgmap::Array6d;
 
-struct vg_mapping : vgi::HandleBase {
+struct vg_mapping : vgmo::FrameLoop {
     vg_mapping_params prm;
-    double cam[6];
-    Array6d xi_base_cam;
-    vgmo::View view;
-    int64_t P = 0, img = 0;
-    vg_sparse_odom *sparse = nullptr;
-    vg_motion_stereo *motion = nullptr;
-    vg_depth_fusion *fusion = nullptr;
-    vg_photometric *photo = nullptr;
     bool photo_has_inter = false;   // the photometric key frame's image is the inter image: set_depth is enough
     int state = vgmap::kBegin, warning = vgmap::kWarnNone, map_idx = -1;
-    bool have_odom = false, have_map = false, have_inter = false;
-    Array6d xi_local{}, xi_local_old{}, xi_odom{}, zeta_odom{}, xi_inter{};
+    bool have_inter = false;
+    Array6d zeta_odom{}, xi_inter{};
     vgi::Grow<uint8_t> d_inter;    // the inter frame's image
-    vgi::Grow<double> d_maps;      // [3 triples][3][P]
-    int map_slot = 0;              // which triple is the map; the other two are scratch
-    double *triple(int k) const { return d_maps.get() + (size_t)((map_slot + k) % 3) * 3 * (size_t)P; }   // 0: the map
     // the frame store: poses on the host, images in device chunks of kChunk images that are never moved
     static constexpr int64_t kChunk = 16;
     std::vector<Array6d> poses;
@@ -44,30 +33,15 @@ struct vg_mapping : vgi::HandleBase {
     uint8_t *frame(int64_t k) const { return chunks[(size_t)(k / kChunk)]->get() + (size_t)(k % kChunk) * (size_t)img; }
     vgi::Grow<unsigned long long> d_sums;
     vgi::GrowPinned<unsigned long long> h_sums;
-    ~vg_mapping()
-    {
-        vg_sparse_odom_destroy(sparse);
-        vg_motion_stereo_destroy(motion);
-        vg_depth_fusion_destroy(fusion);
-        vg_photometric_destroy(photo);
-    }
 };
 
 namespace {
 
 using vgi::fail;
+using vgmo::kMaxPyramid;
+using vgmo::load6;
+using vgmo::store6;
 using vgsh::blocks_of;
-
-constexpr int kMaxPyramid = 8;   // vg_photometric_create refuses more pyramid levels
-
-Array6d load6(const double *p)
-{
-    Array6d a;
-    std::memcpy(a.data(), p, sizeof(double) * 6);
-    return a;
-}
-
-void store6(const Array6d &a, double *p) { std::memcpy(p, a.data(), sizeof(double) * 6); }
 
 int check_thresholds(const vg_mapping_params &p)
 {
@@ -134,28 +108,17 @@ int push_inter_frame(vg_mapping *s, const uint8_t *img, Frame &f)
         f.stored_xi = f.xi_inter;
     }
     const Array6d base = vgmo::camera_motion(s->xi_base_cam, f.xi_local);
-    double *sgm = s->triple(1), *warp = s->triple(2);
-    const double *map = s->triple(0);
-    const size_t P = (size_t)s->P;
     if (vgmo::norm3(base.data()) > s->prm.min_stereo_base) {
-        const Array6d inv = vgth::inverse(base);
-        vg_stereo *st = nullptr;   // EnhancedSgm(base.inverse(), ...): computeStereo(img, interFrame.img)
-        if (const int rc = vg_stereo_create(&st, s->device, s->stream, s->cam, s->cam, inv.data(), &s->prm.motion.stereo)) return rc;
-        const int rc = vg_stereo_compute(st, 1, img, s->d_inter, sgm, sgm + P, sgm + 2 * P, nullptr);
-        vg_stereo_destroy(st);
-        if (rc) return rc;
-        if (const int rc2 = vg_depth_filter_noise(s->fusion, 1, sgm, sgm + P, sgm, sgm + P, nullptr)) return rc2;
+        if (const int rc = vgmo::sgm_map(s, base, img, s->d_inter, true)) return rc;   // computeStereo(img, interFrame.img), filtered
         f.sgm = 1.;
         f.new_slot = 1;
         if (f.state != vgmap::kInit) {   // the prior map projected forward, the new one merged into it
-            if (const int rc2 = vg_depth_warp(s->fusion, 1, base.data(), map, map + P, map + 2 * P, warp, warp + P, warp + 2 * P, nullptr)) return rc2;
-            int64_t mc[5];
-            if (const int rc2 = vg_depth_merge(s->fusion, 1, warp, warp + P, sgm, sgm + P, mc)) return rc2;
-            for (int i = 0; i < 5; i++) f.merge[i] = (double)mc[i];
+            if (const int rc = vgmo::warp_map(s, base)) return rc;
+            if (const int rc = vgmo::merge_maps(s, f.merge)) return rc;
             f.new_slot = 2;
         }
-    } else if (f.state != vgmap::kInit) {
-        if (const int rc = vg_depth_warp(s->fusion, 1, base.data(), map, map + P, map + 2 * P, warp, warp + P, warp + 2 * P, nullptr)) return rc;
+    } else if (f.state != vgmap::kInit) {   // too short a base for stereo: the map is only carried forward
+        if (const int rc = vgmo::warp_map(s, base)) return rc;
         f.new_slot = 2;
     } else {   // the reference's bare throw
         return fail(VG_ERR_STATE, "INIT: the sparse increment moves the camera less than min_stereo_base, no first depth map: call vg_mapping_reinit");
@@ -172,13 +135,7 @@ int improve_stereo(vg_mapping *s, const uint8_t *img, Frame &f)
 {
     const Array6d base = vgmo::camera_motion(s->xi_base_cam, f.xi_local);
     if (vgmo::norm3(base.data()) < s->prm.min_stereo_base || !vgsh::has_baseline(base.data())) return VG_OK;
-    const double *map = s->triple(0);
-    double *m = s->triple(1);
-    const size_t P = (size_t)s->P;
-    int64_t mc[6];
-    if (const int rc = vg_motion_stereo_compute(s->motion, 1, base.data(), img, map, map + P, map + 2 * P, m, m + P, m + 2 * P, mc)) return rc;
-    if (const int rc = vg_depth_filter_noise(s->fusion, 1, m, m + P, m, m + P, nullptr)) return rc;
-    for (int i = 0; i < 6; i++) f.motion[i] = (double)mc[i];
+    if (const int rc = vgmo::refine_map(s, base, img, f.motion)) return rc;
     f.refined = 1.;
     f.new_slot = 1;
     return VG_OK;
@@ -198,14 +155,8 @@ int localize_photo(vg_mapping *s, const uint8_t *img, Frame &f)
         if (const int rc = vg_photometric_set_base(s->photo, s->d_inter, map)) return rc;
         s->photo_has_inter = true;
     }
-    if (const int rc = vg_photometric_set_targets(s->photo, 1, img)) return rc;
-    const int32_t target = 0;
     Array6d vo;
-    double rep[4 * kMaxPyramid];
-    if (const int rc = vg_photometric_compute_pose(s->photo, 1, f.xi_local.data(), &target, f.xi_local.data(), vo.data(), rep)) return rc;
-    for (int i = 0; i < s->prm.num_scales; i++) f.photo[0] += rep[4 * (size_t)i];
-    f.photo[1] = rep[2];
-    f.photo[2] = rep[3];
+    if (const int rc = vgmo::solve_photo(s, img, f.xi_local, vo, f.photo)) return rc;
     const vgmap::Scale sc = vgmap::normalize_scale(s->prm, f.xi_local_old, f.xi_local, vo);
     f.xi_local = sc.xi;
     if (s->prm.normalize_scale) {
@@ -252,10 +203,7 @@ int commit(vg_mapping *s, const uint8_t *img, const Frame &f, bool new_inter)
     if (f.to_store)
         if (const int rc = store_frame(s, f.stored_xi, s->d_inter)) return rc;
     if (new_inter) {
-        vgi::Call call(s);
-        if (const int rc = call.begin()) return rc;
-        VG_HIP(hipMemcpyAsync(s->d_inter, img, (size_t)s->img, hipMemcpyDeviceToDevice, s->stream));
-        if (const int rc = call.finish()) return rc;
+        if (const int rc = vgmo::copy_image(s, s->d_inter, img)) return rc;
         s->have_inter = true;
         s->photo_has_inter = f.mi_ran;   // localizeMI left img as the photometric key frame
         if (f.pushed)
@@ -270,13 +218,6 @@ int commit(vg_mapping *s, const uint8_t *img, const Frame &f, bool new_inter)
     s->state = f.state;
     s->map_idx = f.map_idx;
     s->warning = f.warning;
-    return VG_OK;
-}
-
-int get_pose(const vg_mapping *s, double *xi6, int which)
-{
-    if (!s || !xi6) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    store6(which == 0 ? s->xi_local : which == 1 ? s->xi_inter : vgth::compose(s->xi_inter, s->xi_local), xi6);
     return VG_OK;
 }
 
@@ -315,41 +256,13 @@ int vg_mapping_create(vg_mapping **out, int device, void *hip_stream, const doub
     *out = nullptr;
     if (!eucm || !xi_base_cam || !params) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (const int rc = check_thresholds(*params)) return rc;
-    const vg_stereo_params &sp = params->motion.stereo;
-    if (width != sp.u_max || height != sp.v_max) return fail(VG_ERR_INVALID_ARGUMENT, "the image size must be uMax x vMax of the stereo parameters");
-    if (const int rc = check_pose(xi_base_cam, "xi_base_cam")) return rc;
     std::unique_ptr<vg_mapping> s(new (std::nothrow) vg_mapping());
     if (!s) return fail(VG_ERR_ALLOC, "out of host memory");
     s->prm = *params;
-    // every pipeline checks its own arguments before it asks for the device: a missing device is reported only when all
-    // four have accepted theirs
-    int rcs[4];
-    rcs[0] = vg_motion_stereo_create(&s->motion, device, hip_stream, eucm, eucm, &params->motion);
-    if (rcs[0] == VG_ERR_INVALID_ARGUMENT) return rcs[0];
-    rcs[1] = vg_depth_fusion_create(&s->fusion, device, hip_stream, eucm, &sp);
-    if (rcs[1] == VG_ERR_INVALID_ARGUMENT) return rcs[1];
-    rcs[2] = vg_photometric_create(&s->photo, device, hip_stream, eucm, &sp, xi_base_cam, width, height, params->num_scales);
-    if (rcs[2] == VG_ERR_INVALID_ARGUMENT) return rcs[2];
-    rcs[3] = vg_sparse_odom_create(&s->sparse, device, hip_stream, eucm, xi_base_cam, width, height, &params->sparse);
-    if (rcs[3] == VG_ERR_INVALID_ARGUMENT) return rcs[3];
-    for (int i = 0; i < 4; i++)
-        if (rcs[i]) return rcs[i];
-    int x_max = 0, y_max = 0;
-    if (const int rc = vg_motion_stereo_size(s->motion, &x_max, &y_max)) return rc;
-    s->prm.motion.stereo.x_max = x_max;   // equal_margins resolved once, for the per-inter-frame SGM objects too
-    s->prm.motion.stereo.y_max = y_max;
-    s->prm.motion.stereo.equal_margins = 0;
-    for (int i = 0; i < 6; i++) s->cam[i] = s->view.cam[i] = eucm[i];
-    s->xi_base_cam = load6(xi_base_cam);
-    s->view.g = vgmo::Grid{sp.scale, sp.u0, sp.v0, x_max, y_max};
-    s->view.width = width;
-    s->view.height = height;
-    s->P = (int64_t)x_max * y_max;
-    s->img = (int64_t)width * height;
-    if (const int rc = s->open(device, hip_stream, "photometric mapping")) return rc;
-    VG_HIP(hipSetDevice(device));
+    if (const int rc = vgmo::open_loop(s.get(), device, hip_stream, eucm, xi_base_cam, width, height, params->motion, params->sparse,
+                                       params->num_scales, "photometric mapping"))
+        return rc;
     if (const int rc = s->d_inter.grow((size_t)s->img, "the inter image")) return rc;
-    if (const int rc = s->d_maps.grow(9 * (size_t)s->P, "the depth maps")) return rc;
     if (const int rc = s->d_sums.grow(3, "the alignment sums")) return rc;
     if (const int rc = s->h_sums.grow(3, "the alignment sums' staging")) return rc;
     *out = s.release();
@@ -358,26 +271,9 @@ int vg_mapping_create(vg_mapping **out, int device, void *hip_stream, const doub
 
 void vg_mapping_destroy(vg_mapping *s) { vgi::destroy(s); }
 
-int vg_mapping_size(const vg_mapping *s, int *width, int *height, int *x_max, int *y_max)
-{
-    if (!s || !width || !height || !x_max || !y_max) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    *width = s->view.width;
-    *height = s->view.height;
-    *x_max = s->view.g.x_max;
-    *y_max = s->view.g.y_max;
-    return VG_OK;
-}
+int vg_mapping_size(const vg_mapping *s, int *width, int *height, int *x_max, int *y_max) { return vgmo::size(s, width, height, x_max, y_max); }
 
-int vg_mapping_feed_odometry(vg_mapping *s, const double *xi_odom_new)
-{
-    if (!s || !xi_odom_new) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (const int rc = check_pose(xi_odom_new, "the odometry pose")) return rc;
-    const Array6d xi_new = load6(xi_odom_new);
-    if (s->have_odom) s->xi_local = vgmo::integrate(s->xi_local, s->xi_odom, xi_new);
-    s->xi_odom = xi_new;
-    s->have_odom = true;
-    return VG_OK;
-}
+int vg_mapping_feed_odometry(vg_mapping *s, const double *xi_odom_new) { return vgmo::feed_odometry(s, xi_odom_new); }
 
 int vg_mapping_reinit(vg_mapping *s, const double *xi)
 {
@@ -511,11 +407,7 @@ int vg_mapping_get_frame(vg_mapping *s, int64_t k, double *xi6, uint8_t *img)
     if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "mapping handle is NULL");
     if (k < 0 || k >= (int64_t)s->poses.size()) return fail(VG_ERR_INVALID_ARGUMENT, "the frame index is out of range");
     if (xi6) store6(s->poses[(size_t)k], xi6);
-    if (!img) return VG_OK;
-    vgi::Call call(s);
-    if (const int rc = call.begin()) return rc;
-    VG_HIP(hipMemcpyAsync(img, s->frame(k), (size_t)s->img, hipMemcpyDeviceToDevice, s->stream));
-    return call.finish();
+    return img ? vgmo::copy_image(s, img, s->frame(k)) : VG_OK;
 }
 
 int vg_mapping_add_frame(vg_mapping *s, const double *xi, const uint8_t *img)
@@ -597,31 +489,13 @@ int vg_mapping_warning(const vg_mapping *s, int *warning)
     return VG_OK;
 }
 
-int vg_mapping_xi_local(const vg_mapping *s, double *xi6) { return get_pose(s, xi6, 0); }
-int vg_mapping_xi_inter(const vg_mapping *s, double *xi6) { return get_pose(s, xi6, 1); }
-int vg_mapping_xi_composed(const vg_mapping *s, double *xi6) { return get_pose(s, xi6, 2); }
+int vg_mapping_xi_local(const vg_mapping *s, double *xi6) { return vgmo::get_pose(s, &vg_mapping::xi_inter, xi6, 0); }
+int vg_mapping_xi_inter(const vg_mapping *s, double *xi6) { return vgmo::get_pose(s, &vg_mapping::xi_inter, xi6, 1); }
+int vg_mapping_xi_composed(const vg_mapping *s, double *xi6) { return vgmo::get_pose(s, &vg_mapping::xi_inter, xi6, 2); }
 
-int vg_mapping_get_map(vg_mapping *s, double *depth, double *sigma, double *cost)
-{
-    if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "mapping handle is NULL");
-    if (!s->have_map) return fail(VG_ERR_STATE, "no depth map yet");
-    vgi::Call call(s);
-    if (const int rc = call.begin()) return rc;
-    double *const out[3] = {depth, sigma, cost};
-    for (int i = 0; i < 3; i++)
-        if (out[i]) VG_HIP(hipMemcpyAsync(out[i], s->triple(0) + (size_t)i * (size_t)s->P, (size_t)s->P * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-    return call.finish();
-}
+int vg_mapping_get_map(vg_mapping *s, double *depth, double *sigma, double *cost) { return vgmo::get_map(s, depth, sigma, cost, "mapping handle is NULL"); }
 
-int vg_mapping_map(const vg_mapping *s, const double **depth, const double **sigma, const double **cost)
-{
-    if (!s || !depth || !sigma || !cost) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!s->have_map) return fail(VG_ERR_STATE, "no depth map yet");
-    *depth = s->triple(0);
-    *sigma = s->triple(0) + s->P;
-    *cost = s->triple(0) + 2 * s->P;
-    return VG_OK;
-}
+int vg_mapping_map(const vg_mapping *s, const double **depth, const double **sigma, const double **cost) { return vgmo::map(s, depth, sigma, cost); }
 
 int vg_mapping_check_distance(const vg_mapping_params *params, const double *xi, double K, int *ok)
 {

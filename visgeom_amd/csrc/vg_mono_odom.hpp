@@ -3,7 +3,8 @@
 // getCameraMotion) and the two kernels the loop adds to the pipelines it calls: MonoOdometry::setDepth (:63-79) and
 // ScalePhotometric::wrapImage (src/localization/photometric.cpp:387-415), both one lane per output element and pure gathers.
 // Evaluated in the order written (-ffp-contract=off), so tests/mono_odom_ref.py agrees bit for bit on the kernels.  The pose
-// integration, getCameraMotion and wrapImage's device function live in vg_warp_image.hpp, shared with section 16.
+// integration, getCameraMotion and wrapImage's device function live in vg_warp_image.hpp, the host side of the handle in
+// vg_frame_loop.hpp, both shared with section 16.
 #pragma once
 
 #include "vg_warp_image.hpp"

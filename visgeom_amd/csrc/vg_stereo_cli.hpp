@@ -1,5 +1,6 @@
-// vg_stereo_cli.hpp -- what the `stereo` and `motion_stereo` programs share: binary PGM in, PFM out, the parameters of
-// ex_epipolar_stereo.json's "stereo_parameters" object, path handling and the one-line error exit.  Host only.
+// vg_stereo_cli.hpp -- what the `stereo`, `motion_stereo`, `render`, `mono_odom` and `mapping` programs share: binary PGM in
+// and out, PFM out, the parameters of ex_epipolar_stereo.json's "stereo_parameters" object with its motion stereo part, path
+// handling and the one-line error exit.  Host only.
 #pragma once
 
 #include <cctype>
@@ -73,6 +74,12 @@ inline void write_file(const std::string &path, const std::string &header, const
     bool ok = std::fwrite(header.data(), 1, header.size(), f) == header.size();
     ok = ok && std::fwrite(data, 1, bytes, f) == bytes;
     if (std::fclose(f) != 0 || !ok) throw std::runtime_error("cannot write " + path);
+}
+
+// binary 8-bit PGM
+inline void write_pgm(const std::string &path, int w, int h, const unsigned char *px)
+{
+    write_file(path, "P5\n" + std::to_string(w) + " " + std::to_string(h) + "\n255\n", px, (size_t)w * h);
 }
 
 // float32 PFM, little endian (scale -1), rows bottom to top
@@ -177,6 +184,16 @@ inline void read_params(const vgjson::Value &sp, vg_stereo_params &p)
         }
     }
     if (p.hypotheses != 1) throw std::runtime_error("hypotheses must be 1 (multi-hypothesis SGM is not provided)");
+}
+
+// "stereo_parameters" with its optional "motion_stereo_parameters": {"gradient_thresh"}
+inline void read_motion_stereo_parameters(const vgjson::Value &sp, vg_motion_stereo_params &mp)
+{
+    read_params(sp, mp.stereo);
+    if (!sp.has("motion_stereo_parameters")) return;
+    const vgjson::Value &m = sp.at("motion_stereo_parameters");
+    if (m.kind != vgjson::Value::Object) throw std::runtime_error("motion_stereo_parameters: an object expected");
+    if (m.has("gradient_thresh")) mp.gradient_thresh = as_int(m.at("gradient_thresh"), "gradient_thresh");
 }
 
 inline std::string dir_of(const std::string &path)

@@ -2,6 +2,7 @@
 // of both state machines (feedOdometry's integration, getCameraMotion) and the device function of ScalePhotometric::wrapImage
 // (src/localization/photometric.cpp:387-415), one key frame pixel per call and a pure gather.  No kernel is defined here, so
 // both translation units include it.  Evaluated in the order written (-ffp-contract=off): tests/mono_odom_ref.py agrees bit for bit.
+// The handle the two sections share -- members, create, stage steps, small entries -- is vg_frame_loop.hpp, built on this.
 #pragma once
 
 #include "vg_stereo_device.hpp"

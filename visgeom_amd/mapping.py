@@ -10,10 +10,8 @@ import numpy as np
 
 from . import capi
 from . import motion_stereo as _motion
-from ._handle import Handle, _is_cuda, _u8_images, _vec
+from ._handle import LoopHandle, _dp, _pose, _set_pipelines, _vec, _xi_base_camera
 
-_dp = ctypes.POINTER(ctypes.c_double)
-_i32p = ctypes.POINTER(ctypes.c_int32)
 _i64p = ctypes.POINTER(ctypes.c_int64)
 STATES = ("BEGIN", "INIT", "LOCALIZE", "SLAM")
 WARNINGS = ("NONE", "SCALE", "ROTATION")
@@ -38,15 +36,7 @@ def make_params(motion=None, sparse=None, **kw):
     """vg_mapping_params from the defaults: motion (a vg_motion_stereo_params), sparse (a vg_sparse_odom_params) and keyword
     overrides.  new_kf_distance_thresh and new_kf_angular_thresh are given as the reference's JSON gives them, a distance and an
     angle, and stored squared."""
-    p = default_params()
-    if motion is not None:
-        if not isinstance(motion, capi.MotionStereoParams):
-            raise ValueError("motion must be a vg_motion_stereo_params")
-        p.motion = motion
-    if sparse is not None:
-        if not isinstance(sparse, capi.SparseOdomParams):
-            raise ValueError("sparse must be a vg_sparse_odom_params")
-        p.sparse = sparse
+    p = _set_pipelines(default_params(), motion, sparse)
     for k, v in kw.items():
         if k in _SQUARED:
             setattr(p, k, float(v) ** 2)
@@ -65,18 +55,9 @@ def params_from_json(root):
     """PhotometricMapping(ptree) (mapping.cpp:27-43) of the JSON object `root` (a dict): (eucm [6], xi_base_cam [6], params)
     from "camera_params", "xi_base_camera", "stereo_parameters" and "mapping_parameters" (MappingParameters(ptree): the two
     new_kf thresholds are squared; the fields the reference has as literals may be given there too)"""
-    values = np.ascontiguousarray(root["xi_base_camera"], dtype=np.float64).ravel()
-    xbc = np.zeros(6)
-    capi.check(capi.load().vg_transform_from_values(values.size, values.ctypes.data_as(_dp), xbc.ctypes.data_as(_dp)))
+    xbc = _xi_base_camera(root)
     p = make_params(motion=_motion.params_from_json(root["stereo_parameters"]), **root.get("mapping_parameters", {}))
     return _vec(root["camera_params"], 6, "camera_params"), xbc, p
-
-
-def _pose(xi, what):
-    a = _vec(xi, 6, what)
-    if not np.isfinite(a).all():
-        raise ValueError("%s must be finite" % what)
-    return a
 
 
 def check_distance(params, xi, K=1.):
@@ -125,37 +106,15 @@ def report_dict(rep):
             "motion_counts": rep[19:25].astype(np.int64), "merge_counts": rep[25:30].astype(np.int64), "frames": int(rep[30])}
 
 
-class PhotometricMapping(Handle):
+class PhotometricMapping(LoopHandle):
     """A vg_mapping handle on one device: one EUCM camera, xi_base_cam and the parameters (make_params); the image size is u_max
     x v_max of params.motion.stereo.  Images are uint8 CUDA tensors [height, width], maps float64 CUDA tensors [y_max, x_max],
     poses numpy [6] = [t, rotvec].  The handle's stream is torch's current stream of the device at creation; each call first
     makes it wait for the caller's current stream and is complete when it returns."""
 
     _destroy = "vg_mapping_destroy"
-
-    def __init__(self, eucm, xi_base_cam, params=None, device=0):
-        import torch
-
-        self._c = _vec(eucm, 6, "eucm")
-        self._xbc = _pose(xi_base_cam, "xi_base_cam")
-        self.device = torch.device("cuda", device)
-        self.params = params if params is not None else default_params()
-        if not isinstance(self.params, capi.MappingParams):
-            raise ValueError("params must be a vg_mapping_params (make_params())")
-        sp = self.params.motion.stereo
-        self.width, self.height = sp.u_max, sp.v_max
-        L = capi.load()
-        self._open(L.vg_mapping_create, self._c.ctypes.data_as(_dp), self._xbc.ctypes.data_as(_dp), self.width, self.height,
-                   ctypes.byref(self.params))
-        size = [ctypes.c_int() for _ in range(4)]
-        capi.check(L.vg_mapping_size(self._h, *[ctypes.byref(v) for v in size]))
-        self.x_max, self.y_max = size[2].value, size[3].value
-
-    def _image(self, img, what="img"):
-        img, single = _u8_images(img, self.height, self.width, what)
-        if not single:
-            raise ValueError("%s must be one image [height, width]" % what)
-        return img
+    _prefix = "vg_mapping_"
+    _params = capi.MappingParams
 
     def feed_odometry(self, xi_odom_new):
         """feedOdometry: the wheel odometry's pose of the base frame; the first call (and the first after reinit) only records it"""
@@ -171,19 +130,7 @@ class PhotometricMapping(Handle):
     def feed_image(self, img, samples=None):
         """feedImage: the report of the frame as a dict (REPORT).  samples: the RANSAC sample table for sparse odometry (int32
         [ransac_iterations, num_ransac_points]) or None for the library's."""
-        img = self._image(img)
-        s = None
-        if samples is not None:
-            s = np.ascontiguousarray(samples, dtype=np.int32)
-            sp = self.params.sparse
-            if s.shape != (sp.ransac_iterations, sp.num_ransac_points):
-                raise ValueError("samples must be [%d, %d]" % (sp.ransac_iterations, sp.num_ransac_points))
-        rep = np.zeros(capi.MAPPING_REPORT)
-        self._enter()
-        capi.check(capi.load().vg_mapping_feed_image(self._h, img.data_ptr(), s.ctypes.data_as(_i32p) if s is not None else None,
-                                                     rep.ctypes.data_as(_dp)))
-        self._leave(img)
-        return report_dict(rep)
+        return report_dict(self._feed_image(img, samples, capi.MAPPING_REPORT))
 
     @property
     def num_frames(self):
@@ -237,10 +184,7 @@ class PhotometricMapping(Handle):
         img = self._image(img)
         base = self._image(base, "base") if base is not None else None
         x = _pose(xi, "xi") if xi is not None else None
-        if depth is not None:
-            if not _is_cuda(depth, torch.float64) or tuple(depth.shape) != (self.y_max, self.x_max):
-                raise ValueError("depth must be a float64 CUDA tensor [y_max, x_max] = [%d, %d]" % (self.y_max, self.x_max))
-            depth = depth.contiguous()
+        depth = self._depth(depth)
         out = torch.empty((self.height, self.width), dtype=torch.uint8, device=self.device) if err else None
         sums = np.zeros(3, np.int64)
         self._enter()
@@ -251,47 +195,27 @@ class PhotometricMapping(Handle):
         self._leave(out, img, base, depth)
         return out, sums
 
-    def _get6(self, name):
-        out = np.zeros(6)
-        capi.check(getattr(capi.load(), name)(self._h, out.ctypes.data_as(_dp)))
-        return out
-
-    def _geti(self, name):
-        v = ctypes.c_int()
-        capi.check(getattr(capi.load(), name)(self._h, ctypes.byref(v)))
-        return v.value
-
     @property
     def state(self):
-        return STATES[self._geti("vg_mapping_state")]
+        return STATES[self._geti("state")]
 
     @property
     def map_index(self):
-        return self._geti("vg_mapping_map_index")
+        return self._geti("map_index")
 
     @property
     def warning(self):
-        return WARNINGS[self._geti("vg_mapping_warning")]
+        return WARNINGS[self._geti("warning")]
 
     @property
     def xi_local(self):
-        return self._get6("vg_mapping_xi_local")
+        return self._get6("xi_local")
 
     @property
     def xi_inter(self):
-        return self._get6("vg_mapping_xi_inter")
+        return self._get6("xi_inter")
 
     @property
     def xi_composed(self):
         """xi_inter o xi_local, the pose both reference programs log"""
-        return self._get6("vg_mapping_xi_composed")
-
-    @property
-    def map(self):
-        """a copy of the inter frame's depth map: (depth, sigma, cost) float64 CUDA tensors [y_max, x_max]"""
-        import torch
-
-        out = [torch.empty((self.y_max, self.x_max), dtype=torch.float64, device=self.device) for _ in range(3)]
-        self._enter()
-        capi.check(capi.load().vg_mapping_get_map(self._h, *[t.data_ptr() for t in out]))
-        return self._leave(*out)
+        return self._get6("xi_composed")

@@ -9,10 +9,8 @@ import numpy as np
 
 from . import capi
 from . import motion_stereo as _motion
-from ._handle import Handle, _is_cuda, _u8_images, _vec
+from ._handle import LoopHandle, _dp, _is_cuda, _pose, _set_pipelines, _vec, _xi_base_camera
 
-_dp = ctypes.POINTER(ctypes.c_double)
-_i32p = ctypes.POINTER(ctypes.c_int32)
 STATES = ("BEGIN", "SPARSE_INIT", "READY")
 ACTIONS = ("FIRST", "WAITING", "SPARSE_INIT_KEYFRAME", "REFINED", "KEYFRAME", "DISCARDED")
 REPORT = ("state_before", "state", "action", "K", "length", "length_prior", "iterations", "final_cost", "termination", "counts", "keyframes")
@@ -29,15 +27,7 @@ def default_params():
 def make_params(motion=None, sparse=None, **kw):
     """vg_mono_odom_params from the defaults: motion (a vg_motion_stereo_params, motion_stereo.make_params), sparse (a
     vg_sparse_odom_params, sparse_odom.default_params) and keyword overrides of the thresholds and num_scales"""
-    p = default_params()
-    if motion is not None:
-        if not isinstance(motion, capi.MotionStereoParams):
-            raise ValueError("motion must be a vg_motion_stereo_params")
-        p.motion = motion
-    if sparse is not None:
-        if not isinstance(sparse, capi.SparseOdomParams):
-            raise ValueError("sparse must be a vg_sparse_odom_params")
-        p.sparse = sparse
+    p = _set_pipelines(default_params(), motion, sparse)
     for k, v in kw.items():
         if k in _THRESHOLDS:
             setattr(p, k, float(v))
@@ -52,18 +42,9 @@ def params_from_json(root):
     """MonoOdometry(ptree) (mono_odom.cpp:35-47) of the JSON object `root` (a dict): (eucm [6], xi_base_cam [6], params) from
     "camera_params", "xi_base_camera" and "stereo_parameters" (as motion_stereo.params_from_json reads it); the optional
     "mono_odom_parameters" object of the mono_odom program replaces thresholds and num_scales"""
-    values = np.ascontiguousarray(root["xi_base_camera"], dtype=np.float64).ravel()
-    xbc = np.zeros(6)
-    capi.check(capi.load().vg_transform_from_values(values.size, values.ctypes.data_as(_dp), xbc.ctypes.data_as(_dp)))
+    xbc = _xi_base_camera(root)
     p = make_params(motion=_motion.params_from_json(root["stereo_parameters"]), **root.get("mono_odom_parameters", {}))
     return _vec(root["camera_params"], 6, "camera_params"), xbc, p
-
-
-def _pose(xi, what):
-    a = _vec(xi, 6, what)
-    if not np.isfinite(a).all():
-        raise ValueError("%s must be finite" % what)
-    return a
 
 
 def integrate(xi_local, xi_odom_old, xi_odom_new):
@@ -103,37 +84,15 @@ def compose(a, b):
     return out
 
 
-class MonoOdometry(Handle):
+class MonoOdometry(LoopHandle):
     """A vg_mono_odom handle on one device: one EUCM camera, xi_base_cam and the parameters (make_params); the image size is
     u_max x v_max of params.motion.stereo.  Images are uint8 CUDA tensors [height, width], maps float64 CUDA tensors [y_max,
     x_max], poses numpy [6] = [t, rotvec].  The handle's stream is torch's current stream of the device at creation; each call
     first makes it wait for the caller's current stream and is complete when it returns."""
 
     _destroy = "vg_mono_odom_destroy"
-
-    def __init__(self, eucm, xi_base_cam, params=None, device=0):
-        import torch
-
-        self._c = _vec(eucm, 6, "eucm")
-        self._xbc = _pose(xi_base_cam, "xi_base_cam")
-        self.device = torch.device("cuda", device)
-        self.params = params if params is not None else default_params()
-        if not isinstance(self.params, capi.MonoOdomParams):
-            raise ValueError("params must be a vg_mono_odom_params (make_params())")
-        sp = self.params.motion.stereo
-        self.width, self.height = sp.u_max, sp.v_max
-        L = capi.load()
-        self._open(L.vg_mono_odom_create, self._c.ctypes.data_as(_dp), self._xbc.ctypes.data_as(_dp), self.width, self.height,
-                   ctypes.byref(self.params))
-        size = [ctypes.c_int() for _ in range(4)]
-        capi.check(L.vg_mono_odom_size(self._h, *[ctypes.byref(v) for v in size]))
-        self.x_max, self.y_max = size[2].value, size[3].value
-
-    def _image(self, img, what="img"):
-        img, single = _u8_images(img, self.height, self.width, what)
-        if not single:
-            raise ValueError("%s must be one image [height, width]" % what)
-        return img
+    _prefix = "vg_mono_odom_"
+    _params = capi.MonoOdomParams
 
     def feed_wheel_odometry(self, xi_odom_new):
         """feedWheelOdometry: the wheel odometry's pose of the base frame; the first call only records it"""
@@ -143,18 +102,7 @@ class MonoOdometry(Handle):
     def feed_image(self, img, samples=None):
         """feedImage: the report of the frame as a dict (REPORT; state and action by name, counts int64 [6]).  samples: the
         RANSAC sample table for sparse odometry (int32 [ransac_iterations, num_ransac_points]) or None for the library's."""
-        img = self._image(img)
-        s = None
-        if samples is not None:
-            s = np.ascontiguousarray(samples, dtype=np.int32)
-            sp = self.params.sparse
-            if s.shape != (sp.ransac_iterations, sp.num_ransac_points):
-                raise ValueError("samples must be [%d, %d]" % (sp.ransac_iterations, sp.num_ransac_points))
-        rep = np.zeros(capi.MONO_ODOM_REPORT)
-        self._enter()
-        capi.check(capi.load().vg_mono_odom_feed_image(self._h, img.data_ptr(), s.ctypes.data_as(_i32p) if s is not None else None,
-                                                       rep.ctypes.data_as(_dp)))
-        self._leave(img)
+        rep = self._feed_image(img, samples, capi.MONO_ODOM_REPORT)
         return {"state_before": STATES[int(rep[0])], "state": STATES[int(rep[1])], "action": ACTIONS[int(rep[2])], "K": rep[3],
                 "length": rep[4], "length_prior": rep[5], "iterations": int(rep[6]), "final_cost": rep[7], "termination": int(rep[8]),
                 "counts": rep[9:15].astype(np.int64), "keyframes": int(rep[15])}
@@ -177,10 +125,7 @@ class MonoOdometry(Handle):
 
         src = self._image(src, "src")
         x = _pose(xi, "xi") if xi is not None else None
-        if depth is not None:
-            if not _is_cuda(depth, torch.float64) or tuple(depth.shape) != (self.y_max, self.x_max):
-                raise ValueError("depth must be a float64 CUDA tensor [y_max, x_max] = [%d, %d]" % (self.y_max, self.x_max))
-            depth = depth.contiguous()
+        depth = self._depth(depth)
         dst = torch.empty((self.height, self.width), dtype=torch.uint8, device=self.device)
         self._enter()
         capi.check(capi.load().vg_mono_odom_warp_image(self._h, src.data_ptr(), x.ctypes.data_as(_dp) if x is not None else None,
@@ -188,29 +133,22 @@ class MonoOdometry(Handle):
         self._leave(dst, src, depth)
         return dst
 
-    def _get6(self, name):
-        out = np.zeros(6)
-        capi.check(getattr(capi.load(), name)(self._h, out.ctypes.data_as(_dp)))
-        return out
-
     @property
     def state(self):
-        v = ctypes.c_int()
-        capi.check(capi.load().vg_mono_odom_state(self._h, ctypes.byref(v)))
-        return STATES[v.value]
+        return STATES[self._geti("state")]
 
     @property
     def xi_local(self):
-        return self._get6("vg_mono_odom_xi_local")
+        return self._get6("xi_local")
 
     @property
     def xi_global(self):
-        return self._get6("vg_mono_odom_xi_global")
+        return self._get6("xi_global")
 
     @property
     def xi_composed(self):
         """xi_global o xi_local, the pose the reference prints"""
-        return self._get6("vg_mono_odom_xi_composed")
+        return self._get6("xi_composed")
 
     @property
     def keyframe_increments(self):
@@ -222,13 +160,3 @@ class MonoOdometry(Handle):
         for k in range(n.value):
             capi.check(L.vg_mono_odom_keyframe_increment(self._h, k, out[k].ctypes.data_as(_dp)))
         return out
-
-    @property
-    def map(self):
-        """a copy of the current map: (depth, sigma, cost) float64 CUDA tensors [y_max, x_max]"""
-        import torch
-
-        out = [torch.empty((self.y_max, self.x_max), dtype=torch.float64, device=self.device) for _ in range(3)]
-        self._enter()
-        capi.check(capi.load().vg_mono_odom_get_map(self._h, *[t.data_ptr() for t in out]))
-        return self._leave(*out)
