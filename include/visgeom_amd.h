@@ -1212,6 +1212,84 @@ int vg_mapping_normalize_scale(const vg_mapping_params *params, const double *xi
                                int *warning);
 int vg_mapping_relocalized_pose(const double *xi_map, const double *xi_fr_map, double *out6);
 
+/* =====================================================================================
+ * 17. Calibration trajectory planning: the reference's TrajectoryVisualQuality (include/calibration/trajectory_generation.h,
+ *     src/calibration/trajectory_generation.cpp:86-281) over circular trajectories (CircularTrajectory,
+ *     test/calibration/trajectory.cpp:27-82) -- the robot trajectories to drive in front of a calibration board so that the
+ *     camera-odometry extrinsics become well observable.  A parameter point is HOST [5 T]: per trajectory x0, y0, theta0, the
+ *     chord d and the turn alpha of one step.  The cost of a point is -log det H plus four penalties, H = diag(1 /
+ *     prior_variance) + sum over every trajectory and every pose i >= 1 of J^T C^-1 J (C: the visual covariance of the board
+ *     seen from the pose plus the transported odometry covariance).  The handle owns the device scratch of a batch; every array
+ *     of this section is HOST memory; every call is synchronous on the handle's stream and checks its arguments before HIP is
+ *     touched.  A batch of n points costs three launches whatever n is; a point's result does not depend on the batch it is in.
+ *     A pose with a corner that does not project, or whose JtCJ or C has no finite inverse, is INVALID: the point's cost is
+ *     +inf and invalid[] counts such poses.  EUCM only (VG_MODEL_EUCM; the other models: VG_ERR_INVALID_ARGUMENT).
+ *     TrajectoryQuality, the constant-covariance variant nothing calls, is not built.  Deviations: DESIGN.md section 9,
+ *     "Trajectory planning".
+ * ===================================================================================== */
+#define VG_TRAJECTORY_PARAMS 5           /* parameters of one trajectory */
+#define VG_TRAJECTORY_MAX 8              /* trajectories of a handle */
+#define VG_TRAJECTORY_MIN_STEPS 2        /* poses of one trajectory (number_steps), pose 0 included */
+#define VG_TRAJECTORY_MAX_STEPS 256
+#define VG_TRAJECTORY_MAX_CORNERS 1024   /* board cols x rows */
+#define VG_TRAJECTORY_TERMS 5            /* terms[]: information (-log det H), image limits, curvature, distance, normal */
+#define VG_TRAJECTORY_MAX_POINTS 65535   /* points of one batch; a gradient takes 2 x 5 T + 1 of them per point */
+typedef struct vg_trajectory vg_trajectory;
+typedef struct vg_trajectory_quality {   /* "quality_parameters" of a plan file */
+    double xi_base_cam[6];               /* xiBaseCam: the camera in the robot's frame, [t, rotvec] */
+    double xi_orig_board[6];             /* xiOrigBoard: the board in the world */
+    double turn_radius;                  /* the curvature penalty starts at 1 / turn_radius */
+    int board_cols, board_rows;          /* >= 2 each */
+    double board_step;
+    double min_camera_dist, min_margin, min_cell_size;
+    double prior_variance[6];
+    double feature_variance;
+} vg_trajectory_quality;
+typedef struct vg_trajectory_options {   /* of the minimiser; vg_trajectory_default_options: Ceres' defaults */
+    double function_tolerance;           /* 1e-6: |df| <= tol |f|; 0 switches the test off */
+    double gradient_tolerance;           /* 1e-10: max |g| <= tol */
+    double parameter_tolerance;          /* 1e-8: |dx| <= tol (|x| + tol); 0 switches the test off */
+    int max_iterations;                  /* 1000 */
+} vg_trajectory_options;
+void vg_trajectory_default_options(vg_trajectory_options *o);
+/* model, intrinsics: the camera; width, height: its image; steps HOST [n_trajectories], each in [2, 256]. */
+int vg_trajectory_create(vg_trajectory **out, int device, void *hip_stream, int model, const double *intrinsics, int width, int height,
+                         const vg_trajectory_quality *quality, int n_trajectories, const int *steps);
+void vg_trajectory_destroy(vg_trajectory *h);
+/* *n_params = 5 T, *n_poses = sum of the steps; each may be NULL */
+int vg_trajectory_size(const vg_trajectory *h, int *n_trajectories, int *n_params, int *n_poses);
+/* EvaluateCost at n points: params [n][5 T], cost [n], terms [n][VG_TRAJECTORY_TERMS] (may be NULL), invalid [n] (may be NULL).
+ * cost = terms[0] + the penalties added pose by pose; an invalid point has cost = terms[0] = +inf and its penalty terms summed
+ * over the valid poses. */
+int vg_trajectory_evaluate(vg_trajectory *h, int64_t n, const double *params, double *cost, double *terms, int32_t *invalid);
+/* visualCov at n camera poses [n][6] (the camera in the world): cov [n][36] = JtCJ^-T JtJ JtCJ^-1 and info [n][36] = JtJ,
+ * row-major; invalid [n] is 1 where a corner does not project or JtCJ has no finite inverse, and both matrices are +inf there. */
+int vg_trajectory_visual_cov(vg_trajectory *h, int64_t n, const double *cam_poses, double *cov, double *info, int32_t *invalid);
+/* Evaluate: cost [n] and the central differences grad [n][5 T] with delta_i = max(|p_i| 1e-8, 1e-16), the perturbed values
+ * formed as p_i + delta_i and p_i - delta_i; one batch of n (2 x 5 T + 1) points (at most VG_TRAJECTORY_MAX_POINTS).  invalid [n]
+ * (may be NULL) is 1 where any of a point's evaluations is invalid; its gradient is NaN then. */
+int vg_trajectory_gradient(vg_trajectory *h, int64_t n, const double *params, double *cost, double *grad, int32_t *invalid);
+/* Host only: the points of one gradient, points [2 n_params + 1][n_params] -- row 0 the point itself, row 1 + 2 i with
+ * p_i + delta_i, row 2 + 2 i with p_i - delta_i -- and delta [n_params]. */
+int vg_trajectory_gradient_points(int n_params, const double *params, double *points, double *delta);
+/* Host only: CircularTrajectory::compute for every trajectory of params [5 T]: xi [sum steps][6] and cov [sum steps][36],
+ * trajectory after trajectory.  cov may be NULL. */
+int vg_trajectory_poses(int n_trajectories, const int *steps, const double *params, double *xi, double *cov);
+/* One minimisation per start, all in lock-step: params [n_starts][5 T] holds the starts and receives the results; every round
+ * is one batch with each unfinished start's trial point and its 2 x 5 T perturbed points.  BFGS with a strong-Wolfe line search
+ * (vg_bfgs.hpp) in place of Ceres' GradientProblemSolver; a trial that is invalid, or whose gradient is, is a failed trial and
+ * the search shrinks towards the last valid point.  cost [n_starts]: the cost at the returned parameters; iterations and
+ * termination (vg_termination) [n_starts] may be NULL.  A start that is itself invalid ends with VG_TERM_FAILURE and keeps its
+ * parameters.  options NULL: the defaults. */
+int vg_trajectory_optimize(vg_trajectory *h, int64_t n_starts, double *params, const vg_trajectory_options *options, double *cost,
+                           int32_t *iterations, int32_t *termination);
+/* Host only: the board's corners seen from the camera pose cam_pose [6] -- uv [cols rows][2], row after row of the board, and ok
+ * [cols rows], projectPoint's return value (uv of a corner that does not project is what the formula gives). */
+int vg_trajectory_project_board(int model, const double *intrinsics, const vg_trajectory_quality *quality, const double *cam_pose, double *uv,
+                                int32_t *ok);
+/* kernel launches of the handle since its creation (a measurement: the launches of a call do not depend on its n) */
+int vg_trajectory_launch_count(const vg_trajectory *h, int64_t *count);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",
  * "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop", "solver_no_fold_frames",

@@ -296,6 +296,18 @@ SIGNATURES = {
     "vg_mapping_select_frame_host": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _dp, ctypes.c_double, _ip]),
     "vg_mapping_normalize_scale": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "vg_mapping_relocalized_pose": (ctypes.c_int, [_dp, _dp, _dp]),
+    "vg_trajectory_default_options": (None, [_vp]),
+    "vg_trajectory_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _ip]),
+    "vg_trajectory_destroy": (None, [_vp]),
+    "vg_trajectory_size": (ctypes.c_int, [_vp, _ip, _ip, _ip]),
+    "vg_trajectory_evaluate": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _dp, _dp, _i32p]),
+    "vg_trajectory_visual_cov": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _dp, _dp, _i32p]),
+    "vg_trajectory_gradient": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _dp, _dp, _i32p]),
+    "vg_trajectory_gradient_points": (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp]),
+    "vg_trajectory_poses": (ctypes.c_int, [ctypes.c_int, _ip, _dp, _dp, _dp]),
+    "vg_trajectory_optimize": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _vp, _dp, _i32p, _i32p]),
+    "vg_trajectory_project_board": (ctypes.c_int, [ctypes.c_int, _dp, _vp, _dp, _dp, _i32p]),
+    "vg_trajectory_launch_count": (ctypes.c_int, [_vp, _i64p]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),
@@ -352,6 +364,22 @@ class RenderObject(ctypes.Structure):
                 ("pose", ctypes.c_double * 6), ("width", ctypes.c_double), ("height", ctypes.c_double)]
 
 
+class TrajectoryQuality(ctypes.Structure):
+    """struct vg_trajectory_quality"""
+    _fields_ = [("xi_base_cam", ctypes.c_double * 6), ("xi_orig_board", ctypes.c_double * 6), ("turn_radius", ctypes.c_double),
+                ("board_cols", ctypes.c_int), ("board_rows", ctypes.c_int), ("board_step", ctypes.c_double),
+                ("min_camera_dist", ctypes.c_double), ("min_margin", ctypes.c_double), ("min_cell_size", ctypes.c_double),
+                ("prior_variance", ctypes.c_double * 6), ("feature_variance", ctypes.c_double)]
+
+
+class TrajectoryOptions(ctypes.Structure):
+    """struct vg_trajectory_options"""
+    _fields_ = [("function_tolerance", ctypes.c_double), ("gradient_tolerance", ctypes.c_double), ("parameter_tolerance", ctypes.c_double),
+                ("max_iterations", ctypes.c_int)]
+
+
+TRAJECTORY_PARAMS, TRAJECTORY_MAX, TRAJECTORY_MIN_STEPS, TRAJECTORY_MAX_STEPS, TRAJECTORY_MAX_CORNERS = 5, 8, 2, 256, 1024
+TRAJECTORY_TERMS, TRAJECTORY_MAX_POINTS = 5, 65535
 RENDER_BACKGROUND, RENDER_PLANE, RENDER_MAX_PLANES, RENDER_MIN_SIDE, RENDER_MAX_SIDE, RENDER_COUNTS = 0, 1, 64, 2, 16384, 5
 SPARSE_ODOM_REPORT, SPARSE_ODOM_FEED_REPORT = 8, 12
 SPARSE_ODOM_OK, SPARSE_ODOM_TOO_FEW_MATCHES, SPARSE_ODOM_NO_HYPOTHESIS = 0, 1, 2
