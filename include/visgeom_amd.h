@@ -1290,6 +1290,71 @@ int vg_trajectory_project_board(int model, const double *intrinsics, const vg_tr
 /* kernel launches of the handle since its creation (a measurement: the launches of a call do not depend on its n) */
 int vg_trajectory_launch_count(const vg_trajectory *h, int64_t *count);
 
+/* =====================================================================================
+ * 18. Photometric bundle adjustment: the reference's dense_ba_test (test/reconstruction/dense_ba_test.cpp:38-113, 170-317) --
+ *     the poses of F further frames and the depth of every selected key-frame cell refined together on the grey difference.
+ *     Per frame f and point i the residual r = (I_f(project(X)) - I_0i) / sigma_grey with X = (xi_f o xi_base_cam)^-1
+ *     xi_base_cam (d_i dir_i), sampled by Ceres' bicubic interpolator over the clamping grid on the full-size float image, no
+ *     margin and no loss; per point the prior row p_i = lambda (d_i - d0_i) / sigma0_i; the cost is 1/2 sum r^2 + 1/2 sum p^2.
+ *     The depth block of the normal equations is diagonal and is eliminated exactly (a Schur complement on the GPU), the
+ *     K = 6 F pose system is solved on the host, under the trust-region rule of vg_photometric_compute_pose applied to all
+ *     K + m parameters.  Single scale, EUCM, FP64.  Images are DEVICE u8, maps DEVICE FP64 [y_max][x_max], poses HOST
+ *     [t, rotvec] of a frame's base in the key frame's base.  Every call is synchronous on the handle's stream and checks
+ *     its arguments before HIP is touched; a call out of order gives VG_ERR_STATE.  Deviations: DESIGN.md section 9,
+ *     "Photometric bundle adjustment".
+ * ===================================================================================== */
+#define VG_DENSE_BA_MAX_FRAMES 8
+#define VG_DENSE_BA_TAIL 5               /* sum D dx^2, g . dx, |dx|^2, |x|^2, max |g| of the depth block */
+#define VG_DENSE_BA_NONE (-1.0)          /* prior_weight / grad_thresh: switched off (a zero field means the default) */
+#define VG_DENSE_BA_SIGMA_GREY 5.0
+#define VG_DENSE_BA_PRIOR_WEIGHT 1.0
+#define VG_DENSE_BA_GRAD_THRESH 250.0    /* GRAD_THRESH of initPhotometricData */
+#define VG_DENSE_BA_MAX_ITERATIONS 150
+#define VG_DENSE_BA_FUNCTION_TOLERANCE 1e-6
+typedef struct vg_dense_ba_options {
+    double sigma_grey;         /* the grey residual's sigma; 0: 5.  The reference divides the greys by 255 */
+    double prior_weight;       /* lambda of the depth prior; 0: 1; negative: no prior (the reference has none) */
+    double grad_thresh;        /* a cell is kept when gu^2 + gv^2 >= grad_thresh; 0: 250; negative: every cell (the reference) */
+    int max_iterations;        /* 0: 150 */
+    double function_tolerance; /* 0: 1e-6 */
+} vg_dense_ba_options;
+typedef struct vg_dense_ba vg_dense_ba;
+/* A handle for one EUCM camera (eucm: HOST 6 intrinsics), the depth map's geometry (of `params` only the ScaleParameters
+ * fields are read, as by vg_photometric_create), xi_base_cam (HOST [6]) and the image size.  options NULL: the defaults; a
+ * negative sigma_grey, max_iterations or function_tolerance is refused. */
+int vg_dense_ba_create(vg_dense_ba **out, int device, void *hip_stream, const double *eucm, const vg_stereo_params *params,
+                       const double *xi_base_cam, int width, int height, const vg_dense_ba_options *options);
+void vg_dense_ba_destroy(vg_dense_ba *h);
+/* The key frame: its image (DEVICE u8 [height][width]), depth map and sigma map (may be NULL without a prior).  Builds the
+ * pack: the cells (x, y) of the depth grid in raster order, pixel (u, v) = (uConv(x), vConv(y)), whose depth is finite and at
+ * least MIN_DEPTH 0.25, whose pixel lies in the image and reconstructs, whose Sobel / 8 gradient has gu^2 + gv^2 >=
+ * grad_thresh and, with a prior, whose sigma is finite and positive.  The maps are copied: they are read during the call only. */
+int vg_dense_ba_set_base(vg_dense_ba *h, const uint8_t *img, const double *depth, const double *sigma);
+/* The F further frames, F in [1, 8]: DEVICE u8 [F][height][width]; they replace the earlier ones. */
+int vg_dense_ba_set_frames(vg_dense_ba *h, int frames, const uint8_t *imgs);
+/* Stage entry: the pack.  *count (HOST) receives the number of points m; indices (DEVICE int32 [m], y x_max + x), greys (DEVICE
+ * FP64 [m], 0 .. 255), dirs (DEVICE FP64 [m][3], unit), d0 and sigma0 (DEVICE FP64 [m]) may be NULL -- ask for the count first. */
+int vg_dense_ba_pack(vg_dense_ba *h, int64_t *count, int32_t *indices, double *greys, double *dirs, double *d0, double *sigma0);
+/* Stage entry: residuals and Jacobians at the poses xi (HOST [F][6]) and the depths (DEVICE [m]; NULL: d0).  residuals DEVICE
+ * [F][m], jac_pose DEVICE [F][m][6], jac_depth DEVICE [F][m], a (the depth block's diagonal, sum_f jd^2 + (lambda / sigma0)^2)
+ * and g_depth (its gradient) DEVICE [m]; cost HOST [1]; sums HOST [F][28]: per frame J_pose^T J_pose (upper triangle row-major,
+ * 21), J_pose^T r (6), 1/2 sum r^2.  Any output may be NULL.  A point that does not project, or whose coordinates exceed
+ * +-2^24 px, has a zero residual and zero rows.  All sums are FP64 in a fixed order: bit-identical from run to run.  The rows
+ * stay in the handle for vg_dense_ba_reduce and vg_dense_ba_back_substitute. */
+int vg_dense_ba_evaluate(vg_dense_ba *h, const double *xi, const double *depths, double *residuals, double *jac_pose, double *jac_depth,
+                         double *a, double *g_depth, double *cost, double *sums);
+/* Stage entry: the reduced system of the last evaluation under the damping mu > 0, with e_i = a_i + mu clamp(a_i, 1e-6, 1e32)
+ * and w_i the stack of J_pose[f][i] jd[f][i] over the frames: S = H_pp + mu D_p - sum_i w_i w_i^T / e_i (HOST [K][K], K = 6 F,
+ * symmetric) and rhs = g_p - sum_i w_i g_di / e_i (HOST [K]).  VG_ERR_STATE before an evaluation. */
+int vg_dense_ba_reduce(vg_dense_ba *h, double mu, double *S, double *rhs);
+/* Stage entry: the depth step of the pose step dp (HOST [K]) under mu, dd_i = -(g_di + w_i . dp) / e_i: the candidate depths
+ * d_i + dd_i (DEVICE [m], may be NULL) and the depth block's share of the rule's sums (HOST [VG_DENSE_BA_TAIL]). */
+int vg_dense_ba_back_substitute(vg_dense_ba *h, double mu, const double *dp, double *candidate, double *tail);
+/* The solve from the start poses (HOST [F][6]) and the key frame's depths: xi_out HOST [F][6]; depth_out / sigma_out DEVICE
+ * [y_max][x_max] (may be NULL): the input maps outside the pack, the refined depth and 1 / sqrt(a_i) at the solution inside it;
+ * report HOST [4] (may be NULL): iterations, initial cost, final cost, vg_termination.  An empty pack is refused. */
+int vg_dense_ba_solve(vg_dense_ba *h, const double *xi_start, double *xi_out, double *depth_out, double *sigma_out, double *report);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",
  * "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop", "solver_no_fold_frames",

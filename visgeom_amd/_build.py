@@ -32,7 +32,8 @@ def sources():
     vg_corners_tu: checkerboard corner detection; vg_stereo_tu: fisheye semi-global stereo; vg_motion_tu: motion stereo;
     vg_depth_tu: depth map warp / merge / noise filter; vg_photometric_tu: photometric pose estimation;
     vg_sparse_odom_tu: sparse visual odometry; vg_render_tu: synthetic scene renderer; vg_mono_odom_tu: monocular visual
-    odometry; vg_mapping_tu: photometric mapping; vg_trajectory_tu: calibration trajectory planning)"""
+    odometry; vg_mapping_tu: photometric mapping; vg_trajectory_tu: calibration trajectory planning; vg_dense_ba_tu: photometric
+    bundle adjustment)"""
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
 
 

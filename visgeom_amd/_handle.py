@@ -1,5 +1,5 @@
-"""What the torch wrappers share.  All nine (stereo, motion_stereo, depth_fusion, photometric, sparse_odom, render, mono_odom,
-mapping, trajectory): the life of a library handle and its stream, and the argument checks; a new pipeline's wrapper derives from Handle.
+"""What the torch wrappers share.  All ten (stereo, motion_stereo, depth_fusion, photometric, sparse_odom, render, mono_odom,
+mapping, trajectory, dense_ba): the life of a library handle and its stream, and the argument checks; a new pipeline's wrapper derives from Handle.
 The two frame loops built on the pipelines (mono_odom, mapping) derive from LoopHandle, which adds what a vg_mono_odom and a
 vg_mapping handle have in common."""
 import ctypes

@@ -308,6 +308,15 @@ SIGNATURES = {
     "vg_trajectory_optimize": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _vp, _dp, _i32p, _i32p]),
     "vg_trajectory_project_board": (ctypes.c_int, [ctypes.c_int, _dp, _vp, _dp, _dp, _i32p]),
     "vg_trajectory_launch_count": (ctypes.c_int, [_vp, _i64p]),
+    "vg_dense_ba_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, _dp, _vp, _dp, ctypes.c_int, ctypes.c_int, _vp]),
+    "vg_dense_ba_destroy": (None, [_vp]),
+    "vg_dense_ba_set_base": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "vg_dense_ba_set_frames": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+    "vg_dense_ba_pack": (ctypes.c_int, [_vp, _i64p, _vp, _vp, _vp, _vp, _vp]),
+    "vg_dense_ba_evaluate": (ctypes.c_int, [_vp, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _dp, _dp]),
+    "vg_dense_ba_reduce": (ctypes.c_int, [_vp, ctypes.c_double, _dp, _dp]),
+    "vg_dense_ba_back_substitute": (ctypes.c_int, [_vp, ctypes.c_double, _dp, _vp, _dp]),
+    "vg_dense_ba_solve": (ctypes.c_int, [_vp, _dp, _dp, _vp, _vp, _dp]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),
@@ -334,6 +343,12 @@ class MotionStereoParams(ctypes.Structure):
 class MiOptions(ctypes.Structure):
     """struct vg_mi_options; a zero field means the reference's value (MI_DEFAULTS)"""
     _fields_ = [("function_tolerance", ctypes.c_double), ("gradient_tolerance", ctypes.c_double), ("max_iterations", ctypes.c_int)]
+
+
+class DenseBaOptions(ctypes.Structure):
+    """struct vg_dense_ba_options; a zero field means the default (DENSE_BA_DEFAULTS), DENSE_BA_NONE switches off"""
+    _fields_ = [("sigma_grey", ctypes.c_double), ("prior_weight", ctypes.c_double), ("grad_thresh", ctypes.c_double),
+                ("max_iterations", ctypes.c_int), ("function_tolerance", ctypes.c_double)]
 
 
 class SparseOdomParams(ctypes.Structure):
@@ -392,6 +407,8 @@ MAPPING_WARNING_NONE, MAPPING_WARNING_SCALE, MAPPING_WARNING_ROTATION = range(3)
 MAPPING_REPORT = 32
 MI_NUM_BINS, MI_VALUE_MAX, MI_ODOMETRY_DAMPING = 8, 255., 0.0002
 MI_DEFAULTS = {"function_tolerance": 1e-2, "gradient_tolerance": 1e-3, "max_iterations": 50}
+DENSE_BA_MAX_FRAMES, DENSE_BA_TAIL, DENSE_BA_NONE = 8, 5, -1.
+DENSE_BA_DEFAULTS = {"sigma_grey": 5., "prior_weight": 1., "grad_thresh": 250., "max_iterations": 150, "function_tolerance": 1e-6}
 
 
 class VisgeomError(RuntimeError):
