@@ -609,13 +609,15 @@ int vg_corner_detector_chunk(const vg_corner_detector *d, int width, int height,
 
 /* =====================================================================================
  * 9. Dense fisheye stereo: the reference's EnhancedSgm (src/reconstruction/eucm_sgm.cpp), semi-global matching along the
- *    epipolar curves of two unrectified EUCM images, hypotheses = 1.  Images are DEVICE u8 [n][v_max][u_max], dense; depth
- *    maps are [n][y_max][x_max].  The calls are synchronous on the handle's stream.  Deviations: DESIGN.md section 9.
+ *    epipolar curves of two unrectified EUCM images, one hypothesis per pixel or up to 8 (vg_stereo_compute_mh).  Images are
+ *    DEVICE u8 [n][v_max][u_max], dense; depth maps are [n][y_max][x_max].  The calls are synchronous on the handle's stream.
+ *    Deviations: DESIGN.md section 9.
  * ===================================================================================== */
 typedef struct vg_stereo vg_stereo;
 /* ScaleParameters + StereoParameters + SgmParameters (scale_parameters.h, eucm_stereo.h:34-60, eucm_sgm.h:41-70).  equal_margins
  * != 0 replaces x_max / y_max by (u_max - 2 u0) / scale + 1 and (v_max - 2 v0) / scale + 1.  epipole_margin is the SQUARED
- * pixel distance (the JSON key holds the distance).  verbosity is ignored; hypotheses must be 1. */
+ * pixel distance (the JSON key holds the distance).  verbosity is ignored; hypotheses must be 1, in the struct and in the JSON
+ * (vg_stereo_compute_mh takes the hypothesis count per call; hypo_difference is read there). */
 typedef struct vg_stereo_params {
     int scale, u0, v0, u_max, v_max, x_max, y_max, equal_margins;
     int num_epipolar_planes, epipole_margin;
@@ -647,6 +649,20 @@ int vg_stereo_compute(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const 
                       double *cost, int32_t *disparity);
 /* the number of pairs one chunk of vg_stereo_compute holds */
 int vg_stereo_chunk(const vg_stereo *s, int64_t *pairs);
+/* Multi-hypothesis stereo: computeStereo with hypMax = hyp_max, EnhancedSgm::reconstructDisparityMH (eucm_sgm.cpp:628-738) in
+ * place of reconstructDisparity.  The hypothesis count is an argument of the call: vg_stereo_params.hypotheses (and the JSON
+ * key) must still be 1 at creation; maxHypDiff is the handle's hypo_difference.  hyp_max must be in [2, 8] and at most disp_max
+ * (1 is vg_stereo_compute); n_pairs at least 1.  Per pixel, among the disparities d in [0, disp_max) whose matching error is
+ * at most error_max, a local minimum of the aggregated cost (below its next valid disparity, not above its previous one)
+ * reports the disparity in front of its next valid one; plane h holds the cheapest minimum dearer than plane h - 1's (or as
+ * dear at another disparity) and, from h = 1 on, within hypo_difference of it; the planes after the last one found hold -1.
+ * DEVICE outputs [n][hyp_max][y_max][x_max] (the reference's plane layout), each may be NULL: depth, sigma, cost FP64 as
+ * vg_stereo_compute gives them per plane (cost of plane h: the matching error at index h, as the reference reports it),
+ * disparity int32 (-1 = none) and final_cost int32 (the aggregated cost of the plane's minimum, INT32_MAX where disparity is
+ * -1).  Arguments are checked before HIP is touched.  Device scratch: at most max(2 GiB, one pair's) of 5 disp_max + 3 +
+ * 4 hyp_max bytes per depth pixel per pair; larger batches are worked through in chunks.  Deviations: DESIGN.md section 9. */
+int vg_stereo_compute_mh(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const uint8_t *img2, int hyp_max, double *depth,
+                         double *sigma, double *cost, int32_t *disparity, int32_t *final_cost);
 /* Stage entry: the per-pixel geometry, DEVICE int32 [y_max][x_max][8]: status (1 camera 1 reconstructs the pixel, 2 its
  * point at infinity projects into camera 2), round(pinf) u, v, the curve index, chooseEpipole flags of camera 1 and 2
  * (1 inverted, 2 too close), 0, 0. */
@@ -751,6 +767,19 @@ int vg_depth_merge(vg_depth_fusion *h, int64_t n, double *depth, double *sigma, 
  * with a depth, cleared, smoothed. */
 int vg_depth_filter_noise(vg_depth_fusion *h, int64_t n, const double *depth_in, const double *sigma_in, double *depth, double *sigma,
                           int64_t *counts);
+/* Maps with hypothesis planes (vg_stereo_compute_mh): DEVICE FP64 [n][hyp_max][y_max][x_max], hyp_max in [1, 8].
+ * DepthMap::regularize (depth_map.cpp:960-983) of n such maps, in place: per pixel and for h ascending, a plane whose depth is
+ * below MIN_DEPTH takes depth, sigma and cost of the first plane above it that holds one, and that plane's depth becomes 0
+ * (its sigma and cost stay).  The three arrays must not overlap. */
+int vg_depth_regularize(vg_depth_fusion *h, int64_t n, int hyp_max, double *depth, double *sigma, double *cost);
+/* DepthMap::reconstruct(pack, ALL_HYPOTHESES | SIGMA_VALUE) (depth_map.cpp:532-635) of ONE map [hyp_max][y_max][x_max]: the
+ * pixels whose plane 0 holds a depth >= MIN_DEPTH, in raster order, give one entry per plane with a depth >= MIN_DEPTH, h
+ * ascending.  count (HOST, required) receives the number of entries; call once with the four outputs NULL to learn it, then
+ * with DEVICE arrays of that many entries (hyp_max x_max y_max always suffice), each may be NULL: indices int32 (y x_max + x),
+ * hyp int32, cloud FP64 [count][3] (the pixel's normalised ray times the depth; (0, 0, 0) for a pixel the camera cannot
+ * reconstruct) and sigma_out FP64 (needs sigma).  The order is the same on every run. */
+int vg_depth_pack_mh(vg_depth_fusion *h, int hyp_max, const double *depth, const double *sigma, int64_t *count, int32_t *indices,
+                     int32_t *hyp, double *cloud, double *sigma_out);
 /* Host only, for the key-frame loop: Transformation::inverse (transformation.h:112-119) and inverseCompose (:90-99, a^-1 o b:
  * the pose b re-expressed in the frame a), on [t, rotvec]. */
 int vg_transform_inverse(const double *xi, double *out6);

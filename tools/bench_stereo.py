@@ -13,7 +13,10 @@ Stages (each entry synchronises the handle's stream; the events bracket it on th
                                                            + columns 14 D + 4 (err read twice, sum read-write, sum read, winner)
   depth      vg_stereo_compute - vg_stereo_aggregate  bytes: 64 per depth pixel (geometry 32, err, step, salient, skip, winner,
                                                            depth / sigma / cost written)
-  compute    vg_stereo_compute (the product call)
+  compute    vg_stereo_compute (the product call), with the least and the greatest of its repetitions: its run-to-run spread
+  compute_mh vg_stereo_compute_mh at 2 and 4 hypotheses next to it: the selection rides in the column pass, the depth launch
+             grows with the planes                  bytes beyond compute's: 4 more winner planes written (disparity, final
+                                                           cost) and (K - 1) x 64 in the depth launch, per depth pixel
 
 usage: python tools/bench_stereo.py [reps]     (one JSON line per case)
 """
@@ -30,11 +33,12 @@ from visgeom_amd import stereo  # noqa: E402
 
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 HBM_PEAK = 8.0e12
+MH = (2, 4)   # hypothesis counts of the compute_mh section
 EXAMPLE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "ex_epipolar_stereo.json")
 
 
-def timed(fn, stream):
-    """median seconds of fn() over REPS calls after one warm-up, HIP events on `stream`"""
+def timed(fn, stream, spread=False):
+    """median seconds of fn() over REPS calls after one warm-up, HIP events on `stream`; spread: (median, least, greatest)"""
     fn()
     ts = []
     for _ in range(REPS):
@@ -44,7 +48,7 @@ def timed(fn, stream):
         b.record(stream)
         b.synchronize()
         ts.append(a.elapsed_time(b) * 1e-3)
-    return float(np.median(ts))
+    return (float(np.median(ts)), float(min(ts)), float(max(ts))) if spread else float(np.median(ts))
 
 
 def case(ex, half, n):
@@ -65,14 +69,17 @@ def case(ex, half, n):
     st = s._stream
     t_cost = timed(lambda: s.curve_cost(a, b), st)
     t_agg = timed(lambda: s.aggregate(a, b), st)
-    t_all = timed(lambda: s.compute(a, b), st)
+    t_all, t_lo, t_hi = timed(lambda: s.compute(a, b), st, spread=True)
+    t_mh = {k: timed(lambda: s.compute_mh(a, b, k), st) for k in MH}
     dep = s.compute(a, b)[0]
     P, D = s.x_max * s.y_max, p.disp_max
     stages = {"cost": (t_cost, n * P * (D + 3)), "aggregate": (t_agg - t_cost, n * P * (28 * D + 4)),
               "depth": (t_all - t_agg, n * P * 64)}
     rec = {"workload": "stereo", "u_max": p.u_max, "v_max": p.v_max, "x_max": s.x_max, "y_max": s.y_max, "disp_max": D,
            "desc_length": p.desc_length, "scales": list(p.scales)[:p.n_scales], "use_uv_cache": p.use_uv_cache, "pairs": n,
-           "chunk": s.chunk(), "compute_ms": t_all * 1e3, "depth_pixels_per_s": n * P / t_all,
+           "chunk": s.chunk(), "compute_ms": t_all * 1e3, "compute_ms_min": t_lo * 1e3, "compute_ms_max": t_hi * 1e3,
+           "compute_mh_ms": {str(k): t * 1e3 for k, t in t_mh.items()}, "compute_mh_over_compute": {str(k): t / t_all for k, t in t_mh.items()},
+           "hypo_difference": p.hypo_difference, "depth_pixels_per_s": n * P / t_all,
            "valid_fraction": float((dep > 0).float().mean()), "stages": {}}
     for k, (t, by) in stages.items():
         rec["stages"][k] = {"ms": t * 1e3, "algorithmic_bytes": by, "GB_per_s": by / t / 1e9, "frac_hbm_peak": by / t / HBM_PEAK}

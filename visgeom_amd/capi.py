@@ -197,6 +197,7 @@ SIGNATURES = {
     "vg_stereo_size": (ctypes.c_int, [_vp, _ip, _ip]),
     "vg_stereo_chunk": (ctypes.c_int, [_vp, _i64p]),
     "vg_stereo_compute": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vg_stereo_compute_mh": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "vg_stereo_geometry": (ctypes.c_int, [_vp, _vp]),
     "vg_stereo_curve_cost": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vg_stereo_aggregate": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
@@ -216,6 +217,8 @@ SIGNATURES = {
     "vg_depth_warp": (ctypes.c_int, [_vp, ctypes.c_int64, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _i64p]),
     "vg_depth_merge": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _i64p]),
     "vg_depth_filter_noise": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _i64p]),
+    "vg_depth_regularize": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
+    "vg_depth_pack_mh": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _i64p, _vp, _vp, _vp, _vp]),
     "vg_transform_inverse": (ctypes.c_int, [_dp, _dp]),
     "vg_transform_inverse_compose": (ctypes.c_int, [_dp, _dp, _dp]),
     "vg_photometric_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, _dp, _vp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),

@@ -15,6 +15,7 @@
 
 #include "vg_bicubic.hpp"
 #include "vg_camera.hpp"
+#include "vg_compact.hpp"
 #include "vg_stereo_device.hpp"
 
 namespace vgba {
@@ -95,7 +96,8 @@ VGS_HD bool select_cell(const SelectArgs &a, int64_t cell, double &value, double
     return true;
 }
 
-// pass 1 (WRITE = false): the survivors of every block of 256 cells; pass 2: their raster-ordered places
+// pass 1 (WRITE = false): the survivors of every block of 256 cells; pass 2: their raster-ordered places from the scanned
+// block counts (vg_compact.hpp)
 template <bool WRITE>
 __global__ __launch_bounds__(kLanes) void ba_select_kernel(SelectArgs a)
 {
@@ -119,33 +121,6 @@ __global__ __launch_bounds__(kLanes) void ba_select_kernel(SelectArgs a)
     for (int i = 0; i < 3; i++) a.dir[3 * (int64_t)pos + i] = dir[i];
     a.d0[pos] = d;
     a.s0[pos] = s;
-}
-
-// exclusive scan of the block counts, one workgroup: a contiguous run per thread, the 256 run sums in order
-__global__ __launch_bounds__(kLanes) void ba_scan_kernel(const unsigned *counts, unsigned *offsets, int nb, unsigned *total)
-{
-    __shared__ unsigned run_sum[kLanes];
-    const int chunk = (nb + kLanes - 1) / kLanes;
-    const int lo = min((int)threadIdx.x * chunk, nb), hi = min(lo + chunk, nb);
-    unsigned s = 0;
-    for (int i = lo; i < hi; i++) s += counts[i];
-    run_sum[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned run = 0;
-        for (int t = 0; t < kLanes; t++) {
-            const unsigned c = run_sum[t];
-            run_sum[t] = run;
-            run += c;
-        }
-        *total = run;
-    }
-    __syncthreads();
-    unsigned run = run_sum[threadIdx.x];
-    for (int i = lo; i < hi; i++) {
-        offsets[i] = run;
-        run += counts[i];
-    }
 }
 
 // ---- evaluate --------------------------------------------------------------------------------------------------------
@@ -277,7 +252,7 @@ __global__ __launch_bounds__(kLanes) void ba_point_kernel(PointArgs a)
 }
 
 // The second pass of every sum here, by one wave: the n values p[i stride] in index order, split into 64 contiguous runs -- lane
-// t adds run t in order, lane 0 adds the 64 run sums in order (the association of ba_scan_kernel's scan).  A chain of n / 64 + 64
+// t adds run t in order, lane 0 adds the 64 run sums in order (the association of vg_compact.hpp's scan).  A chain of n / 64 + 64
 // additions instead of n; the order depends on n alone.  MAX: the maximum instead.  The result is lane 0's.
 template <bool MAX>
 __device__ __forceinline__ double run_sum64(const double *p, int64_t stride, int n, double *lds)

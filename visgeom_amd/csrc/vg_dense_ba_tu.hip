@@ -338,7 +338,7 @@ int vg_dense_ba_set_base(vg_dense_ba *s, const uint8_t *img, const double *depth
     a.d0 = s->d_d0;
     a.s0 = s->d_s0;
     hipLaunchKernelGGL((vgba::ba_select_kernel<false>), dim3(nb), dim3(vgba::kLanes), 0, s->stream, a);
-    hipLaunchKernelGGL(vgba::ba_scan_kernel, dim3(1), dim3(vgba::kLanes), 0, s->stream, (const unsigned *)s->d_counts.get(), s->d_offsets.get(), (int)nb,
+    hipLaunchKernelGGL(vgc::scan_block_counts_kernel<vgba::kLanes>, dim3(1), dim3(vgba::kLanes), 0, s->stream, (const unsigned *)s->d_counts.get(), s->d_offsets.get(), (int)nb,
                        s->d_total.get());
     hipLaunchKernelGGL((vgba::ba_select_kernel<true>), dim3(nb), dim3(vgba::kLanes), 0, s->stream, a);
     VG_HIP(hipGetLastError());

@@ -220,4 +220,86 @@ __global__ __launch_bounds__(kLanes) void depth_filter_noise_kernel(const double
     }
 }
 
+constexpr int kMaxHyp = 8;   // hypothesis planes of a map: [n][hyp_max][P]
+
+// DepthMap::regularize (depth_map.cpp:960-983), in place: one lane per (item, pixel) walks its planes in ascending order.  A
+// plane below MIN_DEPTH takes (depth, sigma, cost) of the first filled plane above it, whose depth is then cleared; its sigma
+// and cost stay.  The pixels are independent, so the reference's plane-major loop leaves the same maps.
+__global__ __launch_bounds__(kLanes) void depth_regularize_kernel(double *depth, double *sigma, double *cost, int hyp_max, int64_t P)
+{
+    const int64_t item = blockIdx.y, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
+    if (pix >= P) return;
+    const int64_t base = item * hyp_max * P + pix;
+    for (int h = 0; h < hyp_max - 1; h++) {
+        if (!(depth[base + h * P] < kMinDepth)) continue;
+        int h2 = h + 1;
+        while (h2 < hyp_max && depth[base + h2 * P] < kMinDepth) h2++;
+        if (h2 == hyp_max) continue;
+        depth[base + h * P] = depth[base + h2 * P];
+        sigma[base + h * P] = sigma[base + h2 * P];
+        cost[base + h * P] = cost[base + h2 * P];
+        depth[base + h2 * P] = 0.;
+    }
+}
+
+struct PackMhArgs {
+    double cam[6];
+    Grid g;
+    int hyp_max;
+    const double *depth, *sigma;    // [hyp_max][P]; sigma may be NULL when sigma_out is
+    unsigned *block_counts;         // [blocks]
+    const unsigned *block_offsets;
+    int32_t *indices, *hyp;         // the pack, each may be NULL
+    double *cloud, *sigma_out;
+};
+
+// DepthMap::reconstruct(pack, ALL_HYPOTHESES | SIGMA_VALUE) (depth_map.cpp:532-635) of one map, compacted in the reference's
+// order: the pixels whose plane 0 holds a depth (getIdxVec) in raster order, and of each its filled planes in ascending order.
+// Pass 1 (WRITE = false) counts the entries of every block of 256 pixels; pass 2 places them from the scanned block counts,
+// one wave ballot per plane and the lanes below -- the ordered compaction of the photometric data pack (vg_compact.hpp) with
+// up to hyp_max entries per lane.
+template <bool WRITE>
+__global__ __launch_bounds__(kLanes) void depth_pack_mh_kernel(PackMhArgs a)
+{
+    __shared__ unsigned wave_count[kLanes / 64];
+    const int64_t P = (int64_t)a.g.x_max * a.g.y_max, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool query = pix < P && a.depth[pix] >= kMinDepth;
+    double d[kMaxHyp];
+    unsigned below = 0, total = 0;   // entries of the wave's lower lanes, of the whole wave
+#pragma unroll
+    for (int h = 0; h < kMaxHyp; h++) {
+        d[h] = (query && h < a.hyp_max) ? a.depth[h * P + pix] : 0.;
+        const unsigned long long ball = __ballot(d[h] >= kMinDepth);
+        below += (unsigned)__popcll(ball & ((1ull << lane) - 1ull));
+        total += (unsigned)__popcll(ball);
+    }
+    if (lane == 0) wave_count[wave] = total;
+    __syncthreads();
+    if (!WRITE) {
+        if (threadIdx.x == 0) a.block_counts[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+        return;
+    }
+    if (!query) return;
+    int64_t pos = a.block_offsets[blockIdx.x] + below;
+    for (int k = 0; k < wave; k++) pos += wave_count[k];
+    const int x = (int)(pix % a.g.x_max), y = (int)(pix / a.g.x_max);
+    double X[3], dir[3] = {0., 0., 0.};
+    const bool seen = a.cloud && eucm_reconstruct(a.cam, (double)(x * a.g.scale + a.g.u0), (double)(y * a.g.scale + a.g.v0), X);
+    if (seen) {
+        const double nrm = sqrt(dot3(X, X));
+        for (int i = 0; i < 3; i++) dir[i] = X[i] / nrm;   // normalized()
+    }
+#pragma unroll
+    for (int h = 0; h < kMaxHyp; h++) {   // d[h] is 0 from hyp_max on
+        if (!(d[h] >= kMinDepth)) continue;
+        if (a.indices) a.indices[pos] = (int32_t)pix;
+        if (a.hyp) a.hyp[pos] = h;
+        if (a.sigma_out) a.sigma_out[pos] = a.sigma[h * P + pix];
+        if (a.cloud)
+            for (int i = 0; i < 3; i++) a.cloud[3 * pos + i] = seen ? dir[i] * d[h] : 0.;   // a pixel the camera refuses: (0, 0, 0)
+        pos++;
+    }
+}
+
 }  // namespace vgd

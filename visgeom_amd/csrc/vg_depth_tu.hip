@@ -4,13 +4,14 @@
 // A vg_depth_fusion handle owns the scratch of its three operations: the warp's z-buffer and winner buffer (12 bytes per
 // depth pixel and item, all ones between calls: the gather kernel restores what it read), the per-item poses with the warp's
 // counters in one pinned and one device array, the counters of merge and the noise filter, and the copy the noise filter
-// reads when it runs in place.  Buffers only grow.
+// reads when it runs in place, and the block counts of the multi-hypothesis pack.  Buffers only grow.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <memory>
 #include <new>
 
+#include "vg_compact.hpp"
 #include "vg_depth.hpp"
 #include "vg_handle.hpp"
 #include "vg_stereo_host.hpp"
@@ -27,6 +28,8 @@ struct vg_depth_fusion : vgi::HandleBase {
     vgi::Grow<unsigned long long> d_zbuf;   // [n][P], like the winner buffer
     vgi::Grow<unsigned> d_winner;
     vgi::Grow<double> d_copy;   // [2][n][P]
+    vgi::Grow<unsigned> d_pack_counts, d_pack_offsets, d_pack_total;   // per block of 256 pixels; [1]
+    vgi::GrowPinned<unsigned> h_pack_total;
 #ifdef VG_DEPTH_WARP_STORE
     vgi::Grow<int> d_src_target;
     vgi::Grow<double> d_src_dist;
@@ -222,6 +225,67 @@ int vg_depth_filter_noise(vg_depth_fusion *s, int64_t n, const double *depth_in,
                        sigma_in, depth, sigma, s->g, s->P, dc);
     VG_HIP(hipGetLastError());
     return s->counters.end(call, n, 3, counts);
+}
+
+int vg_depth_regularize(vg_depth_fusion *s, int64_t n, int hyp_max, double *depth, double *sigma, double *cost)
+{
+    if (const int rc = check_call(s, n)) return rc;
+    if (hyp_max < 1 || hyp_max > vgd::kMaxHyp) return fail(VG_ERR_INVALID_ARGUMENT, "hyp_max must be in [1, 8]");
+    if (n == 0) return VG_OK;
+    if (!depth || !sigma || !cost) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    const void *const p[3] = {depth, sigma, cost};
+    if (any_overlap(p, 3, (size_t)(n * hyp_max * s->P) * sizeof(double))) return fail(VG_ERR_INVALID_ARGUMENT, "the three maps must not overlap");
+    if (hyp_max == 1) return VG_OK;   // one plane has nothing above it
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    hipLaunchKernelGGL(vgd::depth_regularize_kernel, dim3(blocks_of(s->P, vgd::kLanes), (unsigned)n), dim3(vgd::kLanes), 0, s->stream, depth, sigma,
+                       cost, hyp_max, s->P);
+    VG_HIP(hipGetLastError());
+    return call.finish();
+}
+
+int vg_depth_pack_mh(vg_depth_fusion *s, int hyp_max, const double *depth, const double *sigma, int64_t *count, int32_t *indices, int32_t *hyp,
+                     double *cloud, double *sigma_out)
+{
+    if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "depth fusion handle is NULL");
+    if (hyp_max < 1 || hyp_max > vgd::kMaxHyp) return fail(VG_ERR_INVALID_ARGUMENT, "hyp_max must be in [1, 8]");
+    if (!depth || !count) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (sigma_out && !sigma) return fail(VG_ERR_INVALID_ARGUMENT, "sigma_out needs the sigma planes");
+    const unsigned nb = blocks_of(s->P, vgd::kLanes);
+    vgd::PackMhArgs a;
+    for (int i = 0; i < 6; i++) a.cam[i] = s->cam[i];
+    a.g = s->g;
+    a.hyp_max = hyp_max;
+    a.depth = depth;
+    a.sigma = sigma;
+    a.indices = indices;
+    a.hyp = hyp;
+    a.cloud = cloud;
+    a.sigma_out = sigma_out;
+    {   // the count: the entries of every block, scanned
+        vgi::Call call(s);
+        if (const int rc = call.begin()) return rc;
+        const char *what = "the pack's block counts";
+        if (const int rc = s->d_pack_counts.grow(nb, what)) return rc;
+        if (const int rc = s->d_pack_offsets.grow(nb, what)) return rc;
+        if (const int rc = s->d_pack_total.grow(1, what)) return rc;
+        if (const int rc = s->h_pack_total.grow(1, what)) return rc;
+        a.block_counts = s->d_pack_counts;
+        a.block_offsets = s->d_pack_offsets;
+        hipLaunchKernelGGL((vgd::depth_pack_mh_kernel<false>), dim3(nb), dim3(vgd::kLanes), 0, s->stream, a);
+        hipLaunchKernelGGL(vgc::scan_block_counts_kernel<vgd::kLanes>, dim3(1), dim3(vgd::kLanes), 0, s->stream, (const unsigned *)s->d_pack_counts.get(),
+                           s->d_pack_offsets.get(), (int)nb, s->d_pack_total.get());
+        VG_HIP(hipGetLastError());
+        VG_HIP(hipMemcpyAsync(s->h_pack_total, s->d_pack_total, sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+        if (const int rc = call.finish()) return rc;
+    }
+    *count = (int64_t)s->h_pack_total.get()[0];
+    if (*count == 0 || (!indices && !hyp && !cloud && !sigma_out)) return VG_OK;
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    hipLaunchKernelGGL((vgd::depth_pack_mh_kernel<true>), dim3(nb), dim3(vgd::kLanes), 0, s->stream, a);
+    VG_HIP(hipGetLastError());
+    return call.finish();
 }
 
 int vg_transform_inverse(const double *xi, double *out6)

@@ -10,6 +10,7 @@
 
 #include "vg_bicubic.hpp"
 #include "vg_camera.hpp"
+#include "vg_compact.hpp"
 #include "vg_stereo_device.hpp"
 
 namespace vgp {
@@ -117,7 +118,7 @@ VGS_HD bool select_point(const SelectArgs &a, int64_t pix, double &value, double
 }
 
 // pass 1 (WRITE = false): the survivors of every block of 256 pixels; pass 2: their raster-ordered places from the scanned
-// block counts, the wave ballots and the lanes below
+// block counts (vg_compact.hpp), the wave ballots and the lanes below
 template <bool WRITE>
 __global__ __launch_bounds__(kLanes) void photo_select_kernel(SelectArgs a)
 {
@@ -139,33 +140,6 @@ __global__ __launch_bounds__(kLanes) void photo_select_kernel(SelectArgs a)
     a.idx[pos] = (int32_t)pix;
     a.val[pos] = value;
     for (int i = 0; i < 3; i++) a.cloud[3 * (int64_t)pos + i] = X[i];
-}
-
-// exclusive scan of the block counts, one workgroup: a contiguous run per thread, the 256 run sums in order
-__global__ __launch_bounds__(kLanes) void photo_scan_kernel(const unsigned *counts, unsigned *offsets, int nb, unsigned *total)
-{
-    __shared__ unsigned run_sum[kLanes];
-    const int chunk = (nb + kLanes - 1) / kLanes;
-    const int lo = min((int)threadIdx.x * chunk, nb), hi = min(lo + chunk, nb);
-    unsigned s = 0;
-    for (int i = lo; i < hi; i++) s += counts[i];
-    run_sum[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned run = 0;
-        for (int t = 0; t < kLanes; t++) {
-            const unsigned c = run_sum[t];
-            run_sum[t] = run;
-            run += c;
-        }
-        *total = run;
-    }
-    __syncthreads();
-    unsigned run = run_sum[threadIdx.x];
-    for (int i = lo; i < hi; i++) {
-        offsets[i] = run;
-        run += counts[i];
-    }
 }
 
 // ---- the cost --------------------------------------------------------------------------------------------------------

@@ -324,7 +324,7 @@ static int launch_packs(vg_photometric *s, const double *depth, bool sobel)
         a.val = s->d_val.get() + s->off[i];
         a.cloud = s->d_cloud.get() + 3 * s->off[i];
         hipLaunchKernelGGL((vgp::photo_select_kernel<false>), dim3(nb), dim3(vgp::kLanes), 0, s->stream, a);
-        hipLaunchKernelGGL(vgp::photo_scan_kernel, dim3(1), dim3(vgp::kLanes), 0, s->stream, (const unsigned *)s->d_counts.get(), s->d_offsets.get(),
+        hipLaunchKernelGGL(vgc::scan_block_counts_kernel<vgp::kLanes>, dim3(1), dim3(vgp::kLanes), 0, s->stream, (const unsigned *)s->d_counts.get(), s->d_offsets.get(),
                            (int)nb, s->d_total.get() + i);
         hipLaunchKernelGGL((vgp::photo_select_kernel<true>), dim3(nb), dim3(vgp::kLanes), 0, s->stream, a);
         // MutualInformation's _hist1 depends on the pack only

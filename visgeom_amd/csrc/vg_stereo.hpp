@@ -1,7 +1,9 @@
 // vg_stereo.hpp -- dense fisheye stereo: the reference's EnhancedSgm (src/reconstruction/eucm_sgm.cpp), semi-global
 // matching along the epipolar curves of two unrectified EUCM images.  The four kernels: per-pixel geometry, curve cost,
 // directional aggregation (left+right, top+bottom with the winner) and depth, on the shared pieces of vg_stereo_device.hpp
-// (among them the descriptor and its matching, which motion stereo runs too).
+// (among them the descriptor and its matching, which motion stereo runs too).  The multi-hypothesis call runs the column
+// kernel's MH instantiation, which selects the K best local minima where it would take the winner, and the depth kernel over
+// the hypothesis planes.
 // The entries are in vg_stereo_tu.hip.
 #pragma once
 
@@ -264,9 +266,92 @@ __global__ __launch_bounds__(kAggLanes) void stereo_agg_rows_kernel(StereoGeom g
     }
 }
 
+constexpr int kMaxHyp = 8;           // hypotheses per pixel of the multi-hypothesis winner
+
+// what the multi-hypothesis winner adds to AggArgs: hyp_max in [2, kMaxHyp], maxHypDiff, and the two outputs
+struct MhArgs {
+    int hyp_max, hypo_difference;
+    int32_t *disparity, *final_cost;   // [n][hyp_max][P]; final_cost may be NULL
+};
+
+// the lowest set bit above position 64 q + b of the 256-bit mask m, -1 if none (q is a constant after unrolling)
+__device__ __forceinline__ int next_bit(const unsigned long long *m, int q, int b)
+{
+    const unsigned long long hi = b == 63 ? 0ull : m[q] & (~0ull << (b + 1));
+    if (hi) return q * 64 + __ffsll((long long)hi) - 1;
+    for (int w = q + 1; w < kAggPer; w++)
+        if (m[w]) return w * 64 + __ffsll((long long)m[w]) - 1;
+    return -1;
+}
+
+// the highest set bit below position 64 q + b, -1 if none
+__device__ __forceinline__ int prev_bit(const unsigned long long *m, int q, int b)
+{
+    const unsigned long long lo = m[q] & ((1ull << b) - 1ull);
+    if (lo) return q * 64 + 63 - __clzll((long long)lo);
+    for (int w = q - 1; w >= 0; w--)
+        if (m[w]) return w * 64 + 63 - __clzll((long long)m[w]);
+    return -1;
+}
+
+// reconstructDisparityMH (eucm_sgm.cpp:628-738) for one pixel, by the wave that holds its whole aggregated cost: cost[q] =
+// total - 2 err of this lane's disparities, valid[q] = err <= error_max.  A valid disparity is a candidate when its cost is
+// below its next valid neighbour's and not above its previous one's; it reports the disparity in front of that next neighbour.
+// hyp_max rounds each take the cheapest candidate (then the lowest disparity) that is dearer than the round before, or as dear
+// at another disparity, and from the second round on within hypo_difference of it.  lds is free between two dyn_steps; the
+// two barriers here keep it so.  Every lane of the wave calls this; lane 0 writes.
+__device__ __forceinline__ void select_hypotheses(const int *cost, const bool *valid, bool off, const MhArgs &m, int64_t out, int64_t P, int *lds)
+{
+    const int lane = threadIdx.x;
+    unsigned long long mask[kAggPer], cand[kAggPer];
+#pragma unroll
+    for (int q = 0; q < kAggPer; q++) {
+        mask[q] = __ballot(valid[q]);
+        if (valid[q]) lds[lane + q * kAggLanes] = cost[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kAggPer; q++) {
+        cand[q] = ~0ull;
+        if (valid[q]) {
+            const int nx = next_bit(mask, q, lane), pv = prev_bit(mask, q, lane);
+            if (nx >= 0 && cost[q] < lds[nx] && (pv < 0 || cost[q] <= lds[pv]))
+                cand[q] = (unsigned long long)(unsigned)cost[q] << 32 | (unsigned)(nx - 1);
+        }
+    }
+    __syncthreads();
+    long long min_cost = 0;
+    int min_disp = -1, h = 0;
+    for (; h < m.hyp_max && !off; h++) {
+        unsigned long long key = ~0ull;
+#pragma unroll
+        for (int q = 0; q < kAggPer; q++) {
+            const long long c = (long long)(cand[q] >> 32);
+            const int r = (int)(cand[q] & 0xffffffffu);
+            const bool ok = cand[q] != ~0ull && (c > min_cost || (c == min_cost && r != min_disp)) && (h == 0 || c <= min_cost + m.hypo_difference);
+            if (ok && cand[q] < key) key = cand[q];
+        }
+        key = wave_min_u64(key);
+        if (key == ~0ull) break;
+        min_cost = (long long)(key >> 32);
+        min_disp = (int)(key & 0xffffffffu);
+        if (lane == 0) {
+            m.disparity[out + h * P] = min_disp;
+            if (m.final_cost) m.final_cost[out + h * P] = (int32_t)min_cost;
+        }
+    }
+    if (lane == 0)
+        for (; h < m.hyp_max; h++) {
+            m.disparity[out + h * P] = -1;
+            if (m.final_cost) m.final_cost[out + h * P] = INT32_MAX;
+        }
+}
+
 // top then bottom tableaux of one column (eucm_sgm.cpp:544-576) added to sum; the bottom pass has the whole sum of every
-// pixel it reaches and picks the winner there (reconstructDisparity, eucm_sgm.cpp:580-626)
-__global__ __launch_bounds__(kAggLanes) void stereo_agg_cols_kernel(StereoGeom g, AggArgs a)
+// pixel it reaches and picks the winner there (reconstructDisparity, eucm_sgm.cpp:580-626; MH: the hyp_max winners of
+// reconstructDisparityMH, to m's planes instead of a.disparity)
+template <bool MH>
+__global__ __launch_bounds__(kAggLanes) void stereo_agg_cols_kernel(StereoGeom g, AggArgs a, MhArgs m)
 {
     __shared__ int lds[256];
     const int64_t colid = blockIdx.x;   // pair * x_max + x
@@ -296,6 +381,24 @@ __global__ __launch_bounds__(kAggLanes) void stereo_agg_cols_kernel(StereoGeom g
                     const int d = lane + q * kAggLanes;
                     if (d < D) s[d] += c[q];
                 }
+                continue;
+            }
+            if (MH) {
+                int cost[kAggPer];
+                bool valid[kAggPer];
+#pragma unroll
+                for (int q = 0; q < kAggPer; q++) {
+                    const int d = lane + q * kAggLanes;
+                    cost[q] = 0;
+                    valid[q] = false;
+                    if (d < D) {
+                        const int ev = er[d];
+                        cost[q] = s[d] + c[q] - 2 * ev;
+                        valid[q] = ev <= g.error_max;
+                    }
+                }
+                // the skip buffer is not consulted (eucm_sgm.cpp:643)
+                select_hypotheses(cost, valid, g.salient_points_only && a.salient[p] == 0, m, pair * m.hyp_max * P + (int64_t)y * X + x, P, lds);
                 continue;
             }
             unsigned long long key = ~0ull;
@@ -329,7 +432,42 @@ struct DepthArgs {
     int64_t n_pairs;
 };
 
-// reconstructDepth (eucm_sgm.cpp:154-218) with the six-argument triangulate (eucm_stereo.cpp:250-296): one lane per pixel
+// one pixel of reconstructDepth (eucm_sgm.cpp:186-213) with the six-argument triangulate (eucm_stereo.cpp:250-296): the
+// range and its sigma at disparity `disp` (-1 is walked like any other), left as they are where the triangulation fails
+__device__ __forceinline__ void depth_at(const StereoGeom &g, const GeomEntry &ge, int64_t pix, int disp, int step, double &dep, double &sig)
+{
+    const int x = (int)(pix % g.x_max), y = (int)(pix / g.x_max);
+    int u21, v21, u22, v22;
+    if (g.use_uv_cache) {
+        CacheWalk cw;
+        cw.start(g, ge);
+        cw.go(kDisparityMargin + disp);
+        const bool in1 = inside(g, cw.r.u, cw.r.v);
+        u21 = in1 ? cw.r.u : -1;
+        v21 = in1 ? cw.r.v : -1;
+        cw.go(cw.k + step);
+        const bool in2 = inside(g, cw.r.u, cw.r.v);
+        u22 = in2 ? cw.r.u : -1;
+        v22 = in2 ? cw.r.v : -1;
+    } else {
+        Raster r;
+        make_raster(g, 1, ge.pinf_u, ge.pinf_v, ge.index, ge.flags2, r);
+        r.steps(disp);
+        u21 = r.u;
+        v21 = r.v;
+        r.steps(step);
+        u22 = r.u;
+        v22 = r.v;
+    }
+    const int gu = x * g.scale + g.u0, gv = y * g.scale + g.v0;
+    double l1, s1;
+    if (triangulate_pairs(g, gu, gv, gu, gv, u21, v21, u22, v22, l1, s1) && l1 < kTriangulateDistMax) {
+        sig = s1;
+        dep = l1;
+    }
+}
+
+// reconstructDepth (eucm_sgm.cpp:154-218): one lane per pixel
 __global__ __launch_bounds__(256) void stereo_depth_kernel(StereoGeom g, DepthArgs a)
 {
     const int64_t P = (int64_t)g.x_max * g.y_max;
@@ -340,36 +478,28 @@ __global__ __launch_bounds__(256) void stereo_depth_kernel(StereoGeom g, DepthAr
     const GeomEntry ge = a.geom[pix];
     if (!((g.salient_points_only && !a.salient[gi]) || a.skip[gi]) && (ge.status & kGeomMask)) {
         cst = (double)a.err[gi * g.disp_max];
-        const int x = (int)(pix % g.x_max), y = (int)(pix / g.x_max);
-        const int disp = a.disparity[gi], step = a.step[gi];
-        int u21, v21, u22, v22;
-        if (g.use_uv_cache) {
-            CacheWalk cw;
-            cw.start(g, ge);
-            cw.go(kDisparityMargin + disp);
-            const bool in1 = inside(g, cw.r.u, cw.r.v);
-            u21 = in1 ? cw.r.u : -1;
-            v21 = in1 ? cw.r.v : -1;
-            cw.go(cw.k + step);
-            const bool in2 = inside(g, cw.r.u, cw.r.v);
-            u22 = in2 ? cw.r.u : -1;
-            v22 = in2 ? cw.r.v : -1;
-        } else {
-            Raster r;
-            make_raster(g, 1, ge.pinf_u, ge.pinf_v, ge.index, ge.flags2, r);
-            r.steps(disp);
-            u21 = r.u;
-            v21 = r.v;
-            r.steps(step);
-            u22 = r.u;
-            v22 = r.v;
-        }
-        const int gu = x * g.scale + g.u0, gv = y * g.scale + g.v0;
-        double l1, s1;
-        if (triangulate_pairs(g, gu, gv, gu, gv, u21, v21, u22, v22, l1, s1) && l1 < kTriangulateDistMax) {
-            sig = s1;
-            dep = l1;
-        }
+        depth_at(g, ge, pix, a.disparity[gi], a.step[gi], dep, sig);
+    }
+    if (a.depth) a.depth[gi] = dep;
+    if (a.sigma) a.sigma[gi] = sig;
+    if (a.cost) a.cost[gi] = cst;
+}
+
+// reconstructDepth over the hypothesis planes: one lane per (pair, plane, pixel); a.disparity and the outputs are
+// [n][hyp_max][P], and the cost of plane h is the matching error at index h (eucm_sgm.cpp:174), not at the plane's disparity
+__global__ __launch_bounds__(256) void stereo_depth_mh_kernel(StereoGeom g, DepthArgs a, int hyp_max)
+{
+    const int64_t P = (int64_t)g.x_max * g.y_max;
+    const int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gi >= P * hyp_max * a.n_pairs) return;
+    const int64_t pix = gi % P, pair = gi / (P * hyp_max);
+    const int h = (int)(gi / P % hyp_max);
+    const int64_t pi = pair * P + pix;
+    double dep = 0., sig = 0., cst = 0.;
+    const GeomEntry ge = a.geom[pix];
+    if (!((g.salient_points_only && !a.salient[pi]) || a.skip[pi]) && (ge.status & kGeomMask)) {
+        cst = (double)a.err[pi * g.disp_max + h];
+        depth_at(g, ge, pix, a.disparity[gi], a.step[pi], dep, sig);
     }
     if (a.depth) a.depth[gi] = dep;
     if (a.sigma) a.sigma[gi] = sig;

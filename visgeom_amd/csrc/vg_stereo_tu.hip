@@ -3,7 +3,8 @@
 //
 // A vg_stereo handle owns the curve tables and the per-pixel geometry of one calibrated pair (built at creation) and the
 // device scratch of one chunk of pairs (grown on demand, at most max(kStereoBudget, one pair)).  A compute call runs four
-// launches per chunk: curve cost, left + right, top + bottom with the winner, depth.
+// launches per chunk: curve cost, left + right, top + bottom with the winner, depth.  vg_stereo_compute_mh runs the same
+// four with the multi-hypothesis variants of the last two: the winner planes take the place of the single winner.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -35,8 +36,9 @@ struct vg_stereo : vgi::HandleBase {
     vgi::Grow<uint8_t> d_scratch;   // bytes
     int64_t P = 0;
 
-    int64_t per_pair() const { return P * (5 * (int64_t)prm.disp_max + 7); }
-    int64_t chunk() const { return std::max<int64_t>(1, kStereoBudget / per_pair()); }
+    // hyp: winner planes per pixel (1: vg_stereo_compute)
+    int64_t per_pair(int hyp = 1) const { return P * (5 * (int64_t)prm.disp_max + 3 + 4 * (int64_t)hyp); }
+    int64_t chunk(int hyp = 1) const { return std::max<int64_t>(1, kStereoBudget / per_pair(hyp)); }
 };
 
 namespace {
@@ -47,16 +49,16 @@ struct Bufs {
     int32_t *sum = nullptr, *disp = nullptr;
 };
 
-// carve n pairs' err / step / salient / skip / sum / disparity out of the handle's scratch
-int scratch_bufs(vg_stereo *s, int64_t n, Bufs &b)
+// carve n pairs' err / step / salient / skip / sum / disparity (hyp planes) out of the handle's scratch
+int scratch_bufs(vg_stereo *s, int64_t n, Bufs &b, int hyp = 1)
 {
     const int64_t P = s->P, D = s->prm.disp_max;
-    if (const int rc = s->d_scratch.grow((size_t)(n * s->per_pair()), "the stereo scratch")) return rc;
+    if (const int rc = s->d_scratch.grow((size_t)(n * s->per_pair(hyp)), "the stereo scratch")) return rc;
     uint8_t *p = s->d_scratch.get();
     b.sum = reinterpret_cast<int32_t *>(p);
     p += n * P * D * 4;
     b.disp = reinterpret_cast<int32_t *>(p);
-    p += n * P * 4;
+    p += n * P * hyp * 4;
     b.err = p;
     p += n * P * D;
     b.step = p;
@@ -82,7 +84,8 @@ void launch_cost(vg_stereo *s, int64_t n, const uint8_t *img1, const uint8_t *im
                        s->g, a);
 }
 
-void launch_agg(vg_stereo *s, int64_t n, const Bufs &b, bool write_total)
+// mh == nullptr: the single winner to b.disp; otherwise the hypothesis planes to mh's arrays
+void launch_agg(vg_stereo *s, int64_t n, const Bufs &b, bool write_total, const vgs::MhArgs *mh = nullptr)
 {
     vgs::AggArgs a;
     a.err = b.err;
@@ -94,7 +97,9 @@ void launch_agg(vg_stereo *s, int64_t n, const Bufs &b, bool write_total)
     a.n_pairs = n;
     a.write_total = write_total ? 1 : 0;
     hipLaunchKernelGGL(vgs::stereo_agg_rows_kernel, dim3((unsigned)(n * s->g.y_max)), dim3(vgs::kAggLanes), 0, s->stream, s->g, a);
-    hipLaunchKernelGGL(vgs::stereo_agg_cols_kernel, dim3((unsigned)(n * s->g.x_max)), dim3(vgs::kAggLanes), 0, s->stream, s->g, a);
+    const dim3 cols((unsigned)(n * s->g.x_max)), lanes(vgs::kAggLanes);
+    if (mh) hipLaunchKernelGGL((vgs::stereo_agg_cols_kernel<true>), cols, lanes, 0, s->stream, s->g, a, *mh);
+    else hipLaunchKernelGGL((vgs::stereo_agg_cols_kernel<false>), cols, lanes, 0, s->stream, s->g, a, vgs::MhArgs{1, 0, nullptr, nullptr});
 }
 
 void launch_depth(vg_stereo *s, int64_t n, const Bufs &b, double *depth, double *sigma, double *cost)
@@ -111,6 +116,23 @@ void launch_depth(vg_stereo *s, int64_t n, const Bufs &b, double *depth, double 
     a.cost = cost;
     a.n_pairs = n;
     hipLaunchKernelGGL(vgs::stereo_depth_kernel, dim3(blocks_of(n * s->P, 256)), dim3(256), 0, s->stream, s->g, a);
+}
+
+// the hypothesis planes: disp and the outputs are [n][hyp][P]
+void launch_depth_mh(vg_stereo *s, int64_t n, const Bufs &b, int hyp, const int32_t *disp, double *depth, double *sigma, double *cost)
+{
+    vgs::DepthArgs a;
+    a.geom = s->d_geom;
+    a.err = b.err;
+    a.step = b.step;
+    a.salient = b.sal;
+    a.skip = b.skip;
+    a.disparity = disp;
+    a.depth = depth;
+    a.sigma = sigma;
+    a.cost = cost;
+    a.n_pairs = n;
+    hipLaunchKernelGGL(vgs::stereo_depth_mh_kernel, dim3(blocks_of(n * hyp * s->P, 256)), dim3(256), 0, s->stream, s->g, a, hyp);
 }
 
 int check_call(vg_stereo *s, int64_t n, const void *img1, const void *img2)
@@ -276,6 +298,37 @@ int vg_stereo_compute(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const 
         launch_cost(s, n, img1 + first * img, img2 + first * img, c);
         launch_agg(s, n, c, false);
         launch_depth(s, n, c, depth ? depth + first * P : nullptr, sigma ? sigma + first * P : nullptr, cost ? cost + first * P : nullptr);
+        VG_HIP(hipGetLastError());
+    }
+    return call.finish();
+}
+
+int vg_stereo_compute_mh(vg_stereo *s, int64_t n_pairs, const uint8_t *img1, const uint8_t *img2, int hyp_max, double *depth, double *sigma,
+                         double *cost, int32_t *disparity, int32_t *final_cost)
+{
+    if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "stereo handle is NULL");
+    if (n_pairs < 1) return fail(VG_ERR_INVALID_ARGUMENT, "the pair count must be at least 1");
+    if (!img1 || !img2) return fail(VG_ERR_INVALID_ARGUMENT, "NULL image");
+    if (hyp_max < 2 || hyp_max > vgs::kMaxHyp || hyp_max > s->prm.disp_max)
+        return fail(VG_ERR_INVALID_ARGUMENT, "hyp_max must be in [2, 8] and at most disparity_max (1: vg_stereo_compute)");
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    const int64_t chunk = std::min<int64_t>(s->chunk(hyp_max), n_pairs);
+    const int64_t HP = hyp_max * s->P, img = (int64_t)s->prm.u_max * s->prm.v_max;
+    Bufs b;
+    if (const int rc = scratch_bufs(s, chunk, b, hyp_max)) return rc;
+    for (int64_t first = 0; first < n_pairs; first += chunk) {
+        const int64_t n = std::min(chunk, n_pairs - first);
+        vgs::MhArgs mh;
+        mh.hyp_max = hyp_max;
+        mh.hypo_difference = s->prm.hypo_difference;
+        mh.disparity = disparity ? disparity + first * HP : b.disp;
+        mh.final_cost = final_cost ? final_cost + first * HP : nullptr;
+        launch_cost(s, n, img1 + first * img, img2 + first * img, b);
+        launch_agg(s, n, b, false, &mh);
+        if (depth || sigma || cost)
+            launch_depth_mh(s, n, b, hyp_max, mh.disparity, depth ? depth + first * HP : nullptr, sigma ? sigma + first * HP : nullptr,
+                            cost ? cost + first * HP : nullptr);
         VG_HIP(hipGetLastError());
     }
     return call.finish();

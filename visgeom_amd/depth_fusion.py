@@ -114,6 +114,54 @@ class DepthFusion(Handle):
         self.counts = counts
         return maps
 
+    def _planes(self, maps, k, hypotheses, what):
+        """k float64 CUDA tensors [hypotheses, y_max, x_max] or [n, hypotheses, y_max, x_max], contiguous: (list, n, single)"""
+        import torch
+
+        hyp = int(hypotheses)
+        if len(maps) < k:
+            raise ValueError("%s must be (%s)" % (what, ", ".join(("depth", "sigma", "cost")[:k])))
+        out = list(maps)[:k]
+        tail = (hyp, self.y_max, self.x_max)
+        for t in out:
+            if not _is_cuda(t, torch.float64) or t.dim() not in (3, 4) or tuple(t.shape[-3:]) != tail or t.shape != out[0].shape:
+                raise ValueError("%s must be float64 CUDA tensors [n, %d, %d, %d] or [%d, %d, %d]" % ((what,) + tail + tail))
+            if not t.is_contiguous():
+                raise ValueError("%s must be contiguous" % what)
+        single = out[0].dim() == 3
+        return out, 1 if single else out[0].shape[0], single
+
+    def regularize(self, maps, hypotheses):
+        """DepthMap::regularize of (depth, sigma, cost) with `hypotheses` planes each, in place: every pixel's filled planes move
+        down over its empty ones; returns maps"""
+        m, n, _ = self._planes(maps, 3, hypotheses, "maps")
+        self._enter()
+        capi.check(capi.load().vg_depth_regularize(self._h, n, int(hypotheses), *[t.data_ptr() for t in m]))
+        self._leave(*m)
+        return maps
+
+    def pack_mh(self, maps, hypotheses):
+        """DepthMap::reconstruct(ALL_HYPOTHESES | SIGMA_VALUE) of one map (depth, sigma) [hypotheses, y_max, x_max]: (indices int32
+        [m], hyp int32 [m], cloud float64 [m, 3], sigma float64 [m]) -- per pixel with a depth in plane 0, in raster order, one
+        entry per filled plane"""
+        import torch
+
+        m, _, single = self._planes(maps, 2, hypotheses, "maps")
+        if not single:
+            raise ValueError("maps must be one map [hypotheses, y_max, x_max]")
+        L, k, cnt = capi.load(), int(hypotheses), ctypes.c_int64()
+        self._enter()
+        capi.check(L.vg_depth_pack_mh(self._h, k, m[0].data_ptr(), m[1].data_ptr(), ctypes.byref(cnt), None, None, None, None))
+        idx, hyp = (torch.empty(cnt.value, dtype=torch.int32, device=self.device) for _ in range(2))
+        cloud = torch.empty((cnt.value, 3), dtype=torch.float64, device=self.device)
+        sig = torch.empty(cnt.value, dtype=torch.float64, device=self.device)
+        if cnt.value:
+            self._enter()
+            capi.check(L.vg_depth_pack_mh(self._h, k, m[0].data_ptr(), m[1].data_ptr(), ctypes.byref(cnt), idx.data_ptr(), hyp.data_ptr(),
+                                          cloud.data_ptr(), sig.data_ptr()))
+        self._leave(idx, hyp, cloud, sig, *m)
+        return idx, hyp, cloud, sig
+
     def filter_noise(self, maps, out=None):
         """DepthMap::filterNoise of (depth, sigma, ...): the filtered (depth, sigma) as new tensors, or written into out =
         (depth, sigma), which may be the inputs themselves.  A cost map given with maps is passed through untouched."""

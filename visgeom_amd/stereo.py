@@ -121,6 +121,24 @@ class Stereo(Handle):
         self._leave(*out, a, b)
         return tuple(t[0] for t in out) if single else out
 
+    def compute_mh(self, img1, img2, hypotheses):
+        """computeStereo with `hypotheses` (2 ... 8) depth hypotheses per pixel (reconstructDisparityMH): (depth, sigma, cost)
+        float64, disparity and final_cost int32, each [n, hypotheses, y_max, x_max] (no n for one [vMax, uMax] pair); plane h
+        holds the h-th cheapest local minimum of the aggregated cost, -1 / INT32_MAX where there is none"""
+        import torch
+
+        a, b, single = self._images(img1, img2)
+        n, k = a.shape[0], int(hypotheses)
+        shape = (n, k, self.y_max, self.x_max)
+        depth, sigma, cost = (torch.empty(shape, dtype=torch.float64, device=self.device) for _ in range(3))
+        disp, final = (torch.empty(shape, dtype=torch.int32, device=self.device) for _ in range(2))
+        self._enter()
+        capi.check(capi.load().vg_stereo_compute_mh(self._h, n, a.data_ptr(), b.data_ptr(), k, depth.data_ptr(), sigma.data_ptr(),
+                                                    cost.data_ptr(), disp.data_ptr(), final.data_ptr()))
+        out = (depth, sigma, cost, disp, final)
+        self._leave(*out, a, b)
+        return tuple(t[0] for t in out) if single else out
+
     def geometry(self):
         """the per-pixel geometry, int32 [y_max, x_max, 8] (status, pinf u, v, curve index, flags 1, flags 2, 0, 0)"""
         import torch
