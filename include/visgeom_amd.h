@@ -1384,6 +1384,68 @@ int vg_dense_ba_back_substitute(vg_dense_ba *h, double mu, const double *dp, dou
  * report HOST [4] (may be NULL): iterations, initial cost, final cost, vg_termination.  An empty pack is refused. */
 int vg_dense_ba_solve(vg_dense_ba *h, const double *xi_start, double *xi_out, double *depth_out, double *sigma_out, double *report);
 
+/* =====================================================================================
+ * 19. Fisheye line detection: the reference's hough_test (test/reconstruction/hough_test.cpp) -- straight 3D lines in one
+ *     unrectified EUCM image.  Every pixel with a strong Sobel gradient defines the plane through the projection centre that
+ *     contains its edge; the plane's normal, projected through a second, small EUCM "accumulator camera", votes in an int32
+ *     accumulator; the accumulator is blurred (float, 5 x 5 Gaussian) and its strict local maxima are the lines; a line's
+ *     image is the conic vg_hough_polynomial gives, walked by the curve rasteriser between its end points.  FP64 in the
+ *     reference's expression order, integer votes: the same bytes on every run.  Images are DEVICE u8.  Every call is
+ *     synchronous on the handle's stream and checks its arguments before HIP is touched.  Deviations: DESIGN.md section 9,
+ *     "Line detection".
+ * ===================================================================================== */
+#define VG_HOUGH_MAX_SIDE 16384
+#define VG_HOUGH_MAX_ACC_SIDE 4096
+#define VG_HOUGH_MAX_SEARCH 8
+#define VG_HOUGH_MIN_BLUR 3
+#define VG_HOUGH_MAX_BLUR 15
+#define VG_HOUGH_COUNTS 6       /* selected pixels, not reconstructed, first votes cast, antipode votes cast, projections
+                                   failed, votes outside the accumulator */
+#define VG_HOUGH_LINE 16        /* centroid u, v; blurred value; unit normal [3]; poly6; pt1 [2]; pt2 [2] */
+#define VG_HOUGH_MAX_LINES 65536
+#define VG_HOUGH_MAX_TRACE 1500  /* LENGTH of the reference's trace */
+#define VG_HOUGH_OK 0
+#define VG_HOUGH_NO_END_POINTS 1
+typedef struct vg_hough_params {
+    int margin;               /* MARGIN 5: pixels this close to the border are not visited; at least 1 */
+    double grad_thresh;       /* GRAD_THRESH 0.001 on gx^2 + gy^2 of the Sobel / 2048 gradient */
+    int search_size;          /* SEARCH_SIZE 2: a maximum beats its (2 s + 1)^2 - 1 neighbours; in [1, 8] */
+    double acc_thresh;        /* ACC_THRESH 7 */
+    double acc_delta_thresh;  /* ACC_DELTA_THRESH 0.05 */
+    double horizon_ratio;     /* 3e-3: C^2 / (A^2 + B^2) below it votes at the antipode as well */
+    int blur_size;            /* 5, odd, in [3, 15] */
+    double blur_sigma;        /* 0.9 */
+} vg_hough_params;
+typedef struct vg_hough vg_hough;
+void vg_hough_params_default(vg_hough_params *p);
+/* A handle for width x height images of the camera eucm6 (HOST 6 intrinsics) voting through the accumulator camera acc_eucm6:
+ * the accumulator is int32 [acc_h][acc_w], acc_w = (int)(2 u0_acc), acc_h = (int)(2 v0_acc).  Image sides in
+ * [2 margin + 3, 16384]; accumulator sides in [2 search_size + 3, 4096] and at least (blur_size + 1) / 2.  params NULL: the
+ * defaults. */
+int vg_hough_create(vg_hough **out, int device, void *hip_stream, int width, int height, const double *eucm6, const double *acc_eucm6,
+                    const vg_hough_params *params);
+void vg_hough_destroy(vg_hough *h);
+int vg_hough_size(const vg_hough *h, int *acc_w, int *acc_h);
+/* Stage entry: the votes of n images (DEVICE u8 [n][height][width]) into acc (DEVICE int32 [n][acc_h][acc_w], cleared first).
+ * counts HOST int64 [n][VG_HOUGH_COUNTS] or NULL.  A pixel that does not reconstruct, a projection that fails and a vote
+ * outside the accumulator cast nothing and are counted. */
+int vg_hough_vote(vg_hough *h, int64_t n_images, const uint8_t *images, int32_t *acc, int64_t *counts);
+/* Votes, blur, maxima and the lines of n images.  lines HOST [n][max_lines][VG_HOUGH_LINE], status HOST int32 [n][max_lines]
+ * (VG_HOUGH_OK or VG_HOUGH_NO_END_POINTS: both end points are NaN then), count HOST int32 [n]: the lines found, which may
+ * exceed max_lines -- the first max_lines in raster order of the accumulator are returned.  poly6 is vg_hough_polynomial of
+ * the reconstructed, unnormalised normal, as in the reference.  acc_blur DEVICE float [n][acc_h][acc_w] or NULL. */
+int vg_hough_detect(vg_hough *h, int64_t n_images, const uint8_t *images, int max_lines, double *lines, int32_t *status, int32_t *count,
+                    float *acc_blur);
+/* Host only: computePolynomial (hough_test.cpp:31-91) of the plane A x + B y + C z = 0 in the camera eucm6. */
+int vg_hough_polynomial(const double *eucm6, const double *plane3, double *poly6);
+/* Host only: findTerminalPoints (hough_test.cpp:100-283): pt4 = pt1, pt2; *status VG_HOUGH_OK, or VG_HOUGH_NO_END_POINTS and
+ * pt4 all NaN when a point outside the image cannot be brought to its border. */
+int vg_hough_end_points(int width, int height, const double *eucm6, const double *plane3, const double *poly6, double *pt4, int *status);
+/* Host only: the walk of hough_test.cpp:499-536 from round(pt1) towards round(pt2): the pixels visited until the walk is within
+ * 2 px (L1) of pt2, at most max_steps (in [0, VG_HOUGH_MAX_TRACE]) of them; uv int32 [max_steps][2], *n the number written.  End points must
+ * be within +-2^24. */
+int vg_hough_trace(const double *poly6, const double *pt4, int max_steps, int32_t *uv, int *n);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",
  * "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop", "solver_no_fold_frames",

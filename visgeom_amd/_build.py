@@ -33,14 +33,14 @@ def sources():
     vg_depth_tu: depth map warp / merge / noise filter; vg_photometric_tu: photometric pose estimation;
     vg_sparse_odom_tu: sparse visual odometry; vg_render_tu: synthetic scene renderer; vg_mono_odom_tu: monocular visual
     odometry; vg_mapping_tu: photometric mapping; vg_trajectory_tu: calibration trajectory planning; vg_dense_ba_tu: photometric
-    bundle adjustment)"""
+    bundle adjustment; vg_hough_tu: fisheye line detection)"""
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
 
 
 # the host programs build_cli() makes: name -> source in csrc/
 CLI_SOURCES = {"calib": "calib_main.cpp", "rectify": "rectify_main.cpp", "stereo": "stereo_main.cpp",
                "motion_stereo": "motion_stereo_main.cpp", "render": "render_main.cpp", "mono_odom": "mono_odom_main.cpp",
-               "mapping": "mapping_main.cpp", "trajectory": "trajectory_main.cpp"}
+               "mapping": "mapping_main.cpp", "trajectory": "trajectory_main.cpp", "hough": "hough_main.cpp"}
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 STAMP = os.path.join(LIB_DIR, "libvisgeom_amd.sources.sha256")
 _INCLUDE = None
@@ -197,12 +197,13 @@ RENDER_CLI = os.path.join(BIN_DIR, "render")
 MONO_ODOM_CLI = os.path.join(BIN_DIR, "mono_odom")
 MAPPING_CLI = os.path.join(BIN_DIR, "mapping")
 TRAJECTORY_CLI = os.path.join(BIN_DIR, "trajectory")
+HOUGH_CLI = os.path.join(BIN_DIR, "hough")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 
 def build_cli(verbose=False):
     """the reference's programs, host-only C++ on the C ABI: `calib file1.json [file2.json ...]`, `rectify file.json` and
-    `stereo file.json`, `motion_stereo sequence.json`, `render world.json`, `mono_odom sequence.json`, `mapping sequence.json` and `trajectory plan.json` (all but the
+    `stereo file.json`, `motion_stereo sequence.json`, `render world.json`, `mono_odom sequence.json`, `mapping sequence.json`, `trajectory plan.json` and `hough lines.json` (all but the
     first are built against the HIP runtime)"""
     os.makedirs(BIN_DIR, exist_ok=True)
     common = ["-L" + LIB_DIR, "-lvisgeom_amd", "-Wl,-rpath," + LIB_DIR, "-Wl,-rpath," + os.path.join(ROCM, "lib")]
@@ -220,7 +221,9 @@ def build_cli(verbose=False):
             ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROCM, "include"),
              os.path.join(CSRC, CLI_SOURCES["mapping"]), "-o", MAPPING_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"],
             ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROCM, "include"),
-             os.path.join(CSRC, CLI_SOURCES["trajectory"]), "-o", TRAJECTORY_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"]]
+             os.path.join(CSRC, CLI_SOURCES["trajectory"]), "-o", TRAJECTORY_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"],
+            ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROCM, "include"),
+             os.path.join(CSRC, CLI_SOURCES["hough"]), "-o", HOUGH_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"]]
     for cmd in cmds:
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

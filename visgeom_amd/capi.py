@@ -320,6 +320,15 @@ SIGNATURES = {
     "vg_dense_ba_reduce": (ctypes.c_int, [_vp, ctypes.c_double, _dp, _dp]),
     "vg_dense_ba_back_substitute": (ctypes.c_int, [_vp, ctypes.c_double, _dp, _vp, _dp]),
     "vg_dense_ba_solve": (ctypes.c_int, [_vp, _dp, _dp, _vp, _vp, _dp]),
+    "vg_hough_params_default": (None, [_vp]),
+    "vg_hough_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _vp]),
+    "vg_hough_destroy": (None, [_vp]),
+    "vg_hough_size": (ctypes.c_int, [_vp, _ip, _ip]),
+    "vg_hough_vote": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _i64p]),
+    "vg_hough_detect": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int, _dp, _i32p, _i32p, _vp]),
+    "vg_hough_polynomial": (ctypes.c_int, [_dp, _dp, _dp]),
+    "vg_hough_end_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _ip]),
+    "vg_hough_trace": (ctypes.c_int, [_dp, _dp, ctypes.c_int, _i32p, _ip]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),
@@ -352,6 +361,13 @@ class DenseBaOptions(ctypes.Structure):
     """struct vg_dense_ba_options; a zero field means the default (DENSE_BA_DEFAULTS), DENSE_BA_NONE switches off"""
     _fields_ = [("sigma_grey", ctypes.c_double), ("prior_weight", ctypes.c_double), ("grad_thresh", ctypes.c_double),
                 ("max_iterations", ctypes.c_int), ("function_tolerance", ctypes.c_double)]
+
+
+class HoughParams(ctypes.Structure):
+    """struct vg_hough_params"""
+    _fields_ = [("margin", ctypes.c_int), ("grad_thresh", ctypes.c_double), ("search_size", ctypes.c_int), ("acc_thresh", ctypes.c_double),
+                ("acc_delta_thresh", ctypes.c_double), ("horizon_ratio", ctypes.c_double), ("blur_size", ctypes.c_int),
+                ("blur_sigma", ctypes.c_double)]
 
 
 class SparseOdomParams(ctypes.Structure):
@@ -410,6 +426,8 @@ MAPPING_WARNING_NONE, MAPPING_WARNING_SCALE, MAPPING_WARNING_ROTATION = range(3)
 MAPPING_REPORT = 32
 MI_NUM_BINS, MI_VALUE_MAX, MI_ODOMETRY_DAMPING = 8, 255., 0.0002
 MI_DEFAULTS = {"function_tolerance": 1e-2, "gradient_tolerance": 1e-3, "max_iterations": 50}
+HOUGH_MAX_SIDE, HOUGH_MAX_ACC_SIDE, HOUGH_MAX_SEARCH, HOUGH_MIN_BLUR, HOUGH_MAX_BLUR = 16384, 4096, 8, 3, 15
+HOUGH_COUNTS, HOUGH_LINE, HOUGH_MAX_LINES, HOUGH_MAX_TRACE, HOUGH_OK, HOUGH_NO_END_POINTS = 6, 16, 65536, 1500, 0, 1
 DENSE_BA_MAX_FRAMES, DENSE_BA_TAIL, DENSE_BA_NONE = 8, 5, -1.
 DENSE_BA_DEFAULTS = {"sigma_grey": 5., "prior_weight": 1., "grad_thresh": 250., "max_iterations": 150, "function_tolerance": 1e-6}
 
