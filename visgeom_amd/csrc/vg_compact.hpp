@@ -1,13 +1,49 @@
-// vg_compact.hpp -- the scan of an ordered compaction, shared by the packs that keep the reference's raster order (the
-// photometric data pack, the bundle adjustment's pack, the multi-hypothesis depth pack, the line detector's maxima).  Each of
-// them counts the survivors of every block of LANES items in a first pass, scans the block counts here, and in a second pass
-// places every survivor at its block's offset plus the survivors of the lower waves and lanes of its block.  A template, so that
-// every translation unit that launches it may hold its instantiation.
+// vg_compact.hpp -- the ordered compaction shared by the packs that keep the reference's raster order (the photometric data
+// pack, the bundle adjustment's pack, the multi-hypothesis depth pack, the line detector's maxima).  Each of them counts the
+// survivors of every block of LANES items in a first pass (block_place<false>), scans the block counts (scan_block_counts), and
+// in a second pass places every survivor at its block's offset plus the survivors of the lower waves and lanes of its block
+// (block_place<true>).  Templates, so that every translation unit that launches them may hold its instantiation.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 namespace vgc {
+
+// the set bits of a wave ballot below the calling lane
+__device__ __forceinline__ unsigned lanes_below(unsigned long long ball) { return (unsigned)__popcll(ball & ((1ull << (threadIdx.x & 63)) - 1ull)); }
+
+// The block step of both passes.  below: the entries of the wave's lower lanes, total: the entries of the whole wave (a lane may
+// hold several); slot: the block's index into counts / offsets.  Pass 1 (WRITE = false) stores the block's count and returns 0;
+// pass 2 returns the place of the lane's first entry: the block's scanned offset, the lower waves, the lower lanes.  It holds a
+// barrier: every thread of the workgroup calls it, and leaves afterwards.
+template <bool WRITE, int LANES>
+__device__ __forceinline__ unsigned block_place(unsigned below, unsigned total, int64_t slot, unsigned *counts, const unsigned *offsets)
+{
+    __shared__ unsigned wave_count[LANES / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_count[wave] = total;
+    __syncthreads();
+    if (!WRITE) {
+        if (threadIdx.x == 0) {
+            unsigned n = 0;
+#pragma unroll
+            for (int k = 0; k < LANES / 64; k++) n += wave_count[k];
+            counts[slot] = n;
+        }
+        return 0;
+    }
+    unsigned pos = offsets[slot] + below;
+    for (int k = 0; k < wave; k++) pos += wave_count[k];
+    return pos;
+}
+
+// one entry per lane at most
+template <bool WRITE, int LANES>
+__device__ __forceinline__ unsigned block_place(bool keep, int64_t slot, unsigned *counts, const unsigned *offsets)
+{
+    const unsigned long long ball = __ballot(keep);
+    return block_place<WRITE, LANES>(lanes_below(ball), (unsigned)__popcll(ball), slot, counts, offsets);
+}
 
 // exclusive scan of nb block counts by one workgroup: a contiguous run per thread, the LANES run sums in order
 template <int LANES>

@@ -25,6 +25,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "vg_image_device.hpp"
+
 namespace vg {
 
 constexpr int kCornerTileW = 64, kCornerTileH = 16;     // output tile of the stencil kernels: 256 lanes x 4 rows
@@ -50,12 +52,7 @@ struct BlurWeights {
     int r2;
 };
 
-__device__ __forceinline__ int reflect101(int x, int n)   // BORDER_REFLECT_101 for |overhang| < n, then clamped
-{
-    if (x < 0) x = -x;
-    if (x >= n) x = 2 * n - 2 - x;
-    return x < 0 ? 0 : (x >= n ? n - 1 : x);
-}
+using vgs::reflect101;   // BORDER_REFLECT_101 for |overhang| < n, then clamped
 
 __device__ __forceinline__ float round_u8(float v) { return fminf(fmaxf(rintf(v), 0.f), 255.f); }
 

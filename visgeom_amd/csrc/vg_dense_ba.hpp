@@ -14,39 +14,19 @@
 #pragma once
 
 #include "vg_bicubic.hpp"
-#include "vg_camera.hpp"
 #include "vg_compact.hpp"
-#include "vg_stereo_device.hpp"
+#include "vg_photometric_row.hpp"
 
 namespace vgba {
 
 using namespace vgs;
 
 constexpr int kLanes = 256, kWaves = kLanes / 64;
-constexpr int kMaxFrames = 8;
-constexpr int kSums = 28;          // per frame: J^T J upper triangle row-major (21) | J^T r (6) | 1/2 sum r^2
+constexpr int kMaxFrames = 8;      // kSums (vg_photometric_row.hpp) sums per frame
 constexpr int kTail = 5;           // sum D dx^2 | g . dx | |dx|^2 | |x|^2 | max |g| of the depth block
 constexpr int kSchurBlocks = 128;  // at most this many workgroups reduce; beyond 128 x 256 points a wave's run grows
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-struct Grid {   // ScaleParameters of the depth map
-    int scale, u0, v0, x_max, y_max;
-};
-
-VGS_HD int reflect101(int i, int n)   // BORDER_REFLECT_101; a one-pixel axis has only itself
-{
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * n - 2 - i;
-    return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
-
-// F images u8 -> float
-__global__ __launch_bounds__(kLanes) void ba_convert_kernel(const uint8_t *src, float *dst, int64_t P)
-{
-    const int64_t item = blockIdx.y, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
-    if (pix < P) dst[item * P + pix] = (float)src[item * P + pix];
-}
 
 // ---- the pack --------------------------------------------------------------------------------------------------------
 
@@ -64,17 +44,6 @@ struct SelectArgs {
     double *val, *dir, *d0, *s0;
 };
 
-// the Sobel / 8 pair of photo_sobel_kernel at one pixel of level 0: float arithmetic, the same association
-VGS_HD void sobel_at(const float *s, int w, int h, int u, int v, float &gu, float &gv)
-{
-    const int um = reflect101(u - 1, w), up = reflect101(u + 1, w), vm = reflect101(v - 1, h), vp = reflect101(v + 1, h);
-    const float *r0 = s + (int64_t)vm * w, *r1 = s + (int64_t)v * w, *r2 = s + (int64_t)vp * w;
-    const float du0 = r0[up] - r0[um], du1 = r1[up] - r1[um], du2 = r2[up] - r2[um];
-    const float dv0 = r2[um] - r0[um], dv1 = r2[u] - r0[u], dv2 = r2[up] - r0[up];
-    gu = ((du0 + 2.f * du1) + du2) * 0.125f;
-    gv = ((dv0 + 2.f * dv1) + dv2) * 0.125f;
-}
-
 VGS_HD bool select_cell(const SelectArgs &a, int64_t cell, double &value, double *dir, double &d, double &s)
 {
     const int x = (int)(cell % a.g.x_max), y = (int)(cell / a.g.x_max);
@@ -86,7 +55,7 @@ VGS_HD bool select_cell(const SelectArgs &a, int64_t cell, double &value, double
     double Xr[3];
     if (!eucm_reconstruct(a.cam, (double)u, (double)v, Xr)) return false;
     float fgu, fgv;
-    sobel_at(a.img, a.w, a.h, u, v, fgu, fgv);
+    sobel8_at(a.img, a.w, a.h, u, v, fgu, fgv);   // the gradient of photo_sobel_kernel, at the cell's pixel only
     const double gu = fgu, gv = fgv;
     if (gu * gu + gv * gv < a.grad_thresh) return false;
     if (a.need_sigma && !(isfinite(s) && s > 0.)) return false;
@@ -97,25 +66,15 @@ VGS_HD bool select_cell(const SelectArgs &a, int64_t cell, double &value, double
 }
 
 // pass 1 (WRITE = false): the survivors of every block of 256 cells; pass 2: their raster-ordered places from the scanned
-// block counts (vg_compact.hpp)
+// block counts (vgc::block_place)
 template <bool WRITE>
 __global__ __launch_bounds__(kLanes) void ba_select_kernel(SelectArgs a)
 {
-    __shared__ unsigned wave_count[kWaves];
     const int64_t cell = (int64_t)blockIdx.x * kLanes + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double value = 0., dir[3] = {0., 0., 0.}, d = 0., s = 0.;
     const bool keep = cell < (int64_t)a.g.x_max * a.g.y_max && select_cell(a, cell, value, dir, d, s);
-    const unsigned long long ball = __ballot(keep);
-    if (lane == 0) wave_count[wave] = (unsigned)__popcll(ball);
-    __syncthreads();
-    if (!WRITE) {
-        if (threadIdx.x == 0) a.block_counts[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
-        return;
-    }
-    if (!keep) return;
-    unsigned pos = a.block_offsets[blockIdx.x] + (unsigned)__popcll(ball & ((1ull << lane) - 1ull));
-    for (int k = 0; k < wave; k++) pos += wave_count[k];
+    const unsigned pos = vgc::block_place<WRITE, kLanes>(keep, blockIdx.x, a.block_counts, a.block_offsets);
+    if (!WRITE || !keep) return;
     a.idx[pos] = (int32_t)cell;
     a.val[pos] = value;
     for (int i = 0; i < 3; i++) a.dir[3 * (int64_t)pos + i] = dir[i];
@@ -162,16 +121,9 @@ VGS_HD void eval_point(const EvalArgs &a, const Frame &fr, int frame, int64_t i,
     double f, dfdr, dfdc;
     bicubic(a.imgs + (int64_t)frame * a.w * a.h, a.w, a.h, pt[1], pt[0], f, dfdr, dfdc);
     r = (f - a.val[i]) / a.sigma_grey;
-    // CameraJacobian::dfdxi (jacobian.h:98-115) with grad = (d/du, d/dv)
-    const double H[9] = {0, -X[2], X[1], X[2], 0, -X[0], -X[1], X[0], 0};
-    double B[9], dv[3], Md[3];
-    vg::mat3_mul(H, fr.L22, B);
-    for (int k = 0; k < 9; k++) B[k] = B[k] - fr.L12[k];
-    for (int j = 0; j < 3; j++) dv[j] = dfdc * e.P[j] + dfdr * e.P[3 + j];
-    for (int j = 0; j < 3; j++) {
-        row[j] = ((-dv[0]) * fr.L11[0 + j] + (-dv[1]) * fr.L11[3 + j] + (-dv[2]) * fr.L11[6 + j]) / a.sigma_grey;
-        row[3 + j] = (dv[0] * B[0 + j] + dv[1] * B[3 + j] + dv[2] * B[6 + j]) / a.sigma_grey;
-    }
+    double dv[3], Md[3];
+    dfdxi_row(X, e.P, dfdc, dfdr, fr.L11, fr.L12, fr.L22, dv, row);   // grad = (d/du, d/dv)
+    for (int k = 0; k < 6; k++) row[k] = row[k] / a.sigma_grey;       // on the finished sums
     mat_vec(fr.M, a.dir + 3 * i, Md);
     jd = dot3(dv, Md) / a.sigma_grey;
 }
@@ -179,8 +131,7 @@ VGS_HD void eval_point(const EvalArgs &a, const Frame &fr, int frame, int64_t i,
 // one lane per (frame, point): blockIdx.y the frame, blockIdx.x * 256 + threadIdx.x the point
 __global__ __launch_bounds__(kLanes) void ba_eval_kernel(EvalArgs a)
 {
-    __shared__ double wave_sums[kWaves][kSums];
-    const int frame = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int frame = blockIdx.y;
     const int64_t i = (int64_t)blockIdx.x * kLanes + threadIdx.x;
     double r = 0., row[6] = {0., 0., 0., 0., 0., 0.}, jd = 0.;
     if (i < a.m) {
@@ -192,25 +143,8 @@ __global__ __launch_bounds__(kLanes) void ba_eval_kernel(EvalArgs a)
         for (int k = 0; k < 6; k++) a.jp[o * 6 + k] = row[k];
     }
     double s[kSums];
-    int q = 0;
-#pragma unroll
-    for (int rr = 0; rr < 6; rr++)
-#pragma unroll
-        for (int c = rr; c < 6; c++) s[q++] = row[rr] * row[c];
-#pragma unroll
-    for (int k = 0; k < 6; k++) s[21 + k] = row[k] * r;
-    s[27] = 0.5 * (r * r);
-#pragma unroll
-    for (int k = 0; k < kSums; k++) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s[k] += __shfl_xor(s[k], off, 64);   // a fixed tree: every lane ends with the same bits
-        if (lane == 0) wave_sums[wave][k] = s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < kSums) {
-        const int k = threadIdx.x;
-        a.partials[((int64_t)frame * a.blocks + blockIdx.x) * kSums + k] = ((wave_sums[0][k] + wave_sums[1][k]) + wave_sums[2][k]) + wave_sums[3][k];
-    }
+    row_products(row, r, s);
+    block_sums<kSums, kLanes>(s, a.partials + ((int64_t)frame * a.blocks + blockIdx.x) * kSums);
 }
 
 struct PointArgs {
@@ -227,10 +161,8 @@ VGS_HD double prior_scale(double lambda, double s0) { return lambda > 0. ? lambd
 // one lane per point: the diagonal entry and the gradient of its depth over the frames in order, and 1/2 p^2
 __global__ __launch_bounds__(kLanes) void ba_point_kernel(PointArgs a)
 {
-    __shared__ double wave_sums[kWaves];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * kLanes + threadIdx.x;
-    double c = 0.;
+    double c[1] = {0.};
     if (i < a.m) {
         double aa = 0., g = 0.;
         for (int f = 0; f < a.F; f++) {
@@ -242,13 +174,9 @@ __global__ __launch_bounds__(kLanes) void ba_point_kernel(PointArgs a)
         const double p = ps * (a.depth[i] - a.d0[i]);
         a.a[i] = aa + ps * ps;
         a.gd[i] = g + ps * p;
-        c = 0.5 * (p * p);
+        c[0] = 0.5 * (p * p);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
-    if (lane == 0) wave_sums[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) a.prior_partials[blockIdx.x] = ((wave_sums[0] + wave_sums[1]) + wave_sums[2]) + wave_sums[3];
+    block_sums<1, kLanes>(c, a.prior_partials + blockIdx.x);
 }
 
 // The second pass of every sum here, by one wave: the n values p[i stride] in index order, split into 64 contiguous runs -- lane
@@ -424,8 +352,6 @@ struct BacksubArgs {
 
 __global__ __launch_bounds__(kLanes) void ba_backsub_kernel(BacksubArgs a)
 {
-    __shared__ double wave_sums[kWaves][kTail];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * kLanes + threadIdx.x;
     double s[kTail] = {0., 0., 0., 0., 0.};
     if (i < a.m) {
@@ -446,21 +372,7 @@ __global__ __launch_bounds__(kLanes) void ba_backsub_kernel(BacksubArgs a)
         s[3] = d * d;
         s[4] = fabs(g);
     }
-#pragma unroll
-    for (int k = 0; k < kTail; k++) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double o = __shfl_xor(s[k], off, 64);
-            s[k] = k == 4 ? fmax(s[k], o) : s[k] + o;
-        }
-        if (lane == 0) wave_sums[wave][k] = s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < kTail) {
-        const int k = threadIdx.x;
-        const double *w0 = wave_sums[0], *w1 = wave_sums[1], *w2 = wave_sums[2], *w3 = wave_sums[3];
-        a.partials[(int64_t)blockIdx.x * kTail + k] = k == 4 ? fmax(fmax(fmax(w0[k], w1[k]), w2[k]), w3[k]) : ((w0[k] + w1[k]) + w2[k]) + w3[k];
-    }
+    block_sums<kTail, kLanes, 4>(s, a.partials + (int64_t)blockIdx.x * kTail);   // slot 4 is the maximum
 }
 
 // workgroup k: entry k of the tail over the workgroups of ba_backsub_kernel

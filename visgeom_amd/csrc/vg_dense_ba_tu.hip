@@ -319,7 +319,7 @@ int vg_dense_ba_set_base(vg_dense_ba *s, const uint8_t *img, const double *depth
     VG_HIP(hipMemcpyAsync(s->d_depth_map, depth, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
     if (sigma) VG_HIP(hipMemcpyAsync(s->d_sigma_map, sigma, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
     else VG_HIP(hipMemsetAsync(s->d_sigma_map, 0, (size_t)n * sizeof(double), s->stream));
-    hipLaunchKernelGGL(vgba::ba_convert_kernel, dim3(blocks_of(P, vgba::kLanes), 1), dim3(vgba::kLanes), 0, s->stream, img, s->d_base.get(), P);
+    hipLaunchKernelGGL(vgs::u8_to_float_kernel<vgba::kLanes>, dim3(blocks_of(P, vgba::kLanes), 1), dim3(vgba::kLanes), 0, s->stream, img, s->d_base.get(), P, P);
     vgba::SelectArgs a;
     a.img = s->d_base;
     a.w = s->w;
@@ -360,8 +360,8 @@ int vg_dense_ba_set_frames(vg_dense_ba *s, int frames, const uint8_t *imgs)
     s->evaluated = false;
     const int64_t P = (int64_t)s->w * s->h;
     if (const int rc = s->d_imgs.grow((size_t)(frames * P), "the frames")) return rc;
-    hipLaunchKernelGGL(vgba::ba_convert_kernel, dim3(blocks_of(P, vgba::kLanes), (unsigned)frames), dim3(vgba::kLanes), 0, s->stream, imgs,
-                       s->d_imgs.get(), P);
+    hipLaunchKernelGGL(vgs::u8_to_float_kernel<vgba::kLanes>, dim3(blocks_of(P, vgba::kLanes), (unsigned)frames), dim3(vgba::kLanes), 0, s->stream, imgs,
+                       s->d_imgs.get(), P, P);
     VG_HIP(hipGetLastError());
     if (const int rc = call.finish()) return rc;
     s->F = frames;

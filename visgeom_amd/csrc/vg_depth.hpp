@@ -7,7 +7,8 @@
 // Evaluated in the order written (-ffp-contract=off), so tests/depth_ref.py agrees bit for bit.
 #pragma once
 
-#include "vg_stereo_device.hpp"
+#include "vg_compact.hpp"
+#include "vg_image_device.hpp"
 
 namespace vgd {
 
@@ -18,10 +19,6 @@ constexpr double kDefaultCost = 5.;     // DEFAULT_COST_DEPTH
 constexpr int kLanes = 256;
 constexpr unsigned long long kZEmpty = ~0ull;
 constexpr unsigned kNoWinner = ~0u;
-
-struct Grid {   // ScaleParameters
-    int scale, u0, v0, x_max, y_max;
-};
 
 // one item of a warp call, as it goes up and comes back: the pose and the counters (zero on the way up)
 struct WarpItem {
@@ -65,13 +62,6 @@ VGS_HD int warp_source(const double *cam, const Grid &g, const WarpItem &it, int
     if (xd < 0 || xd >= g.x_max || yd < 0 || yd >= g.y_max) return kOutside;
     target = (int64_t)yd * g.x_max + xd;
     return kReached;
-}
-
-// every lane of the block calls this: one atomic per wave and counter
-__device__ __forceinline__ void count_wave(unsigned long long *c, bool hit)
-{
-    const int k = __popcll(__ballot(hit));
-    if ((threadIdx.x & 63) == 0 && k) atomicAdd(c, (unsigned long long)k);
 }
 
 // (a) the z-buffer: min over the sources of a target of the bits of dist (monotone for positive doubles)
@@ -261,9 +251,7 @@ struct PackMhArgs {
 template <bool WRITE>
 __global__ __launch_bounds__(kLanes) void depth_pack_mh_kernel(PackMhArgs a)
 {
-    __shared__ unsigned wave_count[kLanes / 64];
     const int64_t P = (int64_t)a.g.x_max * a.g.y_max, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool query = pix < P && a.depth[pix] >= kMinDepth;
     double d[kMaxHyp];
     unsigned below = 0, total = 0;   // entries of the wave's lower lanes, of the whole wave
@@ -271,18 +259,11 @@ __global__ __launch_bounds__(kLanes) void depth_pack_mh_kernel(PackMhArgs a)
     for (int h = 0; h < kMaxHyp; h++) {
         d[h] = (query && h < a.hyp_max) ? a.depth[h * P + pix] : 0.;
         const unsigned long long ball = __ballot(d[h] >= kMinDepth);
-        below += (unsigned)__popcll(ball & ((1ull << lane) - 1ull));
+        below += vgc::lanes_below(ball);
         total += (unsigned)__popcll(ball);
     }
-    if (lane == 0) wave_count[wave] = total;
-    __syncthreads();
-    if (!WRITE) {
-        if (threadIdx.x == 0) a.block_counts[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
-        return;
-    }
-    if (!query) return;
-    int64_t pos = a.block_offsets[blockIdx.x] + below;
-    for (int k = 0; k < wave; k++) pos += wave_count[k];
+    int64_t pos = vgc::block_place<WRITE, kLanes>(below, total, blockIdx.x, a.block_counts, a.block_offsets);
+    if (!WRITE || !query) return;
     const int x = (int)(pix % a.g.x_max), y = (int)(pix / a.g.x_max);
     double X[3], dir[3] = {0., 0., 0.};
     const bool seen = a.cloud && eucm_reconstruct(a.cam, (double)(x * a.g.scale + a.g.u0), (double)(y * a.g.scale + a.g.v0), X);

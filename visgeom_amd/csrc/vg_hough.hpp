@@ -15,7 +15,7 @@
 #include <limits>
 
 #include "vg_compact.hpp"
-#include "vg_stereo_device.hpp"
+#include "vg_image_device.hpp"
 
 namespace vgh {
 
@@ -82,14 +82,6 @@ struct VoteArgs {
     int32_t *acc;                 // [n][acc_h][acc_w], zero on entry
     unsigned long long *counts;   // [n][kCounts], or nullptr
 };
-
-// every lane of the block calls this: one atomic per wave and counter
-__device__ __forceinline__ void count_wave(unsigned long long *c, int k)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) k += __shfl_xor(k, off);
-    if ((threadIdx.x & 63) == 0 && k) atomicAdd(c, (unsigned long long)k);
-}
 
 // the votes of one wave, bin < 0 for none.  Equal bins are added inside the wave first: the wave loops over its distinct bins and
 // the first lane of each issues one atomic with the number of its lanes (the pixels of one edge vote into a handful of bins).
@@ -164,14 +156,9 @@ __global__ __launch_bounds__(kLanes) void hough_vote_kernel(VoteArgs a)
         for (int k = 0; k < kCounts; k++) count_wave(a.counts + item * kCounts + k, cnt[k]);
 }
 
-VGS_HD int reflect101(int i, int n)   // BORDER_REFLECT_101; the handle refuses an accumulator side below the blur's radius + 1
-{
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * n - 2 - i;
-    return i;
-}
-
-// one pass over all items: along the rows (COLUMN = false, from the int32 accumulator) or along the columns (from the row pass)
+// one pass over all items: along the rows (COLUMN = false, from the int32 accumulator) or along the columns (from the row pass).
+// The handle refuses an accumulator side below the blur's radius r + 1, so the overhang r stays below the side and reflect101's
+// clamp never acts.
 template <bool COLUMN, class T>
 __global__ __launch_bounds__(kLanes) void hough_blur_kernel(const T *in, float *out, int w, int h, BlurWeights bw)
 {
@@ -233,23 +220,12 @@ VGS_HD bool maximum_at(const Geom &g, const float *acc, int u, int v, LineRec &r
 template <bool WRITE>
 __global__ __launch_bounds__(kLanes) void hough_maxima_kernel(MaximaArgs a)
 {
-    __shared__ unsigned wave_count[kLanes / 64];
     const Geom &g = a.g;
     const int64_t item = blockIdx.y, bins = (int64_t)g.acc_w * g.acc_h, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     LineRec rec;
     const bool keep = pix < bins && maximum_at(g, a.blur + item * bins, (int)(pix % g.acc_w), (int)(pix / g.acc_w), rec);
-    const unsigned long long ball = __ballot(keep);
-    if (lane == 0) wave_count[wave] = (unsigned)__popcll(ball);
-    __syncthreads();
-    const int64_t slot = item * gridDim.x + blockIdx.x;
-    if (!WRITE) {
-        if (threadIdx.x == 0) a.block_counts[slot] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
-        return;
-    }
-    if (!keep) return;
-    unsigned pos = a.block_offsets[slot] + (unsigned)__popcll(ball & ((1ull << lane) - 1ull));
-    for (int k = 0; k < wave; k++) pos += wave_count[k];
+    const unsigned pos = vgc::block_place<WRITE, kLanes>(keep, item * gridDim.x + blockIdx.x, a.block_counts, a.block_offsets);
+    if (!WRITE || !keep) return;
     if (pos < (unsigned)a.max_lines) a.recs[item * a.max_lines + pos] = rec;
 }
 

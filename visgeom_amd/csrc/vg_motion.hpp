@@ -26,6 +26,8 @@ struct Rec {   // the record of vg_motion_stereo_select, 16 x int32
 // (inputs <= 510), whatever the order.  The blurred value is rounded half to even.
 constexpr int kMaskW = 32, kMaskH = 8, kMaskR = 3;
 
+// Not vgs::reflect101 (vg_image_device.hpp): the mask's halo is fed coordinates up to a whole tile beyond the image, which may be
+// several times a small image's side, so the reflection is repeated until it lands inside where the shared form would clamp.
 VGS_HD int reflect101(int i, int n)
 {
     if (n == 1) return 0;

@@ -9,9 +9,8 @@
 #pragma once
 
 #include "vg_bicubic.hpp"
-#include "vg_camera.hpp"
 #include "vg_compact.hpp"
-#include "vg_stereo_device.hpp"
+#include "vg_photometric_row.hpp"
 
 namespace vgp {
 
@@ -19,25 +18,13 @@ using namespace vgs;
 
 constexpr int kLanes = 256, kWaves = kLanes / 64;
 constexpr int kMaxLevels = 8;            // levels 0 .. 7: the sums of a level stay exact in float
-constexpr int kSums = 28;                // J^T J upper triangle row-major (21) | J^T r (6) | 1/2 sum r^2
 constexpr double kGradThresh = 250.;     // GRAD_THRESH (photometric.h:100)
 constexpr double kDistMax = 50.;         // DIST_MAX (:102)
 constexpr double kGreyMax = 240.;        // photometric.cpp:74
 constexpr double kLossFactor = 3.;       // LOSS_FACTOR (local_cost_functions.h:78)
 constexpr double kMarginPixels = 50.;    // MARGIN_SIZE = 50 / scale (local_cost_functions.cpp:43)
 
-struct Grid {   // ScaleParameters of the depth map
-    int scale, u0, v0, x_max, y_max;
-};
-
-// ---- pyramid ---------------------------------------------------------------------------------------------------------
-
-// level 0 of n images: Mat8u::convertTo(CV_32F)
-__global__ __launch_bounds__(kLanes) void photo_convert_kernel(const uint8_t *src, float *dst, int64_t P, int64_t item_stride)
-{
-    const int64_t item = blockIdx.y, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
-    if (pix < P) dst[item * item_stride + pix] = (float)src[item * P + pix];
-}
+// ---- pyramid (level 0 of n images: u8_to_float_kernel) ----------------------------------------------------------------
 
 // BinaryScalSpace::propagate (scale_space.h:121-132) for one level of n images, as a gather: source row v goes to
 // min(round(v / 2.), h - 1) (round half away: rows 2 vs - 1 and 2 vs, row 0 alone, the last row takes the rest), source column
@@ -57,26 +44,15 @@ __global__ __launch_bounds__(kLanes) void photo_down_kernel(float *pyr, int64_t 
     pyr[blockIdx.y * item_stride + off + pix] = acc * 0.25f;
 }
 
-VGS_HD int reflect101(int i, int n)   // BORDER_REFLECT_101; a one-pixel axis has only itself
-{
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * n - 2 - i;
-    return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
-
-// Sobel(img, CV_32F, 1, 0, 3, 1./8) and (0, 1): smoothing [1 2 1] across, difference [-1 0 1] along, in float
+// the Sobel / 8 pair (sobel8_at) of every pixel of one level of n images
 __global__ __launch_bounds__(kLanes) void photo_sobel_kernel(const float *img, float *gu, float *gv, int64_t item_stride, int w, int h)
 {
     const int64_t pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
     if (pix >= (int64_t)w * h) return;
-    const int u = (int)(pix % w), v = (int)(pix / w);
-    const int um = reflect101(u - 1, w), up = reflect101(u + 1, w), vm = reflect101(v - 1, h), vp = reflect101(v + 1, h);
-    const float *s = img + blockIdx.y * item_stride;
-    const float *r0 = s + (int64_t)vm * w, *r1 = s + (int64_t)v * w, *r2 = s + (int64_t)vp * w;
-    const float du0 = r0[up] - r0[um], du1 = r1[up] - r1[um], du2 = r2[up] - r2[um];
-    const float dv0 = r2[um] - r0[um], dv1 = r2[u] - r0[u], dv2 = r2[up] - r0[up];
-    gu[blockIdx.y * item_stride + pix] = ((du0 + 2.f * du1) + du2) * 0.125f;
-    gv[blockIdx.y * item_stride + pix] = ((dv0 + 2.f * dv1) + dv2) * 0.125f;
+    float fu, fv;
+    sobel8_at(img + blockIdx.y * item_stride, w, h, (int)(pix % w), (int)(pix / w), fu, fv);
+    gu[blockIdx.y * item_stride + pix] = fu;
+    gv[blockIdx.y * item_stride + pix] = fv;
 }
 
 // ---- the data pack ---------------------------------------------------------------------------------------------------
@@ -118,25 +94,15 @@ VGS_HD bool select_point(const SelectArgs &a, int64_t pix, double &value, double
 }
 
 // pass 1 (WRITE = false): the survivors of every block of 256 pixels; pass 2: their raster-ordered places from the scanned
-// block counts (vg_compact.hpp), the wave ballots and the lanes below
+// block counts (vgc::block_place)
 template <bool WRITE>
 __global__ __launch_bounds__(kLanes) void photo_select_kernel(SelectArgs a)
 {
-    __shared__ unsigned wave_count[kWaves];
     const int64_t pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double value = 0., X[3] = {0., 0., 0.};
     const bool keep = pix < (int64_t)a.w * a.h && select_point(a, pix, value, X);
-    const unsigned long long ball = __ballot(keep);
-    if (lane == 0) wave_count[wave] = (unsigned)__popcll(ball);
-    __syncthreads();
-    if (!WRITE) {
-        if (threadIdx.x == 0) a.block_counts[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
-        return;
-    }
-    if (!keep) return;
-    unsigned pos = a.block_offsets[blockIdx.x] + (unsigned)__popcll(ball & ((1ull << lane) - 1ull));
-    for (int k = 0; k < wave; k++) pos += wave_count[k];
+    const unsigned pos = vgc::block_place<WRITE, kLanes>(keep, blockIdx.x, a.block_counts, a.block_offsets);
+    if (!WRITE || !keep) return;
     a.idx[pos] = (int32_t)pix;
     a.val[pos] = value;
     for (int i = 0; i < 3; i++) a.cloud[3 * (int64_t)pos + i] = X[i];
@@ -201,23 +167,15 @@ VGS_HD void eval_point(const EvalArgs &a, const PoseFrame &fr, int64_t i, double
     const double g0 = dfdc * a.inv_scale, g1 = dfdr * a.inv_scale;   // grad = (d/du, d/dv), normalised by the scale
     double drho;
     loss(f - a.val[i], r, drho);
-    // CameraJacobian::dfdxi (jacobian.h:98-115), times drhoderr
-    const double H[9] = {0, -X[2], X[1], X[2], 0, -X[0], -X[1], X[0], 0};
-    double B[9], d[3];
-    vg::mat3_mul(H, fr.L22, B);
-    for (int k = 0; k < 9; k++) B[k] = B[k] - fr.L12[k];
-    for (int j = 0; j < 3; j++) d[j] = g0 * e.P[j] + g1 * e.P[3 + j];
-    for (int j = 0; j < 3; j++) {
-        row[j] = ((-d[0]) * fr.L11[0 + j] + (-d[1]) * fr.L11[3 + j] + (-d[2]) * fr.L11[6 + j]) * drho;
-        row[3 + j] = (d[0] * B[0 + j] + d[1] * B[3 + j] + d[2] * B[6 + j]) * drho;
-    }
+    double d[3];
+    dfdxi_row(X, e.P, g0, g1, fr.L11, fr.L12, fr.L22, d, row);
+    for (int k = 0; k < 6; k++) row[k] = row[k] * drho;   // times drhoderr, on the finished sums
 }
 
 // one lane per (pose, point): blockIdx.y the pose, blockIdx.x * 256 + threadIdx.x the point
 __global__ __launch_bounds__(kLanes) void photo_eval_kernel(EvalArgs a)
 {
-    __shared__ double wave_sums[kWaves][kSums];
-    const int pose = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pose = blockIdx.y;
     const PoseFrame &fr = a.frames[pose];
     if (!fr.active) return;   // uniform over the workgroup: a converged pose of compute_pose
     const int64_t i = (int64_t)blockIdx.x * kLanes + threadIdx.x;
@@ -231,25 +189,8 @@ __global__ __launch_bounds__(kLanes) void photo_eval_kernel(EvalArgs a)
     }
     if (!a.partials) return;
     double s[kSums];
-    int q = 0;
-#pragma unroll
-    for (int rr = 0; rr < 6; rr++)
-#pragma unroll
-        for (int c = rr; c < 6; c++) s[q++] = row[rr] * row[c];
-#pragma unroll
-    for (int k = 0; k < 6; k++) s[21 + k] = row[k] * r;
-    s[27] = 0.5 * (r * r);
-#pragma unroll
-    for (int k = 0; k < kSums; k++) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s[k] += __shfl_xor(s[k], off, 64);   // a fixed tree: every lane ends with the same bits
-        if (lane == 0) wave_sums[wave][k] = s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < kSums) {
-        const int k = threadIdx.x;
-        a.partials[((int64_t)pose * a.blocks + blockIdx.x) * kSums + k] = ((wave_sums[0][k] + wave_sums[1][k]) + wave_sums[2][k]) + wave_sums[3][k];
-    }
+    row_products(row, r, s);
+    block_sums<kSums, kLanes>(s, a.partials + ((int64_t)pose * a.blocks + blockIdx.x) * kSums);
 }
 
 // the second pass: the partials of a pose in index order, one lane per sum

@@ -153,15 +153,8 @@ VGS_HD void mi_point(const MiArgs &a, const PoseFrame &fr, int64_t i, double &f,
     bicubic(a.targets + fr.target * a.target_stride + a.level_off, a.w, a.h, pt[1] * a.inv_scale, pt[0] * a.inv_scale, f, dfdr, dfdc);
     if (!ROW) return;
     const double g0 = dfdc * a.inv_scale, g1 = dfdr * a.inv_scale;   // grad = (d/du, d/dv), normalised by the scale
-    const double H[9] = {0, -X[2], X[1], X[2], 0, -X[0], -X[1], X[0], 0};   // CameraJacobian::dfdxi (jacobian.h:98-115)
-    double B[9], d[3];
-    vg::mat3_mul(H, fr.L22, B);
-    for (int k = 0; k < 9; k++) B[k] = B[k] - fr.L12[k];
-    for (int j = 0; j < 3; j++) d[j] = g0 * e.P[j] + g1 * e.P[3 + j];
-    for (int j = 0; j < 3; j++) {
-        row[j] = (-d[0]) * fr.L11[0 + j] + (-d[1]) * fr.L11[3 + j] + (-d[2]) * fr.L11[6 + j];
-        row[3 + j] = d[0] * B[0 + j] + d[1] * B[3 + j] + d[2] * B[6 + j];
-    }
+    double d[3];
+    dfdxi_row(X, e.P, g0, g1, fr.L11, fr.L12, fr.L22, d, row);
 }
 
 // launch 1, one lane per (pose, point): valVec2 and computeHist2d.  Lane b of a wave owns bin b = idx2 * 8 + idx1 and the wave
@@ -227,15 +220,14 @@ __global__ __launch_bounds__(64) void mi_finish_kernel(MiArgs a)
     }
 }
 
-// launch 3, one lane per (pose, point): dMIdf * dfdxi of the point, the six sums by the xor butterfly and ordered
-// per-workgroup partials of photo_eval_kernel.  The point is projected and sampled again.
+// launch 3, one lane per (pose, point): dMIdf * dfdxi of the point, the six sums by the ordered reduction of
+// photo_eval_kernel (vgs::block_sums).  The point is projected and sampled again.
 __global__ __launch_bounds__(kLanes) void mi_grad_kernel(MiArgs a)
 {
     __shared__ double logv[kMiCells];
-    __shared__ double wave_sums[kWaves][6];
-    const int pose = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pose = blockIdx.y;
     const PoseFrame &fr = a.frames[pose];
-    if (!fr.active) return;
+    if (!fr.active) return;   // uniform over the workgroup, in front of both barriers
     if (threadIdx.x < kMiCells) logv[threadIdx.x] = a.logv[(int64_t)pose * kMiCells + threadIdx.x];
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * kLanes + threadIdx.x;
@@ -258,17 +250,7 @@ __global__ __launch_bounds__(kLanes) void mi_grad_kernel(MiArgs a)
 #pragma unroll
         for (int k = 0; k < 6; k++) s[k] = dMIdf * row[k];
     }
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s[k] += __shfl_xor(s[k], off, 64);
-        if (lane == 0) wave_sums[wave][k] = s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int k = threadIdx.x;
-        a.grad_partials[((int64_t)pose * a.blocks + blockIdx.x) * 6 + k] = ((wave_sums[0][k] + wave_sums[1][k]) + wave_sums[2][k]) + wave_sums[3][k];
-    }
+    block_sums<6, kLanes>(s, a.grad_partials + ((int64_t)pose * a.blocks + blockIdx.x) * 6);
 }
 
 // launch 4: the gradient partials of a pose in workgroup order; dMIdxi -= ... makes the sum negative

@@ -285,7 +285,7 @@ int vg_photometric_level_size(const vg_photometric *s, int scale_idx, int *width
 static int build_pyramids(vg_photometric *s, int64_t n, const uint8_t *img, float *dst)
 {
     const int64_t total = s->off[s->levels];
-    hipLaunchKernelGGL(vgp::photo_convert_kernel, dim3(blocks_of(level_pixels(s, 0), vgp::kLanes), (unsigned)n), dim3(vgp::kLanes), 0, s->stream, img,
+    hipLaunchKernelGGL(vgs::u8_to_float_kernel<vgp::kLanes>, dim3(blocks_of(level_pixels(s, 0), vgp::kLanes), (unsigned)n), dim3(vgp::kLanes), 0, s->stream, img,
                        dst, level_pixels(s, 0), total);
     for (int i = 1; i < s->levels; i++)
         hipLaunchKernelGGL(vgp::photo_down_kernel, dim3(blocks_of(level_pixels(s, i), vgp::kLanes), (unsigned)n), dim3(vgp::kLanes), 0, s->stream, dst,

@@ -9,7 +9,7 @@
 #pragma once
 
 #include "vg_bicubic.hpp"
-#include "vg_stereo_device.hpp"
+#include "vg_image_device.hpp"
 
 namespace vgr {
 
@@ -94,13 +94,6 @@ struct Args {
     uint8_t *image;            // [n][P]
     unsigned long long *counts;   // [n][kCounts] or NULL
 };
-
-// every lane of the block calls this: one atomic per wave and counter
-__device__ __forceinline__ void count_wave(unsigned long long *c, bool hit)
-{
-    const int k = __popcll(__ballot(hit));
-    if ((threadIdx.x & 63) == 0 && k) atomicAdd(c, (unsigned long long)k);
-}
 
 // the bounds test both objects end with.  Written so that a NaN coordinate is outside (the reference's four comparisons let it
 // through; finite inputs give none: DESIGN.md section 9)

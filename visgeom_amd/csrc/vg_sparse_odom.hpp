@@ -17,23 +17,19 @@
 #include "vg_lm6.hpp"
 #include "vg_local.hpp"
 #include "vg_motion_prior.hpp"
-#include "vg_stereo_device.hpp"
+#include "vg_image_device.hpp"
 
 namespace vgso {
+
+using vgs::reflect101;
 
 constexpr int kThreads = 256;
 constexpr int kSelectThreads = 1024;
 constexpr int kMaxFeatures = 1024;   // the selection kernel holds the chosen keys in LDS
 constexpr int kPatch = 4, kDesc = (2 * kPatch + 1) * (2 * kPatch + 1);   // DESC_SIZE = 4: 9 x 9
-constexpr int kBorder = 7;           // harrisCorners' loop bounds
-constexpr int kBox = 3;              // blockSize 7
+constexpr int kBorder = 7;           // harrisCorners' loop bounds; the handle refuses a side below 2 kBorder + 1 = 15
+constexpr int kBox = 3;              // blockSize 7; an overhang of at most kBox < 15, so reflect101's clamp never acts
 constexpr int kTile = 16;            // distance matrix tile
-
-__device__ __forceinline__ int reflect101(int i, int n)
-{
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
 
 // Sobel 3 x 3 (scale 1) with BORDER_REFLECT_101: dx in the low, dy in the high half of one int32 (|.| <= 1020)
 __global__ __launch_bounds__(kThreads) void gradient_kernel(const uint8_t *__restrict__ img, int w, int h, int32_t *__restrict__ grad)

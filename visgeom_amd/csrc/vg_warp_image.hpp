@@ -5,7 +5,7 @@
 // The handle the two sections share -- members, create, stage steps, small entries -- is vg_frame_loop.hpp, built on this.
 #pragma once
 
-#include "vg_stereo_device.hpp"
+#include "vg_image_device.hpp"
 #include "vg_internal.hpp"
 #include "vg_transf_host.hpp"
 
@@ -30,10 +30,6 @@ inline Array6d camera_motion(const Array6d &xi_base_cam, const Array6d &xi)
 }
 
 using namespace vgs;
-
-struct Grid {   // ScaleParameters (vgd::Grid's fields; vg_depth.hpp defines kernels and belongs to its own translation unit)
-    int scale, u0, v0, x_max, y_max;
-};
 
 struct View {   // what the kernels read about the handle
     double cam[6];
