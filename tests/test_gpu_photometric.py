@@ -186,3 +186,11 @@ def test_refusals(torch, handle):
     refused(lambda: handle.compute_pose(poses[0], [-1]))
     refused(lambda: photometric.Photometric(ps.CAM, params(), ps.XI_BASE_CAM, ps.W, ps.H, 9))   # 192 >> 8 == 0
     refused(lambda: photometric.Photometric(ps.CAM, params(), ps.XI_BASE_CAM, 16, 12, 5))       # 12 >> 4 == 0
+    # the grid the wrappers compute for their shape checks is the library's (vg_depth_fusion_size), in both margin modes
+    from visgeom_amd import _handle, depth_fusion, stereo
+
+    for kw in (dict(equal_margins=0, **ps.PRM), dict(equal_margins=1, scale=3, u0=10, v0=7, u_max=ps.W, v_max=ps.H)):
+        p = stereo.make_params(**kw)
+        f = depth_fusion.DepthFusion(ps.CAM, p)
+        assert _handle._grid_size(p) == (f.x_max, f.y_max)
+        f.close()

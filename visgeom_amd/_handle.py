@@ -32,6 +32,11 @@ def _u8_images(img, height, width, what):
     return (img[None] if single else img).contiguous(), single
 
 
+def _grid_size(p):
+    """(x_max, y_max) of a vg_stereo_params as the library's creates compute it: setEqualMargin under equal_margins"""
+    return ((p.u_max - 2 * p.u0) // p.scale + 1, (p.v_max - 2 * p.v0) // p.scale + 1) if p.equal_margins else (p.x_max, p.y_max)
+
+
 def _f64_cuda(t, shape_tail, what):
     """t as a contiguous float64 CUDA tensor [n, *shape_tail]"""
     import torch

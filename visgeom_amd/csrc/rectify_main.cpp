@@ -7,95 +7,17 @@
 // Images are binary 8-bit PGM (P5) in and out: the project has no image library (the reference reads and writes PNG through
 // OpenCV).  Everything is read and checked before the GPU is touched.
 // Host-only program on top of the C ABI (include/visgeom_amd.h); links libvisgeom_amd.so and the HIP runtime for the buffers.
-#include <cctype>
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <iterator>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
-#include <unistd.h>
-
-#include <hip/hip_runtime_api.h>
-
-#include "../../include/visgeom_amd.h"
-#include "vg_json.hpp"
+#include "vg_stereo_cli.hpp"
 
 namespace {
 
-struct Image {
-    int w = 0, h = 0;
-    std::vector<unsigned char> px;
-};
-
-// binary PGM: "P5" <ws> width <ws> height <ws> maxval <one ws> width * height bytes ('#' comments in the header)
-Image read_pgm(const std::string &path)
-{
-    std::ifstream f(path, std::ios::binary);
-    if (!f) throw std::runtime_error("cannot open " + path);
-    std::string data((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-    size_t pos = 0;
-    auto skip_ws = [&]() {
-        while (pos < data.size()) {
-            if (data[pos] == '#') {
-                while (pos < data.size() && data[pos] != '\n') pos++;
-            } else if (std::isspace((unsigned char)data[pos])) {
-                pos++;
-            } else {
-                break;
-            }
-        }
-    };
-    auto number = [&]() {
-        skip_ws();
-        long long v = 0;
-        size_t digits = 0;
-        while (pos < data.size() && std::isdigit((unsigned char)data[pos]) && digits < 12) v = v * 10 + (data[pos++] - '0'), digits++;
-        if (!digits || (pos < data.size() && std::isdigit((unsigned char)data[pos]))) throw std::runtime_error(path + ": malformed PGM header");
-        return v;
-    };
-    if (data.size() < 2 || data[0] != 'P' || data[1] != '5') throw std::runtime_error(path + ": not a binary PGM (P5)");
-    pos = 2;
-    const long long w = number(), h = number(), maxval = number();
-    if (w < 1 || h < 1 || w > 16384 || h > 16384) throw std::runtime_error(path + ": image size out of range");
-    if (maxval < 1 || maxval > 255) throw std::runtime_error(path + ": only 8-bit PGM is supported");
-    if (pos >= data.size() || !std::isspace((unsigned char)data[pos])) throw std::runtime_error(path + ": malformed PGM header");
-    pos++;
-    if (data.size() - pos < (size_t)(w * h)) throw std::runtime_error(path + ": truncated PGM");
-    Image im;
-    im.w = (int)w;
-    im.h = (int)h;
-    im.px.assign(data.begin() + (std::ptrdiff_t)pos, data.begin() + (std::ptrdiff_t)(pos + (size_t)(w * h)));
-    return im;
-}
-
-void write_pgm(const std::string &path, int w, int h, const unsigned char *px)
-{
-    std::FILE *f = std::fopen(path.c_str(), "wb");
-    if (!f) throw std::runtime_error("cannot write " + path);
-    std::fprintf(f, "P5\n%d %d\n255\n", w, h);
-    const size_t n = (size_t)w * (size_t)h;
-    const bool ok = std::fwrite(px, 1, n, f) == n;
-    if (std::fclose(f) != 0 || !ok) throw std::runtime_error("cannot write " + path);
-}
-
-int die(const std::string &msg)
-{
-    std::fprintf(stderr, "rectify: %s\n", msg.c_str());
-    return 1;
-}
-
-#define HIPCHECK(expr)                                                                                  \
-    do {                                                                                                \
-        const hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return die(std::string(#expr) + ": " + hipGetErrorString(e_));            \
-    } while (0)
-#define VGCHECK(expr)                                                                                   \
-    do {                                                                                                \
-        if ((expr) != VG_OK) return die(std::string(#expr) + ": " + vg_last_error());                   \
-    } while (0)
+using vgcli::die;
+using vgcli::Image;
+using vgcli::read_pgm;
+using vgcli::write_pgm;
 
 constexpr size_t kMaxBatchBytes = size_t(1) << 30;   // source bytes of one vg_remap call
 
@@ -103,6 +25,7 @@ constexpr size_t kMaxBatchBytes = size_t(1) << 30;   // source bytes of one vg_r
 
 int main(int argc, char **argv)
 {
+    vgcli::program() = "rectify";
     if (argc != 2) {
         std::fprintf(stderr, "usage: rectify file.json\n");
         return 2;

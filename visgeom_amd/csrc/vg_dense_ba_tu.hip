@@ -17,7 +17,7 @@
 #include "vg_lmn.hpp"
 #include "vg_local.hpp"
 #include "vg_stereo_host.hpp"
-#include "vg_transf_host.hpp"
+#include "vg_pose_host.hpp"
 
 struct vg_dense_ba : vgi::HandleBase {
     double cam[6], xbc[6], Rb[9];
@@ -32,8 +32,7 @@ struct vg_dense_ba : vgi::HandleBase {
     vgi::Grow<double> d_depth_map, d_sigma_map;         // [y_max][x_max]
     vgi::Grow<int32_t> d_idx;                           // the pack, room for every cell
     vgi::Grow<double> d_val, d_dir, d_d0, d_s0;
-    vgi::Grow<unsigned> d_counts, d_offsets, d_total;
-    vgi::GrowPinned<unsigned> h_total;
+    vgi::PackScratch pack;                              // blocks of the grid; one total
     vgi::Grow<vgba::Frame> d_frames;
     vgi::GrowPinned<vgba::Frame> h_frames;
     // per slot: depth [m] | a [m] | gd [m] | res [F][m] | jd [F][m] | jp [F][m][6]; sums [F][28] + the prior's cost
@@ -48,7 +47,6 @@ namespace {
 
 using vgi::fail;
 using vgsh::blocks_of;
-using vgth::Array6d;
 
 struct Slot {
     double *depth, *a, *gd, *res, *jd, *jp;
@@ -89,13 +87,9 @@ int ensure_rows(vg_dense_ba *s)
 
 void make_frame(const vg_dense_ba *s, const double *xi, vgba::Frame &f)
 {
-    Array6d a, b;
-    std::memcpy(a.data(), xi, sizeof(double) * 6);
-    std::memcpy(b.data(), s->xbc, sizeof(double) * 6);
-    const Array6d c = vgth::compose(a, b);
-    const vg::RotTrig rt = vg::rot_trig(c.data() + 3, true, false);
-    vg::rotation_matrix(c.data() + 3, -1., rt, f.Rinv);
-    for (int i = 0; i < 3; i++) f.t[i] = c[i];
+    double c[6];
+    vgth::compose(xi, s->xbc, c);
+    vgth::inverse_frame(c, f.Rinv, f.t);
     vg::mat3_mul(f.Rinv, s->Rb, f.M);
     vg::camera_jacobian_frame(xi, s->xbc, f.L11, f.L12, f.L22);
 }
@@ -251,19 +245,12 @@ int vg_dense_ba_create(vg_dense_ba **out, int device, void *hip_stream, const do
     if (!out) return fail(VG_ERR_INVALID_ARGUMENT, "NULL output");
     *out = nullptr;
     if (!eucm || !params || !xi_base_cam) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    const vg_stereo_params &p = *params;   // only the ScaleParameters fields are read, under vg_photometric_create's ranges
-    if (p.scale < 1 || p.scale > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "scale must be in [1, 16384]");
-    if (std::abs(p.u0) > 16384 || std::abs(p.v0) > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "|u0|, |v0| must be at most 16384");
-    int x_max = p.x_max, y_max = p.y_max;
-    if (p.equal_margins) {   // ScaleParameters::setEqualMargin (scale_parameters.cpp:44-52)
-        if (p.u_max < 1 || p.u_max > 16384 || p.v_max < 1 || p.v_max > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "uMax / vMax must be in [1, 16384]");
-        x_max = (p.u_max - 2 * p.u0) / p.scale + 1;
-        y_max = (p.v_max - 2 * p.v0) / p.scale + 1;
-    }
-    if (x_max < 1 || y_max < 1 || x_max > 16384 || y_max > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "xMax / yMax must be in [1, 16384]");
+    const vg_stereo_params &p = *params;   // only the ScaleParameters fields are read; the image size is an argument
+    int x_max = 0, y_max = 0;
+    if (const int rc = vgsh::scaled_grid(p, false, x_max, y_max)) return rc;
     if (width < 1 || width > 16384 || height < 1 || height > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "the image size must be in [1, 16384]");
-    if (!vgsh::finite_n(eucm, 6) || !vgsh::finite_n(xi_base_cam, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "camera parameters and xi_base_cam must be finite");
-    if (!vgsh::focal_nonzero(eucm, eucm)) return fail(VG_ERR_INVALID_ARGUMENT, "fu, fv must be non-zero");
+    if (!vgsh::finite_n(xi_base_cam, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "xi_base_cam must be finite");
+    if (const int rc = vgsh::check_camera(eucm)) return rc;
     vg_dense_ba_options o = {0., 0., 0., 0, 0.};
     if (options) o = *options;
     if (!(o.sigma_grey >= 0.) || !std::isfinite(o.sigma_grey)) return fail(VG_ERR_INVALID_ARGUMENT, "sigma_grey must be finite and not negative");
@@ -276,8 +263,7 @@ int vg_dense_ba_create(vg_dense_ba **out, int device, void *hip_stream, const do
         s->cam[i] = eucm[i];
         s->xbc[i] = xi_base_cam[i];
     }
-    const vg::RotTrig rt = vg::rot_trig(s->xbc + 3, true, false);
-    vg::rotation_matrix(s->xbc + 3, 1., rt, s->Rb);
+    vgth::rotation(s->xbc, s->Rb);
     s->g = vgba::Grid{p.scale, p.u0, p.v0, x_max, y_max};
     s->w = width;
     s->h = height;
@@ -312,10 +298,7 @@ int vg_dense_ba_set_base(vg_dense_ba *s, const uint8_t *img, const double *depth
     if (const int rc = s->d_dir.grow((size_t)(3 * n), what)) return rc;
     if (const int rc = s->d_d0.grow((size_t)n, what)) return rc;
     if (const int rc = s->d_s0.grow((size_t)n, what)) return rc;
-    if (const int rc = s->d_counts.grow(nb, what)) return rc;
-    if (const int rc = s->d_offsets.grow(nb, what)) return rc;
-    if (const int rc = s->d_total.grow(1, what)) return rc;
-    if (const int rc = s->h_total.grow(1, "the pack count")) return rc;
+    if (const int rc = s->pack.grow(nb, 1, what)) return rc;
     VG_HIP(hipMemcpyAsync(s->d_depth_map, depth, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
     if (sigma) VG_HIP(hipMemcpyAsync(s->d_sigma_map, sigma, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
     else VG_HIP(hipMemsetAsync(s->d_sigma_map, 0, (size_t)n * sizeof(double), s->stream));
@@ -330,21 +313,20 @@ int vg_dense_ba_set_base(vg_dense_ba *s, const uint8_t *img, const double *depth
     a.sigma = s->d_sigma_map;
     a.grad_thresh = s->grad_thresh;
     a.need_sigma = s->lambda > 0. ? 1 : 0;
-    a.block_counts = s->d_counts;
-    a.block_offsets = s->d_offsets;
+    a.block_counts = s->pack.counts;
+    a.block_offsets = s->pack.offsets;
     a.idx = s->d_idx;
     a.val = s->d_val;
     a.dir = s->d_dir;
     a.d0 = s->d_d0;
     a.s0 = s->d_s0;
     hipLaunchKernelGGL((vgba::ba_select_kernel<false>), dim3(nb), dim3(vgba::kLanes), 0, s->stream, a);
-    hipLaunchKernelGGL(vgc::scan_block_counts_kernel<vgba::kLanes>, dim3(1), dim3(vgba::kLanes), 0, s->stream, (const unsigned *)s->d_counts.get(), s->d_offsets.get(), (int)nb,
-                       s->d_total.get());
+    s->pack.scan<vgba::kLanes>(s->stream, (int)nb, 0);
     hipLaunchKernelGGL((vgba::ba_select_kernel<true>), dim3(nb), dim3(vgba::kLanes), 0, s->stream, a);
     VG_HIP(hipGetLastError());
-    VG_HIP(hipMemcpyAsync(s->h_total, s->d_total, sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+    if (const int rc = s->pack.fetch(s->stream, 1)) return rc;
     if (const int rc = call.finish()) return rc;
-    s->m = s->h_total.get()[0];
+    s->m = s->pack.h_totals.get()[0];
     s->has_base = true;
     return ensure_rows(s);
 }

@@ -11,11 +11,10 @@
 #include <memory>
 #include <new>
 
-#include "vg_compact.hpp"
 #include "vg_depth.hpp"
 #include "vg_handle.hpp"
 #include "vg_stereo_host.hpp"
-#include "vg_transf_host.hpp"
+#include "vg_pose_host.hpp"
 
 struct vg_depth_fusion : vgi::HandleBase {
     double cam[6];
@@ -28,8 +27,7 @@ struct vg_depth_fusion : vgi::HandleBase {
     vgi::Grow<unsigned long long> d_zbuf;   // [n][P], like the winner buffer
     vgi::Grow<unsigned> d_winner;
     vgi::Grow<double> d_copy;   // [2][n][P]
-    vgi::Grow<unsigned> d_pack_counts, d_pack_offsets, d_pack_total;   // per block of 256 pixels; [1]
-    vgi::GrowPinned<unsigned> h_pack_total;
+    vgi::PackScratch pack;   // of the multi-hypothesis pack: per block of 256 pixels; one total
 #ifdef VG_DEPTH_WARP_STORE
     vgi::Grow<int> d_src_target;
     vgi::Grow<double> d_src_dist;
@@ -71,19 +69,10 @@ int vg_depth_fusion_create(vg_depth_fusion **out, int device, void *hip_stream, 
     if (!out) return fail(VG_ERR_INVALID_ARGUMENT, "NULL output");
     *out = nullptr;
     if (!eucm || !params) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    const vg_stereo_params &p = *params;   // only the ScaleParameters fields are read, under vg_stereo_create's ranges
-    if (p.scale < 1 || p.scale > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "scale must be in [1, 16384]");
-    if (p.u_max < 1 || p.u_max > 16384 || p.v_max < 1 || p.v_max > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "uMax / vMax must be in [1, 16384]");
-    if (std::abs(p.u0) > 16384 || std::abs(p.v0) > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "|u0|, |v0| must be at most 16384");
-    int x_max = p.x_max, y_max = p.y_max;
-    if (p.equal_margins) {   // ScaleParameters::setEqualMargin (scale_parameters.cpp:44-52)
-        x_max = (p.u_max - 2 * p.u0) / p.scale + 1;
-        y_max = (p.v_max - 2 * p.v0) / p.scale + 1;
-    }
-    if (x_max < 1 || y_max < 1) return fail(VG_ERR_INVALID_ARGUMENT, "the scaled image is empty: xMax < 1 or yMax < 1");
-    if (x_max > 16384 || y_max > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "xMax / yMax must be at most 16384");
-    if (!vgsh::finite_n(eucm, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "camera parameters must be finite");
-    if (!vgsh::focal_nonzero(eucm, eucm)) return fail(VG_ERR_INVALID_ARGUMENT, "fu, fv must be non-zero");
+    const vg_stereo_params &p = *params;   // only the ScaleParameters fields are read
+    int x_max = 0, y_max = 0;
+    if (const int rc = vgsh::scaled_grid(p, true, x_max, y_max)) return rc;
+    if (const int rc = vgsh::check_camera(eucm)) return rc;
     std::unique_ptr<vg_depth_fusion> s(new (std::nothrow) vg_depth_fusion());
     if (!s) return fail(VG_ERR_ALLOC, "out of host memory");
     for (int i = 0; i < 6; i++) s->cam[i] = eucm[i];
@@ -129,12 +118,9 @@ int vg_depth_warp(vg_depth_fusion *s, int64_t n, const double *xi12, const doubl
     if (const int rc = s->d_src_target.grow(np, "the warp's source records")) return rc;
     if (const int rc = s->d_src_dist.grow(np, "the warp's source records")) return rc;
 #endif
-    for (int64_t k = 0; k < n; k++) {   // R^T and t in FP64, with the rotation code of vg_stereo_host.hpp's build_geometry
+    for (int64_t k = 0; k < n; k++) {   // R^T and t in FP64
         vgd::WarpItem &it = s->h_item.get()[k];
-        const double *xi = xi12 + 6 * k;
-        const vg::RotTrig rt = vg::rot_trig(xi + 3, true, false);
-        vg::rotation_matrix(xi + 3, -1., rt, it.Rinv);
-        for (int i = 0; i < 3; i++) it.t[i] = xi[i];
+        vgth::inverse_frame(xi12 + 6 * k, it.Rinv, it.t);
         for (int i = 0; i < 6; i++) it.counts[i] = 0;
     }
     if (!s->warp_clean) {   // the whole blocks: a later call of fewer items relies on it
@@ -265,21 +251,16 @@ int vg_depth_pack_mh(vg_depth_fusion *s, int hyp_max, const double *depth, const
     {   // the count: the entries of every block, scanned
         vgi::Call call(s);
         if (const int rc = call.begin()) return rc;
-        const char *what = "the pack's block counts";
-        if (const int rc = s->d_pack_counts.grow(nb, what)) return rc;
-        if (const int rc = s->d_pack_offsets.grow(nb, what)) return rc;
-        if (const int rc = s->d_pack_total.grow(1, what)) return rc;
-        if (const int rc = s->h_pack_total.grow(1, what)) return rc;
-        a.block_counts = s->d_pack_counts;
-        a.block_offsets = s->d_pack_offsets;
+        if (const int rc = s->pack.grow(nb, 1, "the pack's block counts")) return rc;
+        a.block_counts = s->pack.counts;
+        a.block_offsets = s->pack.offsets;
         hipLaunchKernelGGL((vgd::depth_pack_mh_kernel<false>), dim3(nb), dim3(vgd::kLanes), 0, s->stream, a);
-        hipLaunchKernelGGL(vgc::scan_block_counts_kernel<vgd::kLanes>, dim3(1), dim3(vgd::kLanes), 0, s->stream, (const unsigned *)s->d_pack_counts.get(),
-                           s->d_pack_offsets.get(), (int)nb, s->d_pack_total.get());
+        s->pack.scan<vgd::kLanes>(s->stream, (int)nb, 0);
         VG_HIP(hipGetLastError());
-        VG_HIP(hipMemcpyAsync(s->h_pack_total, s->d_pack_total, sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+        if (const int rc = s->pack.fetch(s->stream, 1)) return rc;
         if (const int rc = call.finish()) return rc;
     }
-    *count = (int64_t)s->h_pack_total.get()[0];
+    *count = (int64_t)s->pack.h_totals.get()[0];
     if (*count == 0 || (!indices && !hyp && !cloud && !sigma_out)) return VG_OK;
     vgi::Call call(s);
     if (const int rc = call.begin()) return rc;
@@ -291,21 +272,14 @@ int vg_depth_pack_mh(vg_depth_fusion *s, int hyp_max, const double *depth, const
 int vg_transform_inverse(const double *xi, double *out6)
 {
     if (!xi || !out6) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    vgth::Array6d a;
-    std::memcpy(a.data(), xi, sizeof(double) * 6);
-    const vgth::Array6d r = vgth::inverse(a);
-    std::memcpy(out6, r.data(), sizeof(double) * 6);
+    vgth::inverse(xi, out6);
     return VG_OK;
 }
 
 int vg_transform_inverse_compose(const double *a6, const double *b6, double *out6)
 {
     if (!a6 || !b6 || !out6) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    vgth::Array6d a, b;
-    std::memcpy(a.data(), a6, sizeof(double) * 6);
-    std::memcpy(b.data(), b6, sizeof(double) * 6);
-    const vgth::Array6d r = vgth::inverse_compose(a, b);
-    std::memcpy(out6, r.data(), sizeof(double) * 6);
+    vgth::inverse_compose(a6, b6, out6);
     return VG_OK;
 }
 

@@ -18,14 +18,8 @@ using vgi::fail;
 
 constexpr int kMaxPyramid = 8;   // vg_photometric_create refuses more pyramid levels
 
-inline Array6d load6(const double *p)
-{
-    Array6d a;
-    std::memcpy(a.data(), p, sizeof(double) * 6);
-    return a;
-}
-
-inline void store6(const Array6d &a, double *p) { std::memcpy(p, a.data(), sizeof(double) * 6); }
+using vgth::load6;
+using vgth::store6;
 
 struct FrameLoop : vgi::HandleBase {
     vg_stereo_params stereo;   // of the per-key-frame SGM objects: equal_margins resolved once into x_max, y_max

@@ -1,11 +1,12 @@
-// vg_handle.hpp -- what the eight image-pipeline handles share on the host (vg_stereo, vg_motion_stereo, vg_depth_fusion,
-// vg_photometric, vg_sparse_odom, vg_render, and through vg_frame_loop.hpp vg_mono_odom and vg_mapping): the device and
-// stream of a handle, grow-only buffers, the envelope of a synchronous call, the range check of an item count and the
-// staging of per-item counters.  Host only; a new pipeline includes this.
+// vg_handle.hpp -- what the image-pipeline handles share on the host (vg_stereo, vg_motion_stereo, vg_depth_fusion,
+// vg_photometric, vg_sparse_odom, vg_render, vg_trajectory, vg_dense_ba, vg_hough, and through vg_frame_loop.hpp vg_mono_odom
+// and vg_mapping): the device and stream of a handle, grow-only buffers, the envelope of a synchronous call, the range check
+// of an item count, the staging of per-item counters and the scratch of an ordered pack.  Host only; a new pipeline includes this.
 #pragma once
 
 #include <string>
 
+#include "vg_compact.hpp"
 #include "vg_internal.hpp"
 
 namespace vgi {
@@ -149,6 +150,34 @@ struct Counters {
 private:
     Grow<unsigned long long> d_;
     GrowPinned<unsigned long long> h_;
+};
+
+// the scratch of an ordered pack (vg_compact.hpp): the count of every block, their scanned offsets, and one total per slot
+// with its pinned copy.  A slot is one scan: a level of a pyramid, an item of a batch ([item][block] counts), or the only one.
+// The count and place launches stay with the pipeline; between them it calls scan() per slot, and fetch() behind the last.
+struct PackScratch {
+    Grow<unsigned> counts, offsets, totals;
+    GrowPinned<unsigned> h_totals;
+    int grow(size_t blocks, size_t slots, const char *what)
+    {
+        if (const int rc = counts.grow(blocks, what)) return rc;
+        if (const int rc = offsets.grow(blocks, what)) return rc;
+        if (const int rc = totals.grow(slots, what)) return rc;
+        return h_totals.grow(slots, what);
+    }
+    // offsets and totals[slot] of the first nb counts
+    template <int LANES>
+    void scan(hipStream_t stream, int nb, int slot) const
+    {
+        hipLaunchKernelGGL(vgc::scan_block_counts_kernel<LANES>, dim3(1), dim3(LANES), 0, stream, (const unsigned *)counts.get(), offsets.get(), nb,
+                           totals.get() + slot);
+    }
+    // queues the copy of the first `slots` totals to h_totals
+    int fetch(hipStream_t stream, size_t slots) const
+    {
+        VG_HIP(hipMemcpyAsync(h_totals.get(), totals.get(), slots * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        return VG_OK;
+    }
 };
 
 }  // namespace vgi

@@ -25,8 +25,7 @@ struct vg_hough : vgi::HandleBase {
     vgi::Counters counters;
     vgi::Grow<int32_t> d_acc;
     vgi::Grow<float> d_rows, d_blur;
-    vgi::Grow<unsigned> d_counts, d_offsets, d_totals;
-    vgi::GrowPinned<unsigned> h_totals;
+    vgi::PackScratch pack;   // counts [image][block], one total per image
     vgi::Grow<vgh::LineRec> d_recs;
     vgi::GrowPinned<vgh::LineRec> h_recs;
 };
@@ -51,13 +50,6 @@ void gaussian(int n, double sigma, float *w)
     }
     sum = 1. / sum;
     for (int i = 0; i < n; i++) w[i] = (float)(cf[i] * sum);
-}
-
-int check_camera(const double *eucm, const char *what)
-{
-    if (!vgsh::finite_n(eucm, 6)) return fail(VG_ERR_INVALID_ARGUMENT, std::string(what) + " parameters must be finite");
-    if (eucm[2] == 0. || eucm[3] == 0.) return fail(VG_ERR_INVALID_ARGUMENT, std::string(what) + ": fu, fv must be non-zero");
-    return VG_OK;
 }
 
 int check_params(const vg_hough_params &p)
@@ -135,8 +127,8 @@ int vg_hough_create(vg_hough **out, int device, void *hip_stream, int width, int
     if (!out) return fail(VG_ERR_INVALID_ARGUMENT, "NULL output");
     *out = nullptr;
     if (!eucm6 || !acc_eucm6) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (const int rc = check_camera(eucm6, "camera")) return rc;
-    if (const int rc = check_camera(acc_eucm6, "accumulator camera")) return rc;
+    if (const int rc = vgsh::check_camera(eucm6, "camera")) return rc;
+    if (const int rc = vgsh::check_camera(acc_eucm6, "accumulator camera")) return rc;
     vg_hough_params p;
     vg_hough_params_default(&p);
     if (params) p = *params;
@@ -216,11 +208,7 @@ int vg_hough_detect(vg_hough *s, int64_t n, const uint8_t *images, int max_lines
         if (const int rc = s->d_rows.grow((size_t)(m * bins), "the blur's row pass")) return rc;
         if (!acc_blur)
             if (const int rc = s->d_blur.grow((size_t)(m * bins), "the blurred accumulators")) return rc;
-        const char *what = "the maxima's block counts";
-        if (const int rc = s->d_counts.grow((size_t)(m * nb), what)) return rc;
-        if (const int rc = s->d_offsets.grow((size_t)(m * nb), what)) return rc;
-        if (const int rc = s->d_totals.grow((size_t)m, what)) return rc;
-        if (const int rc = s->h_totals.grow((size_t)m, what)) return rc;
+        if (const int rc = s->pack.grow((size_t)(m * nb), (size_t)m, "the maxima's block counts")) return rc;
         if (const int rc = s->d_recs.grow((size_t)(m * std::max(max_lines, 1)), "the maxima")) return rc;
         if (const int rc = s->h_recs.grow((size_t)(m * std::max(max_lines, 1)), "the maxima's staging")) return rc;
         float *blur = acc_blur ? acc_blur + first * bins : s->d_blur.get();
@@ -233,22 +221,22 @@ int vg_hough_detect(vg_hough *s, int64_t n, const uint8_t *images, int max_lines
         vgh::MaximaArgs a;
         a.g = s->g;
         a.blur = blur;
-        a.block_counts = s->d_counts;
-        a.block_offsets = s->d_offsets;
+        a.block_counts = s->pack.counts;
+        a.block_offsets = s->pack.offsets;
         a.max_lines = max_lines;
         a.recs = s->d_recs;
         hipLaunchKernelGGL((vgh::hough_maxima_kernel<false>), grid, block, 0, s->stream, a);
         hipLaunchKernelGGL(vgc::scan_block_counts_items_kernel<vgh::kLanes>, dim3((unsigned)m), block, 0, s->stream,
-                           (const unsigned *)s->d_counts.get(), s->d_offsets.get(), (int)nb, s->d_totals.get());
+                           (const unsigned *)s->pack.counts.get(), s->pack.offsets.get(), (int)nb, s->pack.totals.get());
         if (max_lines > 0) hipLaunchKernelGGL((vgh::hough_maxima_kernel<true>), grid, block, 0, s->stream, a);
         VG_HIP(hipGetLastError());
-        VG_HIP(hipMemcpyAsync(s->h_totals, s->d_totals, (size_t)m * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+        if (const int rc = s->pack.fetch(s->stream, (size_t)m)) return rc;
         // every slot is copied; the host reads the written ones only
         if (max_lines > 0)
             VG_HIP(hipMemcpyAsync(s->h_recs, s->d_recs, (size_t)(m * max_lines) * sizeof(vgh::LineRec), hipMemcpyDeviceToHost, s->stream));
         if (const int rc = call.finish()) return rc;
         for (int64_t k = 0; k < m; k++) {
-            const int64_t total = s->h_totals.get()[k], item = first + k;
+            const int64_t total = s->pack.h_totals.get()[k], item = first + k;
             count[item] = (int32_t)total;
             for (int64_t j = 0; j < std::min<int64_t>(total, max_lines); j++)
                 fill_line(s, s->h_recs.get()[k * max_lines + j], lines + (item * max_lines + j) * VG_HOUGH_LINE, status + item * max_lines + j);

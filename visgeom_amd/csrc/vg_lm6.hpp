@@ -40,8 +40,12 @@ struct Step {
     bool ok;   // false: not positive definite or a candidate that is not finite; nothing to evaluate, accept() shrinks the radius
 };
 
-// the state of a solve that starts at s.x, where the cost is `cost`
-VG_LM6_FN void start(const Rule &r, State &s, double cost)
+// start() and verdict() run on the scalars every state of this rule has (cost, radius, decrease_factor, iterations, term,
+// done): S is this State or vg_lmn.hpp's, which owns no parameters; T the matching Step (mu, gdx, ddx, dx2, x2, gmax, ok).
+
+// the state of a solve that starts where the cost is `cost`
+template <class S>
+VG_LM6_FN void start(const Rule &r, S &s, double cost)
 {
     s.cost = cost;
     s.radius = r.radius0;
@@ -102,9 +106,12 @@ VG_LM6_FN void step(const Rule &r, const State &s, const double *G, Step &st)
     }
 }
 
-// One iteration's verdict on the candidate of `st`, whose cost is cost_c (anything when !st.ok).  true: the candidate was taken
-// (s.x, s.cost moved) and the caller's sums at the candidate become its current ones.  s.done ends the solve.
-VG_LM6_FN bool accept(const Rule &r, State &s, const Step &st, double cost_c)
+// One iteration's verdict on the candidate of `st`, whose cost is cost_c (anything when !st.ok).  true: the candidate is taken
+// (s.cost has moved; the owner of the parameters moves them) and the caller's sums at the candidate become its current ones.
+// s.done ends the solve.  x / xc: the six parameters of a state that owns them and their candidate, moved where the cost moves
+// (the device build of accept() keeps its statement order only with the copy at this place).
+template <class S, class T>
+VG_LM6_FN bool verdict(const Rule &r, S &s, const T &st, double cost_c, double *x = nullptr, const double *xc = nullptr)
 {
     s.iterations++;
     double rho = 0.;
@@ -125,7 +132,8 @@ VG_LM6_FN bool accept(const Rule &r, State &s, const Step &st, double cost_c)
     if (s.done) return false;
     bool taken = false;
     if (st.ok && std::isfinite(cost_c) && rho > r.min_rel_decrease) {
-        for (int k = 0; k < 6; k++) s.x[k] = st.xc[k];
+        if (x)
+            for (int k = 0; k < 6; k++) x[k] = xc[k];
         s.cost = cost_c;
         const double t = 2. * rho - 1.;
         s.radius = std::fmin(s.radius / std::fmax(1. - t * t * t, 1. / 3.), r.max_radius);
@@ -142,5 +150,8 @@ VG_LM6_FN bool accept(const Rule &r, State &s, const Step &st, double cost_c)
     if (s.iterations >= r.max_iter) s.done = true;
     return taken;
 }
+
+// the verdict for the state that owns its six parameters: s.x moves with s.cost
+VG_LM6_FN bool accept(const Rule &r, State &s, const Step &st, double cost_c) { return verdict(r, s, st, cost_c, s.x, st.xc); }
 
 }  // namespace vglm6

@@ -6,7 +6,8 @@
 //   dense_step   the reduced system S dx = -rhs (S = H_pp + mu D_p - sum w w^T / e already formed), by the Cholesky of vg_lm6.hpp
 //   head_sums    what accept() needs of the K dense parameters, in vg_lm6.hpp's order
 //   add_tail     the same five numbers of the m eliminated parameters, summed by the caller in a fixed order
-//   accept       the verdict; the caller owns the parameters and moves them when it returns true
+//   accept       the verdict (vglm6::verdict itself, as start is vglm6::start); the caller owns the parameters and moves
+//                them when it returns true
 // With m = 0 and K = 6 every statement has the shape of vglm6::step / accept: the bits are the same (tests/host/lmn_check.cpp).
 //
 // Self-contained like vg_lm6.hpp, whose Rule it shares: a plain host compiler takes it.
@@ -31,15 +32,7 @@ struct Step {
     bool ok;   // false: not positive definite or a candidate that is not finite; nothing to evaluate, accept() shrinks the radius
 };
 
-inline void start(const Rule &r, State &s, double cost)
-{
-    s.cost = cost;
-    s.radius = r.radius0;
-    s.decrease_factor = 2.;
-    s.iterations = 0;
-    s.term = VG_TERM_NO_CONVERGENCE;
-    s.done = r.max_iter < 1;
-}
+using vglm6::start;
 
 // D of one diagonal entry of J^T J
 inline double clamp_diag(const Rule &r, double a) { return a < r.dmin ? r.dmin : (a > r.dmax ? r.dmax : a); }
@@ -107,42 +100,6 @@ inline void add_tail(Step &st, const double *tail)
 
 // One iteration's verdict on the candidate of `st`, whose cost is cost_c (anything when !st.ok).  true: the caller takes the
 // candidate (s.cost has moved) and its sums at the candidate become the current ones.  s.done ends the solve.
-inline bool accept(const Rule &r, State &s, const Step &st, double cost_c)
-{
-    s.iterations++;
-    double rho = 0.;
-    if (st.ok) {
-        const double model_change = 0.5 * (st.mu * st.ddx - st.gdx);
-        rho = model_change > 0. ? (s.cost - cost_c) / model_change : -1.;
-        if (st.gmax <= r.gtol) {
-            s.term = VG_TERM_CONVERGENCE_GRADIENT;
-            s.done = true;
-        } else if (std::sqrt(st.dx2) <= r.ptol * (std::sqrt(st.x2) + r.ptol)) {
-            s.term = VG_TERM_CONVERGENCE_PARAMETER;
-            s.done = true;
-        } else if (model_change > 0. && std::isfinite(cost_c) && std::fabs(s.cost - cost_c) <= r.ftol * s.cost) {
-            s.term = VG_TERM_CONVERGENCE_FUNCTION;
-            s.done = true;
-        }
-    }
-    if (s.done) return false;
-    bool taken = false;
-    if (st.ok && std::isfinite(cost_c) && rho > r.min_rel_decrease) {
-        s.cost = cost_c;
-        const double t = 2. * rho - 1.;
-        s.radius = std::fmin(s.radius / std::fmax(1. - t * t * t, 1. / 3.), r.max_radius);
-        s.decrease_factor = 2.;
-        taken = true;
-    } else {
-        s.radius /= s.decrease_factor;
-        s.decrease_factor *= 2.;
-        if (s.radius < r.min_radius) {
-            s.term = VG_TERM_RADIUS_TOO_SMALL;
-            s.done = true;
-        }
-    }
-    if (s.iterations >= r.max_iter) s.done = true;
-    return taken;
-}
+inline bool accept(const Rule &r, State &s, const Step &st, double cost_c) { return vglm6::verdict(r, s, st, cost_c); }
 
 }  // namespace vglmn

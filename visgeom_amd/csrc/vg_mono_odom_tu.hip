@@ -306,7 +306,7 @@ int vg_mono_odom_camera_motion(const double *xi_base_cam, const double *xi, doub
 int vg_mono_odom_compose(const double *a6, const double *b6, double *out6)
 {
     if (!a6 || !b6 || !out6) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    store6(vgth::compose(load6(a6), load6(b6)), out6);
+    vgth::compose(a6, b6, out6);
     return VG_OK;
 }
 

@@ -9,7 +9,7 @@
 #include <cstring>
 
 #include "vg_geometry.hpp"
-#include "vg_transf_host.hpp"
+#include "vg_pose_host.hpp"
 
 namespace vgmp {
 
@@ -87,10 +87,9 @@ VG_HD void accumulate(const double *A, const double *J, const double *d, double 
 
 inline void add_prior(const MotionPrior &p, const double *x, double *G)
 {
-    vgth::Array6d a;
-    std::memcpy(a.data(), x, sizeof(double) * 6);
-    const vgth::Array6d d = vgth::inverse_compose(p.xi, a);
-    accumulate(p.A, p.J, d.data(), G);
+    double d[6];
+    vgth::inverse_compose(p.xi.data(), x, d);
+    accumulate(p.A, p.J, d, G);
 }
 
 }  // namespace vgmp

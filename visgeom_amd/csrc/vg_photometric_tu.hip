@@ -22,7 +22,7 @@
 #include "vg_photometric.hpp"
 #include "vg_photometric_mi.hpp"
 #include "vg_stereo_host.hpp"
-#include "vg_transf_host.hpp"
+#include "vg_pose_host.hpp"
 
 struct vg_photometric : vgi::HandleBase {
     double cam[6], xbc[6];
@@ -35,8 +35,7 @@ struct vg_photometric : vgi::HandleBase {
     vgi::Grow<float> d_base, d_targets, d_grad;   // [3][total]: img | gu | gv; [n][total]; [2][level 0] for vg_photometric_level
     vgi::Grow<int32_t> d_idx;                     // the packs: level i at off[i], room for every pixel
     vgi::Grow<double> d_val, d_cloud;
-    vgi::Grow<unsigned> d_counts, d_offsets, d_total;
-    vgi::GrowPinned<unsigned> h_total;
+    vgi::PackScratch pack;                        // blocks of level 0; one total per level
     vgi::Grow<vgp::PoseFrame> d_frames;
     vgi::GrowPinned<vgp::PoseFrame> h_frames;
     vgi::Grow<double> d_partials, d_sums;         // [n][blocks][kSums]; [n][kSums]
@@ -51,7 +50,6 @@ namespace {
 
 using vgi::fail;
 using vgsh::blocks_of;
-using vgth::Array6d;
 constexpr int kMaxIterations = 150;    // photometric.cpp:150
 // Ceres' defaults, which the reference leaves in place (photometric.cpp:148-150), under the rule of vg_lm6.hpp
 constexpr vglm6::Rule kRule = vglm6::ceres_defaults(kMaxIterations);
@@ -61,13 +59,9 @@ int64_t level_pixels(const vg_photometric *s, int i) { return (int64_t)s->w[i] *
 // the frame of pose xi: xiCam = xi o xi_base_cam for the points, CameraJacobian(camera, xi, xi_base_cam) for the rows
 void make_frame(const vg_photometric *s, const double *xi, int target, bool active, vgp::PoseFrame &f)
 {
-    Array6d a, b;
-    std::memcpy(a.data(), xi, sizeof(double) * 6);
-    std::memcpy(b.data(), s->xbc, sizeof(double) * 6);
-    const Array6d c = vgth::compose(a, b);
-    const vg::RotTrig rt = vg::rot_trig(c.data() + 3, true, false);
-    vg::rotation_matrix(c.data() + 3, -1., rt, f.Rinv);
-    for (int i = 0; i < 3; i++) f.t[i] = c[i];
+    double c[6];
+    vgth::compose(xi, s->xbc, c);
+    vgth::inverse_frame(c, f.Rinv, f.t);
     vg::camera_jacobian_frame(xi, s->xbc, f.L11, f.L12, f.L22);
     f.target = target;
     f.active = active ? 1 : 0;
@@ -217,11 +211,9 @@ vgp::MiOdometry make_mi_odometry(const double *xi_odom, const double *xi_prior)
 
 void add_mi_odometry(const vgp::MiOdometry &o, const double *x, double *cost, double *gradient)
 {
-    Array6d a, p;
-    std::memcpy(a.data(), x, sizeof(double) * 6);
-    std::memcpy(p.data(), o.prior, sizeof(double) * 6);
-    const Array6d err = vgth::inverse_compose(p, a);
-    vgp::mi_odometry_add(o, err.data(), cost, gradient);
+    double err[6];
+    vgth::inverse_compose(o.prior, x, err);
+    vgp::mi_odometry_add(o, err, cost, gradient);
 }
 
 }  // namespace
@@ -234,22 +226,15 @@ int vg_photometric_create(vg_photometric **out, int device, void *hip_stream, co
     if (!out) return fail(VG_ERR_INVALID_ARGUMENT, "NULL output");
     *out = nullptr;
     if (!eucm || !params || !xi_base_cam) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    const vg_stereo_params &p = *params;   // only the ScaleParameters fields are read, under vg_depth_fusion_create's ranges
-    if (p.scale < 1 || p.scale > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "scale must be in [1, 16384]");
-    if (std::abs(p.u0) > 16384 || std::abs(p.v0) > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "|u0|, |v0| must be at most 16384");
-    int x_max = p.x_max, y_max = p.y_max;
-    if (p.equal_margins) {   // ScaleParameters::setEqualMargin (scale_parameters.cpp:44-52)
-        if (p.u_max < 1 || p.u_max > 16384 || p.v_max < 1 || p.v_max > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "uMax / vMax must be in [1, 16384]");
-        x_max = (p.u_max - 2 * p.u0) / p.scale + 1;
-        y_max = (p.v_max - 2 * p.v0) / p.scale + 1;
-    }
-    if (x_max < 1 || y_max < 1 || x_max > 16384 || y_max > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "xMax / yMax must be in [1, 16384]");
+    const vg_stereo_params &p = *params;   // only the ScaleParameters fields are read; the image size is an argument
+    int x_max = 0, y_max = 0;
+    if (const int rc = vgsh::scaled_grid(p, false, x_max, y_max)) return rc;
     if (width < 1 || width > 16384 || height < 1 || height > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "the image size must be in [1, 16384]");
     if (num_scales < 1 || num_scales > vgp::kMaxLevels) return fail(VG_ERR_INVALID_ARGUMENT, "num_scales must be in [1, 8]");
     if ((width >> (num_scales - 1)) < 1 || (height >> (num_scales - 1)) < 1)
         return fail(VG_ERR_INVALID_ARGUMENT, "num_scales shrinks the coarsest level to zero size");
-    if (!vgsh::finite_n(eucm, 6) || !vgsh::finite_n(xi_base_cam, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "camera parameters and xi_base_cam must be finite");
-    if (!vgsh::focal_nonzero(eucm, eucm)) return fail(VG_ERR_INVALID_ARGUMENT, "fu, fv must be non-zero");
+    if (!vgsh::finite_n(xi_base_cam, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "xi_base_cam must be finite");
+    if (const int rc = vgsh::check_camera(eucm)) return rc;
     std::unique_ptr<vg_photometric> s(new (std::nothrow) vg_photometric());
     if (!s) return fail(VG_ERR_ALLOC, "out of host memory");
     for (int i = 0; i < 6; i++) {
@@ -294,7 +279,7 @@ static int build_pyramids(vg_photometric *s, int64_t n, const uint8_t *img, floa
     return VG_OK;
 }
 
-// the data pack and _hist1 of every scale from the resident pyramid and the depth map, the counts to h_total; with `sobel` the
+// the data pack and _hist1 of every scale from the resident pyramid and the depth map, the counts to pack.h_totals; with `sobel` the
 // gradients of the pyramid first (a new image).  Enqueues only.
 static int launch_packs(vg_photometric *s, const double *depth, bool sobel)
 {
@@ -304,11 +289,10 @@ static int launch_packs(vg_photometric *s, const double *depth, bool sobel)
     for (int i = 0; i < 6; i++) a.cam[i] = s->cam[i];
     a.g = s->g;
     a.depth = depth;
-    const vg::RotTrig rt = vg::rot_trig(s->xbc + 3, true, false);
-    vg::rotation_matrix(s->xbc + 3, 1., rt, a.Rb);
+    vgth::rotation(s->xbc, a.Rb);
     for (int i = 0; i < 3; i++) a.tb[i] = s->xbc[i];
-    a.block_counts = s->d_counts;
-    a.block_offsets = s->d_offsets;
+    a.block_counts = s->pack.counts;
+    a.block_offsets = s->pack.offsets;
     for (int i = 0; i < s->levels; i++) {
         const unsigned nb = blocks_of(level_pixels(s, i), vgp::kLanes);
         if (sobel)
@@ -324,18 +308,16 @@ static int launch_packs(vg_photometric *s, const double *depth, bool sobel)
         a.val = s->d_val.get() + s->off[i];
         a.cloud = s->d_cloud.get() + 3 * s->off[i];
         hipLaunchKernelGGL((vgp::photo_select_kernel<false>), dim3(nb), dim3(vgp::kLanes), 0, s->stream, a);
-        hipLaunchKernelGGL(vgc::scan_block_counts_kernel<vgp::kLanes>, dim3(1), dim3(vgp::kLanes), 0, s->stream, (const unsigned *)s->d_counts.get(), s->d_offsets.get(),
-                           (int)nb, s->d_total.get() + i);
+        s->pack.scan<vgp::kLanes>(s->stream, (int)nb, i);
         hipLaunchKernelGGL((vgp::photo_select_kernel<true>), dim3(nb), dim3(vgp::kLanes), 0, s->stream, a);
         // MutualInformation's _hist1 depends on the pack only
-        hipLaunchKernelGGL(vgp::mi_hist1_kernel, dim3(nb), dim3(vgp::kLanes), 0, s->stream, (const double *)a.val, (const unsigned *)(s->d_total.get() + i),
+        hipLaunchKernelGGL(vgp::mi_hist1_kernel, dim3(nb), dim3(vgp::kLanes), 0, s->stream, (const double *)a.val, (const unsigned *)(s->pack.totals.get() + i),
                            s->d_hist1_partials.get());
         hipLaunchKernelGGL(vgp::mi_hist1_reduce_kernel, dim3(1), dim3(64), 0, s->stream, (const double *)s->d_hist1_partials.get(), (int)nb,
                            s->d_hist1.get() + vgp::kMiBins * i);
     }
     VG_HIP(hipGetLastError());
-    VG_HIP(hipMemcpyAsync(s->h_total, s->d_total, vgp::kMaxLevels * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
-    return VG_OK;
+    return s->pack.fetch(s->stream, vgp::kMaxLevels);
 }
 
 int vg_photometric_set_base(vg_photometric *s, const uint8_t *img, const double *depth)
@@ -353,17 +335,14 @@ int vg_photometric_set_base(vg_photometric *s, const uint8_t *img, const double 
         if (const int rc = s->d_idx.grow((size_t)total, what)) return rc;
         if (const int rc = s->d_val.grow((size_t)total, what)) return rc;
         if (const int rc = s->d_cloud.grow((size_t)(3 * total), what)) return rc;
-        if (const int rc = s->d_counts.grow(nb, what)) return rc;
-        if (const int rc = s->d_offsets.grow(nb, what)) return rc;
-        if (const int rc = s->d_total.grow(vgp::kMaxLevels, what)) return rc;
+        if (const int rc = s->pack.grow(nb, vgp::kMaxLevels, what)) return rc;
         if (const int rc = s->d_hist1.grow((size_t)vgp::kMaxLevels * vgp::kMiBins, what)) return rc;
         if (const int rc = s->d_hist1_partials.grow(nb * vgp::kMiBins, what)) return rc;
-        if (const int rc = s->h_total.grow(vgp::kMaxLevels, "the pack counts")) return rc;
     }
     if (const int rc = build_pyramids(s, 1, img, s->d_base.get())) return rc;
     if (const int rc = launch_packs(s, depth, true)) return rc;
     if (const int rc = call.finish()) return rc;
-    for (int i = 0; i < s->levels; i++) s->m[i] = s->h_total.get()[i];
+    for (int i = 0; i < s->levels; i++) s->m[i] = s->pack.h_totals.get()[i];
     s->has_base = true;
     return VG_OK;
 }
@@ -378,7 +357,7 @@ int vg_photo_set_depth(vg_photometric *s, const double *depth)
     s->has_base = false;   // the packs are rewritten: a failure below leaves no key frame
     if (const int rc = launch_packs(s, depth, false)) return rc;
     if (const int rc = call.finish()) return rc;
-    for (int i = 0; i < s->levels; i++) s->m[i] = s->h_total.get()[i];
+    for (int i = 0; i < s->levels; i++) s->m[i] = s->pack.h_totals.get()[i];
     s->has_base = true;
     return VG_OK;
 }

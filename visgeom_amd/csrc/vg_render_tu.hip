@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "vg_handle.hpp"
+#include "vg_pose_host.hpp"
 #include "vg_render.hpp"
 #include "vg_stereo_host.hpp"
 
@@ -47,16 +48,7 @@ const double *filter_table()   // built once, on first use
 int check_camera(const double *eucm)
 {
     if (!eucm) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!vgsh::finite_n(eucm, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "camera parameters must be finite");
-    if (!vgsh::focal_nonzero(eucm, eucm)) return fail(VG_ERR_INVALID_ARGUMENT, "fu, fv must be non-zero");
-    return VG_OK;
-}
-
-// rotMat of a pose [t, rotvec], row-major, with the rotation code every handle uses
-void rot_mat(const double *xi, double *R)
-{
-    const vg::RotTrig rt = vg::rot_trig(xi + 3, true, false);
-    vg::rotation_matrix(xi + 3, 1., rt, R);
+    return vgsh::check_camera(eucm);
 }
 
 }  // namespace
@@ -102,7 +94,7 @@ int vg_render_create(vg_render **out, int device, void *hip_stream, const double
             o.fu = src.cols / src.width;
             o.fv = src.rows / src.height;
             for (int i = 0; i < 3; i++) o.t[i] = src.pose[i];
-            rot_mat(src.pose, R);
+            vgth::rotation(src.pose, R);
         }
         for (int i = 0; i < 3; i++) {   // the columns of the rotation
             o.ex[i] = R[3 * i];
@@ -175,7 +167,7 @@ int vg_render_views(vg_render *s, int64_t n, const double *xi_cam, uint8_t *imag
         if (const int rc = s->d_v.grow(np, "the texture coordinate buffer")) return rc;
     for (int64_t k = 0; k < n; k++) {
         vgr::View &view = s->h_views.get()[k];
-        rot_mat(xi_cam + 6 * k, view.R);
+        vgth::rotation(xi_cam + 6 * k, view.R);
         for (int i = 0; i < 3; i++) view.t[i] = xi_cam[6 * k + i];
     }
     VG_HIP(hipMemcpyAsync(s->d_views, s->h_views, (size_t)n * sizeof(vgr::View), hipMemcpyHostToDevice, s->stream));

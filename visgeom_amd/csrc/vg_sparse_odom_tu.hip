@@ -17,13 +17,12 @@
 #include "vg_motion_prior.hpp"
 #include "vg_sparse_odom.hpp"
 #include "vg_stereo_host.hpp"
-#include "vg_transf_host.hpp"
+#include "vg_pose_host.hpp"
 
 namespace {
 
 using vgi::fail;
 using vgsh::blocks_of;
-using vgth::Array6d;
 
 constexpr int64_t kMaxPoints = 1 << 20;   // matches of a ransac / score call, entries of a solve call
 
@@ -246,12 +245,11 @@ int run_solve(vg_sparse_odom *s, int64_t n_blocks, const int64_t *offsets, const
 }
 
 // the camera motion xi_c = xi_base_cam^-1 o xi o xi_base_cam
-Array6d camera_motion(const vg_sparse_odom *s, const double *xi)
+void camera_motion(const vg_sparse_odom *s, const double *xi, double *out6)
 {
-    Array6d a, b;
-    std::memcpy(a.data(), xi, sizeof(double) * 6);
-    std::memcpy(b.data(), s->xbc, sizeof(double) * 6);
-    return vgth::compose(vgth::inverse_compose(b, a), b);
+    double rel[6];
+    vgth::inverse_compose(s->xbc, xi, rel);
+    vgth::compose(rel, s->xbc, out6);
 }
 
 // n_hyp poses scored on m matches (index HOST [m] into the point arrays, or NULL); residual DEVICE or NULL; the counts in
@@ -269,11 +267,9 @@ int run_score(vg_sparse_odom *s, int64_t n_hyp, const double *xi, int64_t m, con
         if (const int rc = s->d_index.grow((size_t)m, "the sparse odometry scratch")) return rc;
     double *f = s->h_res.get();
     for (int64_t k = 0; k < n_hyp; k++, f += vgso::kScoreFrame) {
-        const Array6d c = camera_motion(s, xi + 6 * k);
-        const vg::RotTrig rt = vg::rot_trig(c.data() + 3, true, false);
-        for (int i = 0; i < 3; i++) f[i] = c[i];
-        vg::rotation_matrix(c.data() + 3, 1., rt, f + 3);
-        vg::rotation_matrix(c.data() + 3, -1., rt, f + 12);
+        double c[6];   // t | R | Rinv of the camera motion
+        camera_motion(s, xi + 6 * k, c);
+        vgth::inverse_frame(c, f + 12, f, f + 3);
     }
     VG_HIP(hipMemcpyAsync(s->d_frames.get(), s->h_res.get(), (size_t)n_hyp * vgso::kScoreFrame * sizeof(double), hipMemcpyHostToDevice, s->stream));
     if (index) VG_HIP(hipMemcpyAsync(s->d_index.get(), index, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
@@ -428,8 +424,8 @@ int vg_sparse_odom_create(vg_sparse_odom **out, int device, void *hip_stream, co
     if (!(p.prior_err_v > 0.) || !(p.prior_err_w > 0.) || !(p.prior_lambda_t > 0.) || !(p.prior_lambda_r > 0.) || !std::isfinite(p.prior_err_v) ||
         !std::isfinite(p.prior_err_w) || !std::isfinite(p.prior_lambda_t) || !std::isfinite(p.prior_lambda_r))
         return fail(VG_ERR_INVALID_ARGUMENT, "the prior's four constants must be positive and finite");
-    if (!vgsh::finite_n(eucm, 6) || !vgsh::finite_n(xi_base_cam, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "camera parameters and xi_base_cam must be finite");
-    if (!vgsh::focal_nonzero(eucm, eucm)) return fail(VG_ERR_INVALID_ARGUMENT, "fu, fv must be non-zero");
+    if (!vgsh::finite_n(xi_base_cam, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "xi_base_cam must be finite");
+    if (const int rc = vgsh::check_camera(eucm)) return rc;
     std::unique_ptr<vg_sparse_odom> s(new (std::nothrow) vg_sparse_odom());
     if (!s) return fail(VG_ERR_ALLOC, "out of host memory");
     for (int i = 0; i < 6; i++) {
@@ -578,13 +574,12 @@ int vg_sparse_odom_feed(vg_sparse_odom *s, const uint8_t *img, const double *xi_
         if (report) std::memcpy(report, rep, sizeof rep);
         return VG_OK;
     };
-    Array6d prev, now;
-    std::memcpy(prev.data(), s->odom_prev, sizeof(double) * 6);
-    std::memcpy(now.data(), xi_odom_new, sizeof(double) * 6);
-    const Array6d odom_incr = vgth::inverse_compose(prev, now);
+    double odom_incr[6];
+    vgth::inverse_compose(s->odom_prev, xi_odom_new, odom_incr);
     if (s->has_prev && s->n_kp[s->cur] > 0) {   // the skip rule (sparse_odom.cpp:242-244)
-        const Array6d dxi = camera_motion(s, odom_incr.data());
-        if (vg::norm3(dxi.data()) < s->prm.min_stereo_base) return finish(VG_SPARSE_ODOM_SKIPPED);
+        double dxi[6];
+        camera_motion(s, odom_incr, dxi);
+        if (vg::norm3(dxi) < s->prm.min_stereo_base) return finish(VG_SPARSE_ODOM_SKIPPED);
     }
     VG_HIP(hipSetDevice(s->device));
     const int nxt = 1 - s->cur;
@@ -620,13 +615,9 @@ int vg_sparse_odom_feed(vg_sparse_odom *s, const uint8_t *img, const double *xi_
             else
                 draw_samples(s, m, table.data());
         }
-        if (const int rc = run_ransac(s, m, x1, x2, p2, size, odom_incr.data(), table.empty() ? nullptr : table.data(), s->xi_incr, s->d_mask.get(), rep + 4))
+        if (const int rc = run_ransac(s, m, x1, x2, p2, size, odom_incr, table.empty() ? nullptr : table.data(), s->xi_incr, s->d_mask.get(), rep + 4))
             return rc;
-        Array6d loc, inc;
-        std::memcpy(loc.data(), s->xi_local, sizeof(double) * 6);
-        std::memcpy(inc.data(), s->xi_incr, sizeof(double) * 6);
-        const Array6d out = vgth::compose(loc, inc);   // xiLocal = xiLocal.compose(xiIncr)
-        std::memcpy(s->xi_local, out.data(), sizeof(double) * 6);
+        vgth::compose(s->xi_local, s->xi_incr, s->xi_local);   // xiLocal = xiLocal.compose(xiIncr)
     }
     s->cur = nxt;   // refresh state (:432-436)
     s->has_prev = true;

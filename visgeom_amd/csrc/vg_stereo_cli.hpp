@@ -1,4 +1,4 @@
-// vg_stereo_cli.hpp -- what the `stereo`, `motion_stereo`, `render`, `mono_odom` and `mapping` programs share: binary PGM in
+// vg_stereo_cli.hpp -- what the `rectify`, `stereo`, `motion_stereo`, `render`, `mono_odom` and `mapping` programs share: binary PGM in
 // and out, PFM out, the parameters of ex_epipolar_stereo.json's "stereo_parameters" object with its motion stereo part, path
 // handling and the one-line error exit.  Host only.
 #pragma once

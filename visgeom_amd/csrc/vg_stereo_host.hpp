@@ -62,17 +62,14 @@ inline void cross3(const double *a, const double *b, double *c)
     c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-inline int check_params(const vg_stereo_params &p, int &x_max, int &y_max)
+// The ScaleParameters fields of p, the only ones the handles on a depth grid read: their ranges and the grid's size.  uMax / vMax
+// are checked where they are read: always by a handle that also takes them for the image size (image_size_always), under
+// equal_margins by the others.
+inline int scaled_grid(const vg_stereo_params &p, bool image_size_always, int &x_max, int &y_max)
 {
-    if (p.hypotheses != 1) return fail(VG_ERR_INVALID_ARGUMENT, "hypotheses must be 1 (reconstructDisparityMH is not provided)");
-    if (p.disp_max < 4 || p.disp_max > 256 || p.disp_max % 2) return fail(VG_ERR_INVALID_ARGUMENT, "disparity_max must be even in [4, 256]");
-    if (p.desc_length < 3 || p.desc_length > vgs::kMaxDesc || p.desc_length % 2 == 0)
-        return fail(VG_ERR_INVALID_ARGUMENT, "descriptor_size must be odd in [3, 31]");
-    if (p.n_scales < 1 || p.n_scales > vgs::kMaxScales) return fail(VG_ERR_INVALID_ARGUMENT, "1 to 8 descriptor scales");
-    for (int i = 0; i < p.n_scales; i++)
-        if (p.scales[i] < 1 || p.scales[i] > 16) return fail(VG_ERR_INVALID_ARGUMENT, "every descriptor scale must be in [1, 16]");
     if (p.scale < 1 || p.scale > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "scale must be in [1, 16384]");
-    if (p.u_max < 1 || p.u_max > 16384 || p.v_max < 1 || p.v_max > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "uMax / vMax must be in [1, 16384]");
+    if ((image_size_always || p.equal_margins) && (p.u_max < 1 || p.u_max > 16384 || p.v_max < 1 || p.v_max > 16384))
+        return fail(VG_ERR_INVALID_ARGUMENT, "uMax / vMax must be in [1, 16384]");
     if (std::abs(p.u0) > 16384 || std::abs(p.v0) > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "|u0|, |v0| must be at most 16384");
     x_max = p.x_max;
     y_max = p.y_max;
@@ -82,6 +79,19 @@ inline int check_params(const vg_stereo_params &p, int &x_max, int &y_max)
     }
     if (x_max < 1 || y_max < 1) return fail(VG_ERR_INVALID_ARGUMENT, "the scaled image is empty: xMax < 1 or yMax < 1");
     if (x_max > 16384 || y_max > 16384) return fail(VG_ERR_INVALID_ARGUMENT, "xMax / yMax must be at most 16384");
+    return VG_OK;
+}
+
+inline int check_params(const vg_stereo_params &p, int &x_max, int &y_max)
+{
+    if (p.hypotheses != 1) return fail(VG_ERR_INVALID_ARGUMENT, "hypotheses must be 1 (reconstructDisparityMH is not provided)");
+    if (p.disp_max < 4 || p.disp_max > 256 || p.disp_max % 2) return fail(VG_ERR_INVALID_ARGUMENT, "disparity_max must be even in [4, 256]");
+    if (p.desc_length < 3 || p.desc_length > vgs::kMaxDesc || p.desc_length % 2 == 0)
+        return fail(VG_ERR_INVALID_ARGUMENT, "descriptor_size must be odd in [3, 31]");
+    if (p.n_scales < 1 || p.n_scales > vgs::kMaxScales) return fail(VG_ERR_INVALID_ARGUMENT, "1 to 8 descriptor scales");
+    for (int i = 0; i < p.n_scales; i++)
+        if (p.scales[i] < 1 || p.scales[i] > 16) return fail(VG_ERR_INVALID_ARGUMENT, "every descriptor scale must be in [1, 16]");
+    if (const int rc = scaled_grid(p, true, x_max, y_max)) return rc;
     if (p.num_epipolar_planes < 2 || p.num_epipolar_planes > (1 << 20) || p.num_epipolar_planes % 2)
         return fail(VG_ERR_INVALID_ARGUMENT, "num_epipolar_planes must be even in [2, 2^20]");
     if (p.epipole_margin < 0) return fail(VG_ERR_INVALID_ARGUMENT, "epipole_margin must be >= 0");
@@ -100,6 +110,13 @@ inline bool finite_n(const double *v, int n)
 
 // what both handles ask of a camera pair and of a pose [t, rotvec] besides finite_n
 inline bool focal_nonzero(const double *c1, const double *c2) { return c1[2] != 0. && c1[3] != 0. && c2[2] != 0. && c2[3] != 0.; }
+// one camera: six finite values, fu and fv non-zero.  what: the camera's name in a handle that has more than one
+inline int check_camera(const double *eucm, const char *what = nullptr)
+{
+    if (!finite_n(eucm, 6)) return fail(VG_ERR_INVALID_ARGUMENT, std::string(what ? what : "camera") + " parameters must be finite");
+    if (!focal_nonzero(eucm, eucm)) return fail(VG_ERR_INVALID_ARGUMENT, (what ? std::string(what) + ": " : std::string()) + "fu, fv must be non-zero");
+    return VG_OK;
+}
 inline bool has_baseline(const double *xi) { return xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2] > 1e-10; }   // false for NaN
 
 inline unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }

@@ -54,8 +54,7 @@ int check_scene(int model, const double *intrinsics, int width, int height, cons
 {
     if (model != VG_MODEL_EUCM) return fail(VG_ERR_INVALID_ARGUMENT, "trajectory planning is built for the EUCM camera only");
     if (!intrinsics || !q) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!vgsh::finite_n(intrinsics, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "camera parameters must be finite");
-    if (!vgsh::focal_nonzero(intrinsics, intrinsics)) return fail(VG_ERR_INVALID_ARGUMENT, "fu, fv must be non-zero");
+    if (const int rc = vgsh::check_camera(intrinsics)) return rc;
     if (width < 1 || height < 1) return fail(VG_ERR_INVALID_ARGUMENT, "the image's width and height must be positive");
     if (!vgsh::finite_n(q->xi_base_cam, 6) || !vgsh::finite_n(q->xi_orig_board, 6)) return fail(VG_ERR_INVALID_ARGUMENT, "xiBaseCam and xiOrigBoard must be finite");
     if (q->board_cols < 2 || q->board_rows < 2 || (int64_t)q->board_cols * q->board_rows > vgt::kMaxCorners)

@@ -7,7 +7,7 @@
 
 #include "vg_image_device.hpp"
 #include "vg_internal.hpp"
-#include "vg_transf_host.hpp"
+#include "vg_pose_host.hpp"
 
 namespace vgmo {
 
@@ -74,9 +74,7 @@ __device__ inline uint8_t warp_image_value(const WarpImageArgs &a, int64_t pix)
 inline void warp_image_pose(const Array6d &xi_base_cam, const Array6d &xi, WarpImageArgs &args)
 {
     const Array6d motion = camera_motion(xi_base_cam, xi);
-    const vg::RotTrig rt = vg::rot_trig(motion.data() + 3, true, false);
-    vg::rotation_matrix(motion.data() + 3, -1., rt, args.Rinv);   // rotMatInv
-    for (int i = 0; i < 3; i++) args.t[i] = motion[i];
+    vgth::inverse_frame(motion.data(), args.Rinv, args.t);   // rotMatInv, trans
 }
 
 }  // namespace vgmo

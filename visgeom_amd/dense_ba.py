@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 
 from . import capi
-from ._handle import Handle, _is_cuda, _u8_images, _vec
+from ._handle import Handle, _grid_size, _is_cuda, _u8_images, _vec
 
 _dp = ctypes.POINTER(ctypes.c_double)
 REPORT = ("iterations", "initial_cost", "final_cost", "termination")
@@ -53,9 +53,7 @@ class DenseBA(Handle):
             raise ValueError("options must be a vg_dense_ba_options (make_options())")
         self.options = options
         self.width, self.height = int(width), int(height)
-        p = self.params
-        self.x_max = (p.u_max - 2 * p.u0) // p.scale + 1 if p.equal_margins else p.x_max
-        self.y_max = (p.v_max - 2 * p.v0) // p.scale + 1 if p.equal_margins else p.y_max
+        self.x_max, self.y_max = _grid_size(self.params)
         self.frames = 0
         self._open(capi.load().vg_dense_ba_create, self._c.ctypes.data_as(_dp), ctypes.byref(self.params), self._xbc.ctypes.data_as(_dp),
                    self.width, self.height, ctypes.byref(options) if options is not None else None)

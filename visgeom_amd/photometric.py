@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 
 from . import capi
-from ._handle import Handle, _is_cuda, _u8_images, _vec
+from ._handle import Handle, _grid_size, _is_cuda, _u8_images, _vec
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -54,9 +54,7 @@ class Photometric(Handle):
             raise ValueError("img must be [height, width]")
         if not _is_cuda(depth, torch.float64) or depth.dim() != 2:
             raise ValueError("depth must be a float64 CUDA tensor [y_max, x_max]")
-        p = self.params
-        x_max = (p.u_max - 2 * p.u0) // p.scale + 1 if p.equal_margins else p.x_max
-        y_max = (p.v_max - 2 * p.v0) // p.scale + 1 if p.equal_margins else p.y_max
+        x_max, y_max = _grid_size(self.params)
         if tuple(depth.shape) != (y_max, x_max):
             raise ValueError("depth must be [y_max, x_max] = [%d, %d]" % (y_max, x_max))
         depth = depth.contiguous()
@@ -72,9 +70,7 @@ class Photometric(Handle):
 
         if not _is_cuda(depth, torch.float64) or depth.dim() != 2:
             raise ValueError("depth must be a float64 CUDA tensor [y_max, x_max]")
-        p = self.params
-        x_max = (p.u_max - 2 * p.u0) // p.scale + 1 if p.equal_margins else p.x_max
-        y_max = (p.v_max - 2 * p.v0) // p.scale + 1 if p.equal_margins else p.y_max
+        x_max, y_max = _grid_size(self.params)
         if tuple(depth.shape) != (y_max, x_max):
             raise ValueError("depth must be [y_max, x_max] = [%d, %d]" % (y_max, x_max))
         depth = depth.contiguous()
