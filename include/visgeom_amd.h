@@ -780,6 +780,60 @@ int vg_depth_regularize(vg_depth_fusion *h, int64_t n, int hyp_max, double *dept
  * reconstruct) and sigma_out FP64 (needs sigma).  The order is the same on every run. */
 int vg_depth_pack_mh(vg_depth_fusion *h, int hyp_max, const double *depth, const double *sigma, int64_t *count, int32_t *indices,
                      int32_t *hyp, double *cloud, double *sigma_out);
+/* Section 11, continued: point clouds, the plane prior and the accuracy score (deviations: section 9,
+ * "Point clouds and accuracy").  The flags of DepthMap::reconstruct with the reference's values (depth_map.h:39-49). */
+#define VG_RECON_QUERY_POINTS 1u
+#define VG_RECON_IMAGE_VALUES 2u /* refused: the reference asserts on it */
+#define VG_RECON_MINMAX 4u
+#define VG_RECON_ALL_HYPOTHESES 8u
+#define VG_RECON_DEFAULT_VALUES 16u
+#define VG_RECON_SIGMA_VALUE 32u
+#define VG_RECON_QUERY_INDICES 64u
+#define VG_RECON_INDEX_MAPPING 128u
+/* The entries of vg_depth_reconstruct: DEVICE arrays of m entries each (m: the sum of counts), every one may be NULL.  indices
+ * (y x_max + x), hyp, points [m][2] (the reference's imagePointVec: the image point the ray goes through), sigma_out (needs
+ * SIGMA_VALUE), index_map (the query's position; needs INDEX_MAPPING and a query flag), item (the map an entry came from), valid
+ * (1 where the camera reconstructs the ray), cloud [m][3], or [m][2][3] (near, far) under MINMAX. */
+typedef struct vg_recon_outputs {
+    int32_t *indices, *hyp;
+    double *points, *sigma_out;
+    int32_t *index_map, *item;
+    uint8_t *valid;
+    double *cloud;
+} vg_recon_outputs;
+/* DepthMap::reconstruct(pack, flags) (depth_map.cpp:532-635) of n maps, depth and sigma DEVICE FP64 [n][hyp_max][y_max][x_max],
+ * hyp_max in [1, 8]; without ALL_HYPOTHESES only plane 0 is read; sigma may be NULL unless SIGMA_VALUE or MINMAX reads it.
+ * Queried are, without a query flag, the pixels whose plane 0 holds a depth >= MIN_DEPTH in raster order, the ray through
+ * (uConv(x), vConv(y)); under QUERY_INDICES (stronger than QUERY_POINTS, as in the reference) query_indices, DEVICE int32
+ * [n_query] shared by all items: an index in [0, x_max y_max) is used with the ray through its pixel, any other is skipped;
+ * under QUERY_POINTS query_points, DEVICE FP64 [n_query][2]: the pixel is x = round((u - u0) / scale), y likewise (half away
+ * from zero, compared against the map in double), a point outside the map or not finite is skipped, the depth is the nearest
+ * pixel's and the ray goes through the query point itself.  Per queried pixel and for h ascending a plane with depth <
+ * MIN_DEPTH (NaN included) is skipped, except under DEFAULT_VALUES at h = 0, where the entry takes depth 5 and sigma 30.  The
+ * cloud is the normalised ray times the depth; under MINMAX times max(depth - 3 sigma, MIN_DEPTH) and depth + 3 sigma; (0, 0,
+ * 0) with valid 0 where the camera cannot reconstruct.  xi (HOST [n][6], may be NULL, every entry finite): item k's valid
+ * cloud points are moved by Transformation::transform of xi[k]; failed entries stay (0, 0, 0).  Order: item after item, query
+ * order, h ascending; bit-identical from run to run.  counts (HOST int64 [n], required) receives the entries per item; out ==
+ * NULL or all of its members NULL only counts.  A call whose entries could reach 2^31 (n times the queries or pixels times
+ * the planes read) is refused. */
+int vg_depth_reconstruct(vg_depth_fusion *h, int64_t n, int hyp_max, uint32_t flags, const double *depth, const double *sigma,
+                         int64_t n_query, const double *query_points, const int32_t *query_indices, const double *xi, int64_t *counts,
+                         const vg_recon_outputs *out);
+/* DepthMap::generatePlane (depth_map.cpp:762-803): the depth of the plane z = 0 of the frame xi_cam_plane (HOST [6], the plane's
+ * frame in the camera's) inside the polygon (HOST [k][3] in the plane's frame, k in [3, 16]) as one map, DEVICE FP64 [y_max][x_max].
+ * A pixel is 0 / 0 where the camera refuses it, where z . ray < 1e-3, or where ray . (p_i x p_i+1) < 0 for an edge; otherwise
+ * depth |ray (t . z) / (z . ray)| and sigma 1.  cost (may be NULL) is 5 everywhere. */
+int vg_depth_generate_plane(vg_depth_fusion *h, const double *xi_cam_plane, int k, const double *polygon, double *depth, double *sigma,
+                            double *cost);
+/* analyzeError of the reference's stereo_test (stereo_test.cpp:32-84) for n maps: depth and sigma DEVICE FP64 [n][y_max][x_max]
+ * are rounded to float, truth is DEVICE float [n][v_max][u_max] (the renderer's depth buffer) read at (vConv(y), uConv(x)); a
+ * grid that leaves the image is refused.  Per pixel: Ngt counts truth != 0; a pixel with truth == 0 or depth == 0, or with a NaN
+ * in either, is skipped; otherwise Nmax counts it and dist adds truth; with diff = truth - depth in float it is an inlier unless
+ * sigma > sigma_max (the reference's 10) or |diff| > sigma, and then N counts it, err adds diff and err2 diff^2, in double.
+ * counts: HOST int64 [n][3] Ngt, Nmax, N; sums: HOST FP64 [n][3] err, err2, dist, the same bits on every run (per-workgroup
+ * partials from a fixed tree, added in block order); inliers: DEVICE u8 [n][y_max][x_max], 0 / 255, may be NULL. */
+int vg_depth_compare(vg_depth_fusion *h, int64_t n, const double *depth, const double *sigma, const float *truth, double sigma_max,
+                     int64_t *counts, double *sums, uint8_t *inliers);
 /* Host only, for the key-frame loop: Transformation::inverse (transformation.h:112-119) and inverseCompose (:90-99, a^-1 o b:
  * the pose b re-expressed in the frame a), on [t, rotvec]. */
 int vg_transform_inverse(const double *xi, double *out6);

@@ -40,7 +40,8 @@ def sources():
 # the host programs build_cli() makes: name -> source in csrc/
 CLI_SOURCES = {"calib": "calib_main.cpp", "rectify": "rectify_main.cpp", "stereo": "stereo_main.cpp",
                "motion_stereo": "motion_stereo_main.cpp", "render": "render_main.cpp", "mono_odom": "mono_odom_main.cpp",
-               "mapping": "mapping_main.cpp", "trajectory": "trajectory_main.cpp", "hough": "hough_main.cpp"}
+               "mapping": "mapping_main.cpp", "trajectory": "trajectory_main.cpp", "hough": "hough_main.cpp",
+               "stereo_accuracy": "stereo_accuracy_main.cpp"}
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 STAMP = os.path.join(LIB_DIR, "libvisgeom_amd.sources.sha256")
 _INCLUDE = None
@@ -198,12 +199,13 @@ MONO_ODOM_CLI = os.path.join(BIN_DIR, "mono_odom")
 MAPPING_CLI = os.path.join(BIN_DIR, "mapping")
 TRAJECTORY_CLI = os.path.join(BIN_DIR, "trajectory")
 HOUGH_CLI = os.path.join(BIN_DIR, "hough")
+STEREO_ACCURACY_CLI = os.path.join(BIN_DIR, "stereo_accuracy")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 
 def build_cli(verbose=False):
     """the reference's programs, host-only C++ on the C ABI: `calib file1.json [file2.json ...]`, `rectify file.json` and
-    `stereo file.json`, `motion_stereo sequence.json`, `render world.json`, `mono_odom sequence.json`, `mapping sequence.json`, `trajectory plan.json` and `hough lines.json` (all but the
+    `stereo file.json`, `motion_stereo sequence.json`, `render world.json`, `mono_odom sequence.json`, `mapping sequence.json`, `trajectory plan.json`, `hough lines.json` and `stereo_accuracy sequence.json` (all but the
     first are built against the HIP runtime)"""
     os.makedirs(BIN_DIR, exist_ok=True)
     common = ["-L" + LIB_DIR, "-lvisgeom_amd", "-Wl,-rpath," + LIB_DIR, "-Wl,-rpath," + os.path.join(ROCM, "lib")]
@@ -223,7 +225,9 @@ def build_cli(verbose=False):
             ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROCM, "include"),
              os.path.join(CSRC, CLI_SOURCES["trajectory"]), "-o", TRAJECTORY_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"],
             ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROCM, "include"),
-             os.path.join(CSRC, CLI_SOURCES["hough"]), "-o", HOUGH_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"]]
+             os.path.join(CSRC, CLI_SOURCES["hough"]), "-o", HOUGH_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"],
+            ["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROCM, "include"),
+             os.path.join(CSRC, CLI_SOURCES["stereo_accuracy"]), "-o", STEREO_ACCURACY_CLI] + common + ["-L" + os.path.join(ROCM, "lib"), "-lamdhip64"]]
     for cmd in cmds:
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

@@ -219,6 +219,9 @@ SIGNATURES = {
     "vg_depth_filter_noise": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _i64p]),
     "vg_depth_regularize": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
     "vg_depth_pack_mh": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _i64p, _vp, _vp, _vp, _vp]),
+    "vg_depth_reconstruct": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, _vp, _vp, ctypes.c_int64, _vp, _vp, _dp, _i64p, _vp]),
+    "vg_depth_generate_plane": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _vp, _vp, _vp]),
+    "vg_depth_compare": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_double, _i64p, _dp, _vp]),
     "vg_transform_inverse": (ctypes.c_int, [_dp, _dp]),
     "vg_transform_inverse_compose": (ctypes.c_int, [_dp, _dp, _dp]),
     "vg_photometric_create": (ctypes.c_int, [_vpp, ctypes.c_int, _vp, _dp, _vp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
@@ -428,6 +431,15 @@ MI_NUM_BINS, MI_VALUE_MAX, MI_ODOMETRY_DAMPING = 8, 255., 0.0002
 MI_DEFAULTS = {"function_tolerance": 1e-2, "gradient_tolerance": 1e-3, "max_iterations": 50}
 HOUGH_MAX_SIDE, HOUGH_MAX_ACC_SIDE, HOUGH_MAX_SEARCH, HOUGH_MIN_BLUR, HOUGH_MAX_BLUR = 16384, 4096, 8, 3, 15
 HOUGH_COUNTS, HOUGH_LINE, HOUGH_MAX_LINES, HOUGH_MAX_TRACE, HOUGH_OK, HOUGH_NO_END_POINTS = 6, 16, 65536, 1500, 0, 1
+RECON_QUERY_POINTS, RECON_IMAGE_VALUES, RECON_MINMAX, RECON_ALL_HYPOTHESES = 1, 2, 4, 8
+RECON_DEFAULT_VALUES, RECON_SIGMA_VALUE, RECON_QUERY_INDICES, RECON_INDEX_MAPPING = 16, 32, 64, 128
+RECON_KNOWN = 1 | 4 | 8 | 16 | 32 | 64 | 128
+RECON_MAX_POLYGON = 16
+
+
+class ReconOutputs(ctypes.Structure):
+    """struct vg_recon_outputs"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("indices", "hyp", "points", "sigma_out", "index_map", "item", "valid", "cloud")]
 DENSE_BA_MAX_FRAMES, DENSE_BA_TAIL, DENSE_BA_NONE = 8, 5, -1.
 DENSE_BA_DEFAULTS = {"sigma_grey": 5., "prior_weight": 1., "grad_thresh": 250., "max_iterations": 150, "function_tolerance": 1e-6}
 

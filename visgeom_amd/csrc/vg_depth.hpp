@@ -283,4 +283,218 @@ __global__ __launch_bounds__(kLanes) void depth_pack_mh_kernel(PackMhArgs a)
     }
 }
 
+// ---- point clouds, the plane prior and the accuracy score ------------------------------------------
+
+constexpr double kDefaultDepth = 5.;   // DEFAULT_DEPTH (stereo_misc.h)
+constexpr int kMaxPolygon = 16;
+
+enum : unsigned {   // DepthMap's reconstruct flags (depth_map.h:39-49), the values of VG_RECON_*
+    kQueryPoints = 1, kImageValues = 2, kMinMax = 4, kAllHypotheses = 8, kDefaultValues = 16, kSigmaValue = 32, kQueryIndices = 64, kIndexMapping = 128
+};
+
+struct ReconArgs {
+    double cam[6];
+    Grid g;
+    int64_t P, units;               // pixels of a plane; lanes per item: P, or the queries
+    int hyp_max, num_hyps;          // planes of a map, planes read
+    unsigned flags;
+    const double *depth, *sigma;    // [n][hyp_max][P]; sigma may be NULL when no flag reads it
+    const int32_t *query_idx;       // [units] or NULL
+    const double *query_pts;        // [units][2] or NULL
+    const double *pose;             // [n][12]: rotMat row-major, trans; or NULL
+    const unsigned *item_first;     // [n]: the entries of the items in front; NULL for one item
+    unsigned *block_counts;         // [n][blocks]
+    const unsigned *block_offsets;
+    int nb;
+    int32_t *indices, *hyp, *index_map, *item;   // the entries, each may be NULL
+    double *points, *sigma_out, *cloud;
+    uint8_t *valid;
+};
+
+// DepthMap::reconstruct(pack, flags) (depth_map.cpp:532-635) of gridDim.y maps, compacted in the reference's order: item after
+// item, the queries (or the pixels with a depth in plane 0) in order, of each its planes in ascending order.  One lane per query
+// and item holds up to kMaxHyp entries; pass 1 counts, pass 2 places (vg_compact.hpp).  No lane leaves in front of block_place.
+template <bool WRITE>
+__global__ __launch_bounds__(kLanes) void depth_reconstruct_kernel(ReconArgs a)
+{
+    const int64_t item = blockIdx.y, unit = (int64_t)blockIdx.x * kLanes + threadIdx.x;
+    const double *dep = a.depth + item * a.hyp_max * a.P;
+    int64_t pix = -1;
+    double pu = 0., pv = 0.;   // the image point the ray goes through
+    if (unit < a.units) {
+        if (a.flags & kQueryIndices) {
+            const int32_t q = a.query_idx[unit];
+            if (q >= 0 && q < a.P) pix = q;
+        } else if (a.flags & kQueryPoints) {
+            pu = a.query_pts[2 * unit];
+            pv = a.query_pts[2 * unit + 1];
+            const double fx = round((pu - a.g.u0) / a.g.scale), fy = round((pv - a.g.v0) / a.g.scale);   // xConv, yConv; in double
+            if (fx >= 0. && fx < (double)a.g.x_max && fy >= 0. && fy < (double)a.g.y_max) pix = (int64_t)fy * a.g.x_max + (int64_t)fx;
+        } else if (dep[unit] >= kMinDepth) {   // getIdxVec()
+            pix = unit;
+        }
+    }
+    if (pix >= 0 && !((a.flags & kQueryPoints) && !(a.flags & kQueryIndices))) {
+        pu = (double)((int)(pix % a.g.x_max) * a.g.scale + a.g.u0);
+        pv = (double)((int)(pix / a.g.x_max) * a.g.scale + a.g.v0);
+    }
+    double d[kMaxHyp];
+    unsigned below = 0, total = 0, filled = 0;   // filled: the planes that hold a depth of their own
+#pragma unroll
+    for (int h = 0; h < kMaxHyp; h++) {
+        d[h] = (pix >= 0 && h < a.num_hyps) ? dep[h * a.P + pix] : 0.;
+        if (d[h] >= kMinDepth) {
+            filled |= 1u << h;
+        } else {
+            d[h] = (h == 0 && pix >= 0 && (a.flags & kDefaultValues)) ? kDefaultDepth : 0.;
+        }
+        const unsigned long long ball = __ballot(d[h] >= kMinDepth);
+        below += vgc::lanes_below(ball);
+        total += (unsigned)__popcll(ball);
+    }
+    int64_t pos = vgc::block_place<WRITE, kLanes>(below, total, item * a.nb + blockIdx.x, a.block_counts, a.block_offsets);
+    if (!WRITE || pix < 0) return;
+    if (a.item_first) pos += a.item_first[item];
+    const bool minmax = (a.flags & kMinMax) != 0;
+    double X[3], dir[3] = {0., 0., 0.};
+    const bool seen = eucm_reconstruct(a.cam, pu, pv, X);
+    if (seen && a.cloud) {
+        const double nrm = sqrt(dot3(X, X));
+        for (int i = 0; i < 3; i++) dir[i] = X[i] / nrm;   // normalized()
+    }
+    const double *R = a.pose ? a.pose + 12 * item : nullptr;
+    const double *sig = a.sigma ? a.sigma + item * a.hyp_max * a.P : nullptr;
+#pragma unroll
+    for (int h = 0; h < kMaxHyp; h++) {
+        if (!(d[h] >= kMinDepth)) continue;
+        const double s = !sig ? 0. : (filled >> h & 1u) ? sig[h * a.P + pix] : kDefaultSigma;
+        if (a.indices) a.indices[pos] = (int32_t)pix;
+        if (a.hyp) a.hyp[pos] = h;
+        if (a.index_map) a.index_map[pos] = (int32_t)unit;
+        if (a.item) a.item[pos] = (int32_t)item;
+        if (a.valid) a.valid[pos] = seen ? 1 : 0;
+        if (a.sigma_out) a.sigma_out[pos] = s;
+        if (a.points) {
+            a.points[2 * pos] = pu;
+            a.points[2 * pos + 1] = pv;
+        }
+        if (a.cloud) {
+            const int m = minmax ? 2 : 1;
+            for (int e = 0; e < m; e++) {
+                const double range = !minmax ? d[h] : e == 0 ? dmax(d[h] - 3 * s, kMinDepth) : d[h] + 3 * s;
+                double c[3] = {0., 0., 0.}, w[3];
+                if (seen) {
+                    for (int i = 0; i < 3; i++) c[i] = dir[i] * range;
+                    if (R) {   // Transformation::transform
+                        mat_vec(R, c, w);
+                        for (int i = 0; i < 3; i++) c[i] = w[i] + R[9 + i];
+                    }
+                }
+                for (int i = 0; i < 3; i++) a.cloud[(pos * m + e) * 3 + i] = c[i];
+            }
+        }
+        pos++;
+    }
+}
+
+struct PlaneArgs {
+    double cam[6];
+    Grid g;
+    double t[3], z[3];                // the plane's origin and z axis in the camera frame
+    double poly[kMaxPolygon][3];      // the polygon in the camera frame
+    int k;
+    double *depth, *sigma, *cost;     // [P]; cost may be NULL
+};
+
+// DepthMap::generatePlane (depth_map.cpp:762-803): one lane per pixel
+__global__ __launch_bounds__(kLanes) void depth_generate_plane_kernel(PlaneArgs a)
+{
+    const int64_t P = (int64_t)a.g.x_max * a.g.y_max, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
+    if (pix >= P) return;
+    const int x = (int)(pix % a.g.x_max), y = (int)(pix / a.g.x_max);
+    double vec[3], d = 0., s = 0.;
+    if (eucm_reconstruct(a.cam, (double)(x * a.g.scale + a.g.u0), (double)(y * a.g.scale + a.g.v0), vec)) {
+        const double zvec = dot3(a.z, vec);
+        if (!(zvec < 1e-3)) {
+            bool inside = true;
+            for (int i = 0; i < a.k && inside; i++) {
+                const double *p = a.poly[i], *q = a.poly[i + 1 == a.k ? 0 : i + 1];
+                const double nrm[3] = {p[1] * q[2] - p[2] * q[1], p[2] * q[0] - p[0] * q[2], p[0] * q[1] - p[1] * q[0]};
+                if (dot3(vec, nrm) < 0) inside = false;
+            }
+            if (inside) {
+                const double alpha = dot3(a.t, a.z) / zvec;
+                for (int i = 0; i < 3; i++) vec[i] *= alpha;
+                d = sqrt(dot3(vec, vec));
+                s = 1.;
+            }
+        }
+    }
+    a.depth[pix] = d;
+    a.sigma[pix] = s;
+    if (a.cost) a.cost[pix] = kDefaultCost;
+}
+
+struct CompareArgs {
+    Grid g;
+    int u_max, v_max;
+    int64_t P;
+    int nb;
+    double sigma_max;
+    const double *depth, *sigma;    // [n][P]
+    const float *truth;             // [n][v_max][u_max]
+    double *partial;                // [n][nb][kCompareSums] of every workgroup
+    uint8_t *inliers;               // [n][P] or NULL
+};
+
+constexpr int kCompareSums = 6;   // err, err2, dist, then Ngt, Nmax, N: counts of at most 2^28 pixels are exact in FP64
+
+// analyzeError (stereo_test.cpp:32-84) per pixel; the sums and the counts of a workgroup leave through block_sums' fixed tree: no
+// atomics (three counters of one item would take 12 same-address atomics per workgroup)
+__global__ __launch_bounds__(kLanes) void depth_compare_kernel(CompareArgs a)
+{
+    const int64_t item = blockIdx.y, pix = (int64_t)blockIdx.x * kLanes + threadIdx.x;
+    double sums[kCompareSums] = {0., 0., 0., 0., 0., 0.};
+    if (pix < a.P) {
+        const int x = (int)(pix % a.g.x_max), y = (int)(pix / a.g.x_max);
+        const float truth = a.truth[(item * a.v_max + (y * a.g.scale + a.g.v0)) * a.u_max + (x * a.g.scale + a.g.u0)];
+        const float d = (float)a.depth[item * a.P + pix], s = (float)a.sigma[item * a.P + pix];   // toMat, sigmaToMat
+        bool inlier = false;
+        if (truth != 0.f) sums[3] = 1.;
+        if (!(truth == 0.f || d == 0.f) && !(truth != truth || d != d)) {
+            sums[4] = 1.;
+            sums[2] = (double)truth;
+            const float diff = truth - d;
+            if (!((double)s > a.sigma_max || fabsf(diff) > s)) {
+                inlier = true;
+                sums[5] = 1.;
+                sums[0] = (double)diff;
+                sums[1] = (double)diff * (double)diff;
+            }
+        }
+        if (a.inliers) a.inliers[item * a.P + pix] = inlier ? 255 : 0;
+    }
+    block_sums<kCompareSums, kLanes>(sums, a.partial + (item * a.nb + blockIdx.x) * kCompareSums);
+}
+
+// the partials of an item added in block order: workgroup `item` stages kLanes blocks at a time in LDS with coalesced loads, and
+// lane k < kCompareSums walks column k of the stage, eight loads ahead of its chain of dependent adds
+__global__ __launch_bounds__(kLanes) void depth_compare_sum_kernel(const double *partial, int nb, double *sums)
+{
+    __shared__ double stage[kLanes * kCompareSums];
+    const double *p = partial + (int64_t)blockIdx.x * nb * kCompareSums;
+    double s = 0.;
+    for (int first = 0; first < nb; first += kLanes) {
+        const int m = min(kLanes, nb - first);
+        for (int i = threadIdx.x; i < kCompareSums * m; i += kLanes) stage[i] = p[kCompareSums * (int64_t)first + i];
+        __syncthreads();
+        if (threadIdx.x < kCompareSums) {
+#pragma unroll 8
+            for (int b = 0; b < m; b++) s += stage[kCompareSums * b + threadIdx.x];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < kCompareSums) sums[blockIdx.x * kCompareSums + threadIdx.x] = s;
+}
+
 }  // namespace vgd

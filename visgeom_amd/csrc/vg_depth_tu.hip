@@ -4,7 +4,8 @@
 // A vg_depth_fusion handle owns the scratch of its three operations: the warp's z-buffer and winner buffer (12 bytes per
 // depth pixel and item, all ones between calls: the gather kernel restores what it read), the per-item poses with the warp's
 // counters in one pinned and one device array, the counters of merge and the noise filter, and the copy the noise filter
-// reads when it runs in place, and the block counts of the multi-hypothesis pack.  Buffers only grow.
+// reads when it runs in place, the block counts of the multi-hypothesis pack, and of the point cloud (vg_depth_reconstruct) its
+// block counts per item, the items' offsets and poses, and of vg_depth_compare the partial sums per workgroup.  Buffers only grow.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -28,6 +29,14 @@ struct vg_depth_fusion : vgi::HandleBase {
     vgi::Grow<unsigned> d_winner;
     vgi::Grow<double> d_copy;   // [2][n][P]
     vgi::PackScratch pack;   // of the multi-hypothesis pack: per block of 256 pixels; one total
+    int u_max = 0, v_max = 0;               // the image the grid samples: the truth of vg_depth_compare
+    vgi::PackScratch recon;                 // of vg_depth_reconstruct: counts [item][block], one total per item
+    vgi::Grow<unsigned> d_first;            // [n]: the entries of the items in front
+    vgi::GrowPinned<unsigned> h_first;
+    vgi::Grow<double> d_pose;               // [n][12]
+    vgi::GrowPinned<double> h_pose;
+    vgi::Grow<double> d_partial, d_sums;    // of vg_depth_compare: [n][blocks][6], [n][6]: three sums, three counts
+    vgi::GrowPinned<double> h_sums;
 #ifdef VG_DEPTH_WARP_STORE
     vgi::Grow<int> d_src_target;
     vgi::Grow<double> d_src_dist;
@@ -78,6 +87,8 @@ int vg_depth_fusion_create(vg_depth_fusion **out, int device, void *hip_stream, 
     for (int i = 0; i < 6; i++) s->cam[i] = eucm[i];
     s->g = vgd::Grid{p.scale, p.u0, p.v0, x_max, y_max};
     s->P = (int64_t)x_max * y_max;
+    s->u_max = p.u_max;
+    s->v_max = p.v_max;
     if (const int rc = s->open(device, hip_stream, "depth fusion")) return rc;
     *out = s.release();
     return VG_OK;
@@ -267,6 +278,182 @@ int vg_depth_pack_mh(vg_depth_fusion *s, int hyp_max, const double *depth, const
     hipLaunchKernelGGL((vgd::depth_pack_mh_kernel<true>), dim3(nb), dim3(vgd::kLanes), 0, s->stream, a);
     VG_HIP(hipGetLastError());
     return call.finish();
+}
+
+int vg_depth_reconstruct(vg_depth_fusion *s, int64_t n, int hyp_max, uint32_t flags, const double *depth, const double *sigma, int64_t n_query,
+                         const double *query_points, const int32_t *query_indices, const double *xi, int64_t *counts, const vg_recon_outputs *out)
+{
+    // what needs no handle is checked first, the handle next
+    if (const int rc = vgi::check_items(n, 0, "item")) return rc;
+    if (flags & VG_RECON_IMAGE_VALUES) return fail(VG_ERR_INVALID_ARGUMENT, "IMAGE_VALUES is not provided (the reference asserts on it)");
+    constexpr uint32_t known = VG_RECON_QUERY_POINTS | VG_RECON_MINMAX | VG_RECON_ALL_HYPOTHESES | VG_RECON_DEFAULT_VALUES | VG_RECON_SIGMA_VALUE |
+                               VG_RECON_QUERY_INDICES | VG_RECON_INDEX_MAPPING;
+    if (flags & ~known) return fail(VG_ERR_INVALID_ARGUMENT, "unknown reconstruct flags");
+    if (hyp_max < 1 || hyp_max > vgd::kMaxHyp) return fail(VG_ERR_INVALID_ARGUMENT, "hyp_max must be in [1, 8]");
+    if (n > 0 && (!depth || !counts)) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n > 0 && (flags & (VG_RECON_SIGMA_VALUE | VG_RECON_MINMAX)) && !sigma) return fail(VG_ERR_INVALID_ARGUMENT, "SIGMA_VALUE and MINMAX need the sigma planes");
+    const bool by_index = (flags & VG_RECON_QUERY_INDICES) != 0, by_point = !by_index && (flags & VG_RECON_QUERY_POINTS);
+    if (by_index || by_point) {
+        if (n_query < 0 || n_query >= (int64_t)1 << 31) return fail(VG_ERR_INVALID_ARGUMENT, "the query count must be in [0, 2^31)");
+        if (n_query > 0 && !(by_index ? (const void *)query_indices : (const void *)query_points))
+            return fail(VG_ERR_INVALID_ARGUMENT, "the query flag is set but its array is NULL");
+    }
+    const vg_recon_outputs none = {};
+    const vg_recon_outputs &o = out ? *out : none;
+    if (o.sigma_out && !(flags & VG_RECON_SIGMA_VALUE)) return fail(VG_ERR_INVALID_ARGUMENT, "sigma_out needs SIGMA_VALUE");
+    if (o.index_map && !((flags & VG_RECON_INDEX_MAPPING) && (by_index || by_point)))
+        return fail(VG_ERR_INVALID_ARGUMENT, "index_map needs INDEX_MAPPING and a query");
+    if (xi && !vgsh::finite_n(xi, 6 * (int)n)) return fail(VG_ERR_INVALID_ARGUMENT, "the poses must be finite");
+    if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "depth fusion handle is NULL");
+    if (n == 0) return VG_OK;
+    const int64_t units = (by_index || by_point) ? n_query : s->P;
+    const int num_hyps = (flags & VG_RECON_ALL_HYPOTHESES) ? hyp_max : 1;
+    if (n * units * num_hyps >= (int64_t)1 << 31) return fail(VG_ERR_INVALID_ARGUMENT, "the entries could reach 2^31: fewer items or queries per call");
+    for (int64_t k = 0; k < n; k++) counts[k] = 0;
+    if (units == 0) return VG_OK;
+    const unsigned nb = blocks_of(units, vgd::kLanes);
+    vgd::ReconArgs a = {};
+    for (int i = 0; i < 6; i++) a.cam[i] = s->cam[i];
+    a.g = s->g;
+    a.P = s->P;
+    a.units = units;
+    a.hyp_max = hyp_max;
+    a.num_hyps = num_hyps;
+    a.flags = flags;
+    a.depth = depth;
+    a.sigma = sigma;
+    a.query_idx = by_index ? query_indices : nullptr;
+    a.query_pts = by_point ? query_points : nullptr;
+    a.nb = (int)nb;
+    const dim3 grid(nb, (unsigned)n), block(vgd::kLanes);
+    {   // the count: the entries of every block, scanned per item
+        vgi::Call call(s);
+        if (const int rc = call.begin()) return rc;
+        if (const int rc = s->recon.grow((size_t)n * nb, (size_t)n, "the reconstruct block counts")) return rc;
+        a.block_counts = s->recon.counts;
+        a.block_offsets = s->recon.offsets;
+        hipLaunchKernelGGL((vgd::depth_reconstruct_kernel<false>), grid, block, 0, s->stream, a);
+        hipLaunchKernelGGL(vgc::scan_block_counts_items_kernel<vgd::kLanes>, dim3((unsigned)n), block, 0, s->stream,
+                           (const unsigned *)s->recon.counts.get(), s->recon.offsets.get(), (int)nb, s->recon.totals.get());
+        VG_HIP(hipGetLastError());
+        if (const int rc = s->recon.fetch(s->stream, (size_t)n)) return rc;
+        if (const int rc = call.finish()) return rc;
+    }
+    int64_t total = 0;
+    for (int64_t k = 0; k < n; k++) total += counts[k] = (int64_t)s->recon.h_totals.get()[k];
+    if (total == 0 || !(o.indices || o.hyp || o.points || o.sigma_out || o.index_map || o.item || o.valid || o.cloud)) return VG_OK;
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    if (n > 1) {
+        if (const int rc = s->d_first.grow((size_t)n, "the reconstruct item offsets")) return rc;
+        if (const int rc = s->h_first.grow((size_t)n, "the reconstruct item offsets")) return rc;
+        unsigned run = 0;
+        for (int64_t k = 0; k < n; k++) {
+            s->h_first.get()[k] = run;
+            run += (unsigned)counts[k];
+        }
+        VG_HIP(hipMemcpyAsync(s->d_first, s->h_first, (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice, s->stream));
+        a.item_first = s->d_first;
+    }
+    if (xi) {
+        if (const int rc = s->d_pose.grow((size_t)n * 12, "the reconstruct poses")) return rc;
+        if (const int rc = s->h_pose.grow((size_t)n * 12, "the reconstruct poses")) return rc;
+        for (int64_t k = 0; k < n; k++) {
+            double *p = s->h_pose.get() + 12 * k;
+            vgth::rotation(xi + 6 * k, p);
+            for (int i = 0; i < 3; i++) p[9 + i] = xi[6 * k + i];
+        }
+        VG_HIP(hipMemcpyAsync(s->d_pose, s->h_pose, (size_t)n * 12 * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        a.pose = s->d_pose;
+    }
+    a.indices = o.indices;
+    a.hyp = o.hyp;
+    a.index_map = o.index_map;
+    a.item = o.item;
+    a.points = o.points;
+    a.sigma_out = o.sigma_out;
+    a.cloud = o.cloud;
+    a.valid = o.valid;
+    hipLaunchKernelGGL((vgd::depth_reconstruct_kernel<true>), grid, block, 0, s->stream, a);
+    VG_HIP(hipGetLastError());
+    return call.finish();
+}
+
+int vg_depth_generate_plane(vg_depth_fusion *s, const double *xi_cam_plane, int k, const double *polygon, double *depth, double *sigma, double *cost)
+{
+    if (k < 3 || k > vgd::kMaxPolygon) return fail(VG_ERR_INVALID_ARGUMENT, "the polygon must have 3 to 16 vertices");
+    if (!xi_cam_plane || !polygon || !depth || !sigma) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!vgsh::finite_n(xi_cam_plane, 6) || !vgsh::finite_n(polygon, 3 * k)) return fail(VG_ERR_INVALID_ARGUMENT, "the pose and the polygon must be finite");
+    if (!s) return fail(VG_ERR_INVALID_ARGUMENT, "depth fusion handle is NULL");
+    const size_t bytes = (size_t)s->P * sizeof(double);
+    const void *const p[3] = {depth, sigma, cost};
+    if (any_overlap(p, cost ? 3 : 2, bytes)) return fail(VG_ERR_INVALID_ARGUMENT, "the outputs overlap each other");
+    vgd::PlaneArgs a = {};
+    double R[9];
+    vgth::rotation(xi_cam_plane, R);
+    for (int i = 0; i < 6; i++) a.cam[i] = s->cam[i];
+    a.g = s->g;
+    for (int i = 0; i < 3; i++) {
+        a.t[i] = xi_cam_plane[i];
+        a.z[i] = R[3 * i + 2];   // rotMat().col(2)
+    }
+    for (int j = 0; j < k; j++) {   // Transformation::transform
+        double w[3];
+        vgs::mat_vec(R, polygon + 3 * j, w);
+        for (int i = 0; i < 3; i++) a.poly[j][i] = w[i] + xi_cam_plane[i];
+    }
+    a.k = k;
+    a.depth = depth;
+    a.sigma = sigma;
+    a.cost = cost;
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    hipLaunchKernelGGL(vgd::depth_generate_plane_kernel, dim3(blocks_of(s->P, vgd::kLanes)), dim3(vgd::kLanes), 0, s->stream, a);
+    VG_HIP(hipGetLastError());
+    return call.finish();
+}
+
+int vg_depth_compare(vg_depth_fusion *s, int64_t n, const double *depth, const double *sigma, const float *truth, double sigma_max, int64_t *counts,
+                     double *sums, uint8_t *inliers)
+{
+    if (const int rc = check_call(s, n)) return rc;
+    if (n == 0) return VG_OK;
+    if (!depth || !sigma || !truth || !counts || !sums) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (std::isnan(sigma_max)) return fail(VG_ERR_INVALID_ARGUMENT, "sigma_max is NaN");
+    const vgd::Grid &g = s->g;   // uConv / vConv of every map pixel must lie in the image the truth covers
+    if (g.u0 < 0 || g.v0 < 0 || (int64_t)(g.x_max - 1) * g.scale + g.u0 >= s->u_max || (int64_t)(g.y_max - 1) * g.scale + g.v0 >= s->v_max)
+        return fail(VG_ERR_INVALID_ARGUMENT, "the depth grid leaves the uMax x vMax image: no truth to compare with");
+    const unsigned nb = blocks_of(s->P, vgd::kLanes);
+    vgi::Call call(s);
+    if (const int rc = call.begin()) return rc;
+    constexpr int K = vgd::kCompareSums;
+    if (const int rc = s->d_partial.grow((size_t)n * nb * K, "the comparison's partial sums")) return rc;
+    if (const int rc = s->d_sums.grow((size_t)n * K, "the comparison's sums")) return rc;
+    if (const int rc = s->h_sums.grow((size_t)n * K, "the comparison's sums")) return rc;
+    vgd::CompareArgs a = {};
+    a.g = g;
+    a.u_max = s->u_max;
+    a.v_max = s->v_max;
+    a.P = s->P;
+    a.nb = (int)nb;
+    a.sigma_max = sigma_max;
+    a.depth = depth;
+    a.sigma = sigma;
+    a.truth = truth;
+    a.partial = s->d_partial;
+    a.inliers = inliers;
+    hipLaunchKernelGGL(vgd::depth_compare_kernel, dim3(nb, (unsigned)n), dim3(vgd::kLanes), 0, s->stream, a);
+    hipLaunchKernelGGL(vgd::depth_compare_sum_kernel, dim3((unsigned)n), dim3(vgd::kLanes), 0, s->stream, (const double *)s->d_partial.get(), (int)nb,
+                       s->d_sums.get());
+    VG_HIP(hipGetLastError());
+    VG_HIP(hipMemcpyAsync(s->h_sums, s->d_sums, (size_t)n * K * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (const int rc = call.finish()) return rc;
+    for (int64_t k = 0; k < n; k++)
+        for (int i = 0; i < 3; i++) {
+            sums[3 * k + i] = s->h_sums.get()[K * k + i];
+            counts[3 * k + i] = (int64_t)s->h_sums.get()[K * k + 3 + i];   // whole numbers below 2^28: exact
+        }
+    return VG_OK;
 }
 
 int vg_transform_inverse(const double *xi, double *out6)
