@@ -79,8 +79,9 @@ def _cast(acc, acc_cam, A, B, C):
     return int(inside.sum()), int((~ok).sum()), int((ok & ~inside).sum())
 
 
-def vote(img, cam, acc_cam, prm):
-    """(accumulator int32 [acc_h, acc_w], counts int64 [6]) of one image (.cpp:363-420)"""
+def vote(img, cam, acc_cam, prm, stats=None):
+    """(accumulator int32 [acc_h, acc_w], counts int64 [6]) of one image (.cpp:363-420).  A dict given as `stats` is filled with
+    the (cast, failed, outside) counts of the first and of the antipode votes and the number of antipode votes tried."""
     w, h = acc_size(acc_cam)
     acc = np.zeros((h, w), dtype=np.int32)
     kx, ky = sobel(img)
@@ -111,6 +112,8 @@ def vote(img, cam, acc_cam, prm):
         anti = C * C / (A * A + B * B) < prm["horizon_ratio"]   # 0 / 0 is NaN: no antipode vote
         c2, f2, o2 = _cast(acc, acc_cam, -A[anti], -B[anti], -C[anti])
     counts[2:] = (c1, c2, f1 + f2, o1 + o2)
+    if stats is not None:
+        stats.update(first=(c1, f1, o1), antipode=(c2, f2, o2), antipode_tried=int(anti.sum()))
     return acc, counts
 
 
@@ -147,9 +150,14 @@ def blur(acc, prm):
     return a
 
 
-def maxima(b, acc_cam, prm):
-    """the kept bins of the blurred accumulator in raster order (.cpp:458-482): [(centroid u, v, value, ABC)]"""
+def maxima(b, acc_cam, prm, stats=None):
+    """the kept bins of the blurred accumulator in raster order (.cpp:458-482): [(centroid u, v, value, ABC)].  A dict given
+    as `stats` is filled with why candidates were dropped: "window" bins passed the (2 s + 1)^2 test, of which
+    "not_reconstructed" failed the accumulator camera's reconstruction and "behind" gave n[2] < 0; "bins" lists the raster
+    positions v * acc_w + u of the kept ones."""
     s = prm["search_size"]
+    if stats is not None:
+        stats.update(window=0, not_reconstructed=0, behind=0, bins=[])
     h, w = b.shape
     out = []
     vs, us = np.nonzero(~(b.astype(np.float64) < prm["acc_thresh"]))
@@ -170,8 +178,14 @@ def maxima(b, acc_cam, prm):
                 vacc += dv * x
         cu, cv = u + fdiv(uacc, nacc), v + fdiv(vacc, nacc)
         ABC = reconstruct(acc_cam, cu, cv)
+        if stats is not None:
+            stats["window"] += 1
+            stats["not_reconstructed"] += ABC is None
+            stats["behind"] += ABC is not None and ABC[2] < 0
         if ABC is None or ABC[2] < 0:   # deviation: the reference goes on with an unset vector when the reconstruction fails
             continue
+        if stats is not None:
+            stats["bins"].append(v * w + u)
         out.append((cu, cv, val, ABC))
     return out
 
@@ -294,13 +308,13 @@ def trace(poly, pt4, max_steps=MAX_TRACE):
     return np.array(out, dtype=np.int32).reshape(-1, 2)
 
 
-def detect(img, cam, acc_cam, prm):
-    """one image through every stage: dict(acc, counts, blur, lines float64 [k, 16], status int32 [k])"""
+def detect(img, cam, acc_cam, prm, stats=None):
+    """one image through every stage: dict(acc, counts, blur, lines float64 [k, 16], status int32 [k]); stats: see maxima"""
     height, width = img.shape
-    acc, counts = vote(img, cam, acc_cam, prm)
+    acc, counts = vote(img, cam, acc_cam, prm, stats)
     b = blur(acc, prm)
     lines, status = [], []
-    for cu, cv, val, ABC in maxima(b, acc_cam, prm):
+    for cu, cv, val, ABC in maxima(b, acc_cam, prm, stats):
         nrm = math.sqrt(ABC[0] * ABC[0] + ABC[1] * ABC[1] + ABC[2] * ABC[2])
         poly = polynomial(cam, ABC)
         pts = end_points(width, height, cam, ABC, poly)
