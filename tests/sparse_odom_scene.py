@@ -46,17 +46,17 @@ def sample_table(points, m, seed=SEED):
     return np.stack([rng.choice(m, size=points, replace=False) for _ in range(sr.RANSAC_ITERATIONS)]).astype(np.int32)
 
 
-def points_set():
-    """dict(x1, x2 [120][3], p2 [120][2], size [120], xi_true, xi_odom, wrong [25] indices, far [6] indices, samples2, samples3)"""
-    if "points" not in _CACHE:
+def points_set(n=120):
+    """dict(x1, x2 [n][3], p2 [n][2], size [n], xi_true, xi_odom, wrong indices, far indices, samples2, samples3): of 120 points
+    25 are wrong and 6 far; another n keeps the construction and the shares (the sample tables need n >= 3)"""
+    if ("points", n) not in _CACHE:
         rng = np.random.default_rng(SEED)
-        n = 120
         xi_true = np.asarray(STEPS[0], float)
         xi_odom = xi_true * ODOM_FACTORS[0]
         xc = sr.camera_motion(np.asarray(XI_BASE_CAM, float), xi_true)
         R, t = pr.rotation_matrix(xc[3:]), xc[:3]
-        far = np.arange(100, 106)
-        wrong = np.arange(10, 35)
+        far = np.arange(n * 100 // 120, n * 106 // 120)
+        wrong = np.arange(n * 10 // 120, n * 35 // 120)
         p1 = np.stack([rng.uniform(15, W - 15, n), rng.uniform(15, H - 15, n)], 1)
         d1, _ = pr.reconstruct(CAM, p1[:, 0], p1[:, 1])
         depth = rng.uniform(0.8, 3.0, n)
@@ -69,10 +69,11 @@ def points_set():
         p2 = p2 + noise
         p2[wrong] = np.stack([rng.uniform(15, W - 15, len(wrong)), rng.uniform(15, H - 15, len(wrong))], 1)
         x2, _ = pr.reconstruct(CAM, p2[:, 0], p2[:, 1])
-        _CACHE["points"] = {"x1": np.ascontiguousarray(d1), "x2": np.ascontiguousarray(x2), "p2": np.ascontiguousarray(p2), "size": np.ones(n),
-                            "xi_true": xi_true, "xi_odom": xi_odom, "wrong": wrong, "far": far,
-                            "samples2": sample_table(2, n), "samples3": sample_table(3, n)}
-    return _CACHE["points"]
+        _CACHE["points", n] = {"x1": np.ascontiguousarray(d1), "x2": np.ascontiguousarray(x2), "p2": np.ascontiguousarray(p2), "size": np.ones(n),
+                               "xi_true": xi_true, "xi_odom": xi_odom, "wrong": wrong, "far": far}
+        if n >= 3:
+            _CACHE["points", n].update(samples2=sample_table(2, n), samples3=sample_table(3, n))
+    return _CACHE["points", n]
 
 
 def detection(k, max_features):
@@ -148,6 +149,6 @@ def short_solves(points, iterations=3):
     return _CACHE[key]
 
 
-def clean_block():
-    """indices of the 95 correspondences that were not replaced"""
-    return np.setdiff1d(np.arange(120), points_set()["wrong"])
+def clean_block(n=120):
+    """indices of the correspondences that were not replaced: 95 of 120"""
+    return np.setdiff1d(np.arange(n), points_set(n)["wrong"])
