@@ -35,7 +35,12 @@ extern "C" {
 enum vg_model {
     VG_MODEL_EUCM = 0, /* [alpha,beta,fu,fv,u0,v0]          include/projection/eucm.h:29-226 */
     VG_MODEL_UCM = 1,  /* [xi,fu,fv,u0,v0]                  include/projection/ucm.h:32-197  */
-    VG_MODEL_MEI = 2   /* [xi,k1,k2,k3,k4,k5,fu,fv,u0,v0]   include/projection/mei.h:29-285  */
+    VG_MODEL_MEI = 2,  /* [xi,k1,k2,k3,k4,k5,fu,fv,u0,v0]   include/projection/mei.h:29-285  */
+    /* 3 is unassigned: every entry refuses it as an unknown model.  The two below are not in the reference (DESIGN.md section
+     * 5.26); the calibration, pose refinement and rectification entries take them, the localization costs of section 6, the
+     * trajectory planner and the image pipelines do not (VG_ERR_INVALID_ARGUMENT). */
+    VG_MODEL_KB = 4,   /* [k1,k2,k3,k4,fu,fv,u0,v0]         Kannala-Brandt (OpenCV "fisheye", Kalibr "equidistant") */
+    VG_MODEL_DS = 5    /* [xi,alpha,fu,fv,u0,v0]            double sphere (Usenko et al. 2018) */
 };
 
 /* enum TransformationStatus, include/calibration/calib_cost_functions.h:25 */

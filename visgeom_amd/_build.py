@@ -26,7 +26,8 @@ PRODUCTION_LIB = os.path.join(LIB_DIR, "production", "libvisgeom_amd.so")
 
 def sources():
     """the translation units of the library: every .hip file of csrc/ (vg_problem_tu: error string, debug hooks, problem
-    assembly; vg_emit_tu: chain prep + emit launches; vg_block_tu: per-block drop-in and block groups; vg_measure_tu: roofline
+    assembly; vg_emit_tu: chain prep + emit launches; vg_emit_models_tu: the emit launches of the Kannala-Brandt and double-sphere
+    cameras; vg_block_tu: per-block drop-in and block groups; vg_measure_tu: roofline
     helpers; vg_gram_tu: normal equations; vg_solver_tu: LM / Schur + communicator; vg_refine_tu: per-image pose LM; vg_frontend_tu: calibration JSON;
     vg_local_tu: localization costs; vg_rectify_tu: rectification maps and remap;
     vg_corners_tu: checkerboard corner detection; vg_stereo_tu: fisheye semi-global stereo; vg_motion_tu: motion stereo;

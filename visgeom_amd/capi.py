@@ -16,8 +16,9 @@ _vp = ctypes.c_void_p
 _vpp = ctypes.POINTER(ctypes.c_void_p)
 
 MODEL_EUCM, MODEL_UCM, MODEL_MEI = 0, 1, 2
-MODELS = {"eucm": MODEL_EUCM, "ucm": MODEL_UCM, "mei": MODEL_MEI}
-NUM_INTRINSICS = {MODEL_EUCM: 6, MODEL_UCM: 5, MODEL_MEI: 10}
+MODEL_KB, MODEL_DS = 4, 5   # Kannala-Brandt and double sphere (not in the reference); 3 is unassigned and refused
+MODELS = {"eucm": MODEL_EUCM, "ucm": MODEL_UCM, "mei": MODEL_MEI, "kb": MODEL_KB, "ds": MODEL_DS}
+NUM_INTRINSICS = {MODEL_EUCM: 6, MODEL_UCM: 5, MODEL_MEI: 10, MODEL_KB: 8, MODEL_DS: 6}
 TRANSFORM_DIRECT, TRANSFORM_INVERSE = 0, 1
 MAX_CHAIN = 5
 DOUBLE_BIG = 1e15

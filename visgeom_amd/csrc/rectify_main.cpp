@@ -3,7 +3,7 @@
 // builds the pinhole -> camera maps once (vg_rectify_map) and remaps every listed image through them (vg_remap, same-size
 // images batched into one launch), writing img_<k>.pgm into the working directory.
 // JSON: camera_params, pinhole_params [width, height, u0, v0, f], xi_eucm_pinhole (any transformFromData form), image_names,
-// and optionally "camera_model": "eucm" (the default, as in the reference) | "ucm" | "mei".
+// and optionally "camera_model": "eucm" (the default, as in the reference) | "ucm" | "mei" | "kb" | "ds".
 // Images are binary 8-bit PGM (P5) in and out: the project has no image library (the reference reads and writes PNG through
 // OpenCV).  Everything is read and checked before the GPU is touched.
 // Host-only program on top of the C ABI (include/visgeom_amd.h); links libvisgeom_amd.so and the HIP runtime for the buffers.
@@ -38,7 +38,7 @@ int main(int argc, char **argv)
         const vgjson::Value root = vgjson::parse_file(argv[1]);
         if (root.has("camera_model")) {
             const std::string m = root.at("camera_model").as_string();
-            model = m == "eucm" ? VG_MODEL_EUCM : m == "ucm" ? VG_MODEL_UCM : m == "mei" ? VG_MODEL_MEI : -1;
+            model = m == "eucm" ? VG_MODEL_EUCM : m == "ucm" ? VG_MODEL_UCM : m == "mei" ? VG_MODEL_MEI : m == "kb" ? VG_MODEL_KB : m == "ds" ? VG_MODEL_DS : -1;
             if (model < 0) throw std::runtime_error("unknown camera_model \"" + m + "\"");
         }
         intr = root.at("camera_params").as_vector();

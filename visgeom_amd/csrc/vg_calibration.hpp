@@ -86,6 +86,47 @@ inline bool reconstruct_point(int model, const double *p, const double *uv, doub
         X[0] = xn; X[1] = yn; X[2] = num / denom;
         return true;
     }
+    if (model == VG_MODEL_KB) {
+        // d(theta) = rd by Newton from theta = rd; fails when it does not settle in 20 steps, when d' <= 0 on the way or when
+        // theta leaves [0, pi].  The ray is a unit vector
+        const double k1 = p[0], k2 = p[1], k3 = p[2], k4 = p[3], fu = p[4], fv = p[5], u0 = p[6], v0 = p[7];
+        const double mx = (uv[0] - u0) / fu, my = (uv[1] - v0) / fv;
+        const double rd = std::hypot(mx, my);
+        if (rd == 0.) {
+            X[0] = 0.; X[1] = 0.; X[2] = 1.;
+            return true;
+        }
+        double theta = rd;
+        bool settled = false;
+        for (int it = 0; it < 20 && !settled; it++) {
+            const double t2 = theta * theta;
+            const double d = theta * (1. + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))));
+            const double dp = 1. + t2 * (3. * k1 + t2 * (5. * k2 + t2 * (7. * k3 + t2 * (9. * k4))));
+            if (!(dp > 0.)) return false;
+            const double step = (d - rd) / dp;
+            theta -= step;
+            if (!(theta >= 0. && theta <= M_PI)) return false;
+            settled = std::fabs(step) <= 1e-12 * theta;  // Newton is quadratic: what is left after this step is below one ulp
+        }
+        if (!settled) return false;
+        {   // the polynomial must not have folded over at the root either
+            const double t2 = theta * theta;
+            if (!(1. + t2 * (3. * k1 + t2 * (5. * k2 + t2 * (7. * k3 + t2 * (9. * k4)))) > 0.)) return false;
+        }
+        const double sc = std::sin(theta) / rd;
+        X[0] = sc * mx; X[1] = sc * my; X[2] = std::cos(theta);
+        return true;
+    }
+    if (model == VG_MODEL_DS) {
+        const double xi = p[0], alpha = p[1], fu = p[2], fv = p[3], u0 = p[4], v0 = p[5];
+        const double mx = (uv[0] - u0) / fu, my = (uv[1] - v0) / fv;
+        const double r2 = mx * mx + my * my;
+        if (alpha > 0.5 && r2 > 1. / (2. * alpha - 1.)) return false;
+        const double mz = (1. - alpha * alpha * r2) / (alpha * std::sqrt(1. - (2. * alpha - 1.) * r2) + 1. - alpha);
+        const double sc = (mz * xi + std::sqrt(mz * mz + (1. - xi * xi) * r2)) / (mz * mz + r2);
+        X[0] = sc * mx; X[1] = sc * my; X[2] = sc * mz - xi;
+        return true;
+    }
     const double xi = p[0];
     const double fu = model == VG_MODEL_UCM ? p[1] : p[6], fv = model == VG_MODEL_UCM ? p[2] : p[7];
     const double u0 = model == VG_MODEL_UCM ? p[3] : p[8], v0 = model == VG_MODEL_UCM ? p[4] : p[9];
@@ -541,6 +582,8 @@ inline void parse_cameras(vg_calibration *c, const vgjson::Value &root)  // :134
         if (type == "eucm") { c->log += "Model : EUCM\n"; model = VG_MODEL_EUCM; }
         else if (type == "ucm") { c->log += "Model : UCM\n"; model = VG_MODEL_UCM; }
         else if (type == "mei") { c->log += "Model : MEI\n"; model = VG_MODEL_MEI; }
+        else if (type == "kb") { c->log += "Model : KB\n"; model = VG_MODEL_KB; }   // not in the reference: DESIGN.md section 5.26
+        else if (type == "ds") { c->log += "Model : DS\n"; model = VG_MODEL_DS; }
         else throw Error{VG_ERR_INVALID_ARGUMENT, "invalid camera model name"};
         if ((int)c->intrinsicMap[name].size() != vg::num_intrinsics(model))
             throw Error{VG_ERR_INVALID_ARGUMENT, "invalid number of intrinsic parameters"};

@@ -7,13 +7,16 @@
 // where the reference's three copies are the same expression (so the value is bit-identical);
 // where they differ in association (UCM/Mei: rho summed z^2+x^2+y^2 in the projector but
 // x^2+y^2+z^2 in the Jacobians, ucm.h:44 vs :125) both forms are kept.
+// Kannala-Brandt and double sphere, further down, are not in the reference: their order of operations is stated here and
+// restated in tests/camera_models_ref.py.
 #pragma once
 
 #include "vg_geometry.hpp"
 
 namespace vg {
 
-enum Model : int { kEUCM = 0, kUCM = 1, kMEI = 2 };
+// Kannala-Brandt and double sphere are not in the reference; value 3 stays unassigned and refused
+enum Model : int { kEUCM = 0, kUCM = 1, kMEI = 2, kKB = 4, kDS = 5 };
 
 template <int MODEL>
 struct CameraTraits;
@@ -30,7 +33,19 @@ struct CameraTraits<kMEI> {
     static constexpr int K = 10;
 };
 
-VG_HD int num_intrinsics(int model) { return model == kEUCM ? 6 : model == kUCM ? 5 : model == kMEI ? 10 : -1; }
+template <>
+struct CameraTraits<kKB> {
+    static constexpr int K = 8;
+};
+template <>
+struct CameraTraits<kDS> {
+    static constexpr int K = 6;
+};
+
+VG_HD int num_intrinsics(int model)
+{
+    return model == kEUCM ? 6 : model == kUCM ? 5 : model == kMEI ? 10 : model == kKB ? 8 : model == kDS ? 6 : -1;
+}
 
 // Result of one corner.  P = [du/dX (3) | dv/dX (3)], Ju / Jv = the two intrinsic-Jacobian rows.
 template <int K>
@@ -239,6 +254,129 @@ VG_HD void eval_corner(const double *__restrict__ p, double x, double y, double 
     }
 }
 
+// ------------------------------------------------------------------------------- Kannala-Brandt
+// Not in the reference.  p = [k1, k2, k3, k4, fu, fv, u0, v0];  r = |(x, y)|, theta = atan2(r, z),
+// d(theta) = theta + k1 theta^3 + k2 theta^5 + k3 theta^7 + k4 theta^9, c = d / r, (u, v) = (fu c x + u0, fv c y + v0).
+// With s = x / r, t = y / r, A = d' z / rho^2 and B = -d' r / rho^2 (rho^2 = r^2 + z^2):
+//   du/dX = fu [A s^2 + c t^2, s t (A - c), s B],   dv/dX = fv [s t (A - c), A t^2 + c s^2, t B]
+// (the diagonal terms are sums, never differences, of A and c: on the axis both are 1 / z).  Fails behind the origin on the
+// axis (r = 0, z <= 0) and where the polynomial has folded over (d' <= 0); a point behind the camera with r > 0 is valid.
+// On-axis form: for z > 0 and r^2 <= kKbAxisRatio2 z^2 (theta <= 1e-15) c = 1 / z exactly to double precision, s and t are
+// not formed (r may be zero or a rounded subnormal), du/dX = [fu / z, 0, 0], dv/dX = [0, fv / z, 0] and the distortion
+// columns, at most fu theta^3 <= 1e-45 fu, are zero.
+constexpr double kKbAxisRatio2 = 1e-30;
+
+template <bool WANT_P, bool WANT_I>
+VG_HD void eval_corner(const double *__restrict__ p, double x, double y, double z, CornerEval<8> &e,
+                       std::integral_constant<int, kKB>)
+{
+    const double k1 = p[0], k2 = p[1], k3 = p[2], k4 = p[3], fu = p[4], fv = p[5], u0 = p[6], v0 = p[7];
+    const double r2 = x * x + y * y;
+    const double r = sqrt(r2);
+    const double zz = z * z;
+    const bool axis = z > 0. && r2 <= kKbAxisRatio2 * zz;
+    const double theta = atan2(r, z);
+    const double t2 = theta * theta;
+    const double d = theta * (1. + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))));
+    const double dp = 1. + t2 * (3. * k1 + t2 * (5. * k2 + t2 * (7. * k3 + t2 * (9. * k4))));
+    const bool ok = dp > 0. && !(r == 0. && z <= 0.);
+    e.ok = ok;
+    const double rs = axis ? 1. : r;  // never a division by the on-axis r
+    const double c = axis ? 1. / z : d / rs;
+    e.u = fu * (c * x) + u0;
+    e.v = fv * (c * y) + v0;
+    if (WANT_P || WANT_I) {
+        const double s = axis ? 0. : x / rs, t = axis ? 0. : y / rs;
+        if (WANT_P) {
+            const double rho2 = r2 + zz;
+            const double A = axis ? c : dp * z / rho2;
+            const double B = -dp * r / rho2;
+            const double ss = axis ? 1. : s * s, tt = axis ? 0. : t * t;  // on the axis A = c: any split of s^2 + t^2 = 1
+            const double st = s * t, AmC = A - c;
+            e.P[0] = ok ? fu * (A * ss + c * tt) : 0.;
+            e.P[1] = ok ? fu * (st * AmC) : 0.;
+            e.P[2] = ok ? fu * (s * B) : 0.;
+            e.P[3] = ok ? fv * (st * AmC) : 0.;
+            e.P[4] = ok ? fv * (A * tt + c * ss) : 0.;
+            e.P[5] = ok ? fv * (t * B) : 0.;
+        }
+        if (WANT_I) {
+            const double t3 = theta * t2, t5 = t3 * t2, t7 = t5 * t2, t9 = t7 * t2;
+            const double fus = fu * s, fvt = fv * t;
+            e.Ju[0] = ok ? fus * t3 : 0.;
+            e.Ju[1] = ok ? fus * t5 : 0.;
+            e.Ju[2] = ok ? fus * t7 : 0.;
+            e.Ju[3] = ok ? fus * t9 : 0.;
+            e.Ju[4] = ok ? c * x : 0.;
+            e.Ju[5] = 0.;
+            e.Ju[6] = ok ? 1. : 0.;
+            e.Ju[7] = 0.;
+            e.Jv[0] = ok ? fvt * t3 : 0.;
+            e.Jv[1] = ok ? fvt * t5 : 0.;
+            e.Jv[2] = ok ? fvt * t7 : 0.;
+            e.Jv[3] = ok ? fvt * t9 : 0.;
+            e.Jv[4] = 0.;
+            e.Jv[5] = ok ? c * y : 0.;
+            e.Jv[6] = 0.;
+            e.Jv[7] = ok ? 1. : 0.;
+        }
+    }
+}
+
+// -------------------------------------------------------------------------------- double sphere
+// Usenko, Demmel, Cremers 2018; not in the reference.  p = [xi, alpha, fu, fv, u0, v0];
+// d1 = |X|, w = xi d1 + z, d2 = |(x, y, w)|, den = alpha d2 + (1 - alpha) w, (u, v) = (fu x / den + u0, fv y / den + v0);
+// valid iff z > -w2 d1.  With G = alpha (1 + xi w / d1) / d2 + (1 - alpha) xi / d1 and H = alpha w / d2 + 1 - alpha:
+//   d den / d(x, y, z) = (x G, y G, H (xi z / d1 + 1)),  d den / d xi = d1 H,  d den / d alpha = d2 - w.
+template <bool WANT_P, bool WANT_I>
+VG_HD void eval_corner(const double *__restrict__ p, double x, double y, double z, CornerEval<6> &e,
+                       std::integral_constant<int, kDS>)
+{
+    const double xi = p[0], alpha = p[1], fu = p[2], fv = p[3], u0 = p[4], v0 = p[5];
+    const double r2 = x * x + y * y;
+    const double d1 = sqrt(r2 + z * z);
+    const double w = xi * d1 + z;
+    const double d2 = sqrt(r2 + w * w);
+    const double gamma = 1. - alpha;
+    const double den = alpha * d2 + gamma * w;
+    const double w1 = alpha <= 0.5 ? alpha / gamma : gamma / alpha;
+    const double w2 = (w1 + xi) / sqrt(2. * w1 * xi + xi * xi + 1.);
+    const bool ok = z > -w2 * d1;  // false for X = 0 and for a NaN w2 (parameters outside the box)
+    e.ok = ok;
+    const double xn = x / den, yn = y / den;
+    e.u = fu * xn + u0;
+    e.v = fv * yn + v0;
+    if (WANT_P || WANT_I) {
+        const double k = 1. / (den * den);
+        const double H = alpha * w / d2 + gamma;
+        if (WANT_P) {
+            const double G = alpha * (1. + xi * w / d1) / d2 + gamma * xi / d1;
+            const double dz = H * (xi * z / d1 + 1.);
+            e.P[0] = ok ? fu * k * (den - x * x * G) : 0.;
+            e.P[1] = ok ? -fu * k * (x * y * G) : 0.;
+            e.P[2] = ok ? -fu * k * (x * dz) : 0.;
+            e.P[3] = ok ? -fv * k * (x * y * G) : 0.;
+            e.P[4] = ok ? fv * k * (den - y * y * G) : 0.;
+            e.P[5] = ok ? -fv * k * (y * dz) : 0.;
+        }
+        if (WANT_I) {
+            const double dxi = d1 * H, dal = d2 - w;
+            e.Ju[0] = ok ? -fu * k * (x * dxi) : 0.;
+            e.Ju[1] = ok ? -fu * k * (x * dal) : 0.;
+            e.Ju[2] = ok ? xn : 0.;
+            e.Ju[3] = 0.;
+            e.Ju[4] = ok ? 1. : 0.;
+            e.Ju[5] = 0.;
+            e.Jv[0] = ok ? -fv * k * (y * dxi) : 0.;
+            e.Jv[1] = ok ? -fv * k * (y * dal) : 0.;
+            e.Jv[2] = 0.;
+            e.Jv[3] = ok ? yn : 0.;
+            e.Jv[4] = 0.;
+            e.Jv[5] = ok ? 1. : 0.;
+        }
+    }
+}
+
 template <int MODEL, bool WANT_P, bool WANT_I>
 VG_HD void eval_corner(const double *__restrict__ p, double x, double y, double z,
                        CornerEval<CameraTraits<MODEL>::K> &e)
@@ -393,6 +531,20 @@ __device__ __forceinline__ void eval_corner_fast(const double *__restrict__ p, d
     e.Jv[7] = yd;
     e.Jv[8] = 0.;
     e.Jv[9] = 1.;
+}
+
+// Kannala-Brandt and double sphere have no tuned form yet: the Gram kernels evaluate them in the order (and with the IEEE
+// divisions) of eval_corner above, whose rows are already exact zeros where the projection fails.  Not measured.
+__device__ __forceinline__ void eval_corner_fast(const double *__restrict__ p, double x, double y, double z, CornerEval<8> &e,
+                                                 std::integral_constant<int, kKB> m)
+{
+    eval_corner<true, true>(p, x, y, z, e, m);
+}
+
+__device__ __forceinline__ void eval_corner_fast(const double *__restrict__ p, double x, double y, double z, CornerEval<6> &e,
+                                                 std::integral_constant<int, kDS> m)
+{
+    eval_corner<true, true>(p, x, y, z, e, m);
 }
 
 template <int MODEL>

@@ -196,15 +196,25 @@ int launch_emit(hipStream_t stream, const vg::EmitArgs &a, bool want_jac, bool i
     return VG_OK;
 }
 
-// one emit launch of one dataset (or of a chunk of it) with the camera model as a value; a.nt_stores and a.map_window are set
+#ifndef VG_TU_EMIT_MODELS   // vg_emit_models_tu.hip takes the launch templates above and nothing below
+// one emit launch of one dataset (or of a chunk of it) with the camera model as a value; a.nt_stores and a.map_window are set.
+// The reference's three models are instantiated here; Kannala-Brandt and double sphere in a translation unit of their own
+// (vg_emit_models_tu.hip): the two compile side by side and this unit's code object holds what it held before.
 int launch_emit(hipStream_t stream, int model, const vg::EmitArgs &a, bool want_jac, bool inline_chain)
 {
     switch (model) {
     case VG_MODEL_EUCM: return launch_emit<vg::kEUCM>(stream, a, want_jac, inline_chain);
     case VG_MODEL_UCM: return launch_emit<vg::kUCM>(stream, a, want_jac, inline_chain);
-    default: return launch_emit<vg::kMEI>(stream, a, want_jac, inline_chain);
+    case VG_MODEL_MEI: return launch_emit<vg::kMEI>(stream, a, want_jac, inline_chain);
+    case VG_MODEL_KB:
+    case VG_MODEL_DS: return vgi::launch_emit_added_model(stream, model, a, want_jac, inline_chain);
+    default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
     }
 }
+
+// The merged launch (vg_emit_multi_kernel) is built for the reference's three models; a Kannala-Brandt or double-sphere dataset
+// takes the one-dataset launch, the others of the same problem still merge among themselves.
+bool emit_merged_model(int model) { return model == VG_MODEL_EUCM || model == VG_MODEL_UCM || model == VG_MODEL_MEI; }
 
 // The datasets `ids` of the problem in merged launches (vg_emit_multi_kernel) of up to kEmitMultiMax datasets each, in the order
 // given.  The caller checked every one of them: Jacobians wanted, frames fit the LDS, one launch holds its observations; and it
@@ -258,5 +268,6 @@ int launch_emit_merged(vg_problem *p, const vg_dataset_outputs *outs, const std:
     }
     return VG_OK;
 }
+#endif  // VG_TU_EMIT_MODELS
 
 }  // namespace

@@ -128,7 +128,7 @@ int vg_problem_evaluate(vg_problem *p, const vg_dataset_outputs *outs)
         }
         if (!outs[i].residuals) return fail(VG_ERR_INVALID_ARGUMENT, "residuals is NULL");
         if (wants_jacobian(d, outs[i].jac_intr, outs[i].jac_member) && emit_frames_in_lds(d.N, d.frame_stride) &&
-            d.n_blocks <= max_blocks_per_launch(d))
+            d.n_blocks <= max_blocks_per_launch(d) && emit_merged_model(p->cams[d.camera].model))
             shared.push_back(i);
         else alone.push_back(i);
     }

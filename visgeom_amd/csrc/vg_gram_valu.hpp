@@ -42,12 +42,16 @@ struct GramValuArgs {
     unsigned int n_wg;
 };
 
-// structurally non-zero columns of the two intrinsic-Jacobian rows (eucm.h:169-226, ucm.h:153-197, mei.h:193-285)
+// structurally non-zero columns of the two intrinsic-Jacobian rows (eucm.h:169-226, ucm.h:153-197, mei.h:193-285; Kannala-Brandt
+// and double sphere: eval_corner in vg_camera.hpp)
 template <int MODEL>
 __host__ __device__ constexpr bool intr_nonzero(int row /*0 = u, 1 = v*/, int i)
 {
     if (MODEL == kEUCM) return row == 0 ? (i != 3 && i != 5) : (i != 2 && i != 4);
     if (MODEL == kUCM) return row == 0 ? (i != 2 && i != 4) : (i != 1 && i != 3);
+    if (MODEL == kKB) return row == 0 ? (i != 5 && i != 7) : (i != 4 && i != 6);
+    if (MODEL == kDS) return row == 0 ? (i != 3 && i != 5) : (i != 2 && i != 4);
+    static_assert(MODEL == kEUCM || MODEL == kUCM || MODEL == kMEI || MODEL == kKB || MODEL == kDS, "camera model");
     return row == 0 ? (i != 7 && i != 9) : (i != 6 && i != 8);  // Mei
 }
 

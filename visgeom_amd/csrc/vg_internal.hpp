@@ -277,6 +277,8 @@ inline int valid_dataset(const vg_problem *p, int d)
 // touching the problem's own parameter vector); implemented in vg_emit_tu.hip
 int prepare_at(vg_problem *p, const double *d_params);
 int ensure_frames(vg_problem *p);  // chain prep at the problem's own parameters if the frames are stale
+// one emit launch of a Kannala-Brandt or double-sphere dataset (vg_emit_models_tu.hip: their vg_emit_kernel instantiations)
+int launch_emit_added_model(hipStream_t stream, int model, const vg::EmitArgs &a, bool want_jac, bool inline_chain);
 // sum != NULL: also the fixed-order sum over the dataset's blocks, [W*W] (one extra launch on the vector-pipe route)
 int gram_fused_at(vg_problem *p, int dataset_id, const double *d_params, double *gram, double *sum);
 // the fused Gram of every dataset the merged vector-pipe launch can take (taken[d] = 1), at a device parameter buffer;

@@ -417,9 +417,10 @@ __device__ __forceinline__ void emit_fetch_args(const EmitArgs &a)
 template <int K>
 __device__ __forceinline__ void emit_pin_intrinsics(const double *x)
 {
-    static_assert(K == 5 || K == 6 || K == 10, "UCM, EUCM, Mei");
+    static_assert(K == 5 || K == 6 || K == 8 || K == 10, "UCM, EUCM / double sphere, Kannala-Brandt, Mei");
     if constexpr (K == 5) asm volatile("" ::"s"(x[0]), "s"(x[1]), "s"(x[2]), "s"(x[3]), "s"(x[4]));
     else if constexpr (K == 6) asm volatile("" ::"s"(x[0]), "s"(x[1]), "s"(x[2]), "s"(x[3]), "s"(x[4]), "s"(x[5]));
+    else if constexpr (K == 8) asm volatile("" ::"s"(x[0]), "s"(x[1]), "s"(x[2]), "s"(x[3]), "s"(x[4]), "s"(x[5]), "s"(x[6]), "s"(x[7]));
     else asm volatile("" ::"s"(x[0]), "s"(x[1]), "s"(x[2]), "s"(x[3]), "s"(x[4]), "s"(x[5]), "s"(x[6]), "s"(x[7]), "s"(x[8]), "s"(x[9]));
 }
 

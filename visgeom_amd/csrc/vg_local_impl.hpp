@@ -43,6 +43,10 @@ inline size_t io_doubles(const vg_reproject_set *s)
     return 12 + 2 * n + 12 * n + (s->sparse ? 0 : 10 * n);
 }
 
+// the kernels of this section are instantiated for the reference's three models; their switches end in Mei, so Kannala-Brandt
+// and double sphere are refused at the entries, before HIP is touched
+inline bool local_model(int model) { return model == VG_MODEL_EUCM || model == VG_MODEL_UCM || model == VG_MODEL_MEI; }
+
 // std::vector growth inside the set-up may throw; nothing may cross the extern "C" boundary
 inline int create(vg_reproject_set **out, int device, void *hip_stream, int model, const double *intr, const double *xb, bool sparse,
                   int64_t n_blocks, const int64_t *offsets, const double *x1, const double *x2, const double *p2, const double *size)
@@ -51,6 +55,7 @@ try {
     *out = nullptr;
     const int K = vg::num_intrinsics(model);
     if (K < 0) return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
+    if (!local_model(model)) return fail(VG_ERR_INVALID_ARGUMENT, "the localization costs are built for EUCM, UCM and Mei only");
     if (!intr || !xb || n_blocks < 0 || (n_blocks > 0 && (!x1 || !p2))) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (sparse && n_blocks > 0 && (!offsets || !x2 || !size)) return fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (n_blocks >= (1ll << 31) / 8) return fail(VG_ERR_INVALID_ARGUMENT, "too many blocks");
@@ -171,13 +176,15 @@ inline int launch(vg_reproject_set *s, int64_t b0, int64_t nb, const double *xi_
             switch (s->model) {
             case vg::kEUCM: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kEUCM, true>), grid, blk, lds, s->stream, a); break;
             case vg::kUCM: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kUCM, true>), grid, blk, lds, s->stream, a); break;
-            default: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kMEI, true>), grid, blk, lds, s->stream, a); break;
+            case vg::kMEI: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kMEI, true>), grid, blk, lds, s->stream, a); break;
+            default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
             }
         } else {
             switch (s->model) {
             case vg::kEUCM: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kEUCM, false>), grid, blk, kLocalLds, s->stream, a); break;
             case vg::kUCM: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kUCM, false>), grid, blk, kLocalLds, s->stream, a); break;
-            default: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kMEI, false>), grid, blk, kLocalLds, s->stream, a); break;
+            case vg::kMEI: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kMEI, false>), grid, blk, kLocalLds, s->stream, a); break;
+            default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
             }
         }
     } else {
@@ -198,7 +205,8 @@ inline int launch(vg_reproject_set *s, int64_t b0, int64_t nb, const double *xi_
         switch (s->model) {
         case vg::kEUCM: hipLaunchKernelGGL((vg::vg_mono_reproject_kernel<vg::kEUCM>), mgrid, mblk, sizeof(double) * vg::kMonoLdsDoubles, s->stream, a); break;
         case vg::kUCM: hipLaunchKernelGGL((vg::vg_mono_reproject_kernel<vg::kUCM>), mgrid, mblk, sizeof(double) * vg::kMonoLdsDoubles, s->stream, a); break;
-        default: hipLaunchKernelGGL((vg::vg_mono_reproject_kernel<vg::kMEI>), mgrid, mblk, sizeof(double) * vg::kMonoLdsDoubles, s->stream, a); break;
+        case vg::kMEI: hipLaunchKernelGGL((vg::vg_mono_reproject_kernel<vg::kMEI>), mgrid, mblk, sizeof(double) * vg::kMonoLdsDoubles, s->stream, a); break;
+        default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
         }
     }
     VG_HIP(hipGetLastError());
@@ -298,6 +306,7 @@ int vg_camera_jacobian_evaluate(int device, void *hip_stream, int model, const d
 {
     const int K = vg::num_intrinsics(model);
     if (K < 0) return vgi::fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
+    if (!vgl::local_model(model)) return vgi::fail(VG_ERR_INVALID_ARGUMENT, "CameraJacobian is built for EUCM, UCM and Mei only");
     if (!intrinsics || !T12 || n < 0 || (n > 0 && !X2)) return vgi::fail(VG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (dfdxi && !grad) return vgi::fail(VG_ERR_INVALID_ARGUMENT, "dfdxi needs the image gradient");
     if (n >= (1ll << 31)) return vgi::fail(VG_ERR_INVALID_ARGUMENT, "too many points");
@@ -318,7 +327,8 @@ int vg_camera_jacobian_evaluate(int device, void *hip_stream, int model, const d
     switch (model) {
     case vg::kEUCM: hipLaunchKernelGGL((vg::vg_camera_jacobian_kernel<vg::kEUCM>), grid, blk, vgl::kLocalLds, st, a); break;
     case vg::kUCM: hipLaunchKernelGGL((vg::vg_camera_jacobian_kernel<vg::kUCM>), grid, blk, vgl::kLocalLds, st, a); break;
-    default: hipLaunchKernelGGL((vg::vg_camera_jacobian_kernel<vg::kMEI>), grid, blk, vgl::kLocalLds, st, a); break;
+    case vg::kMEI: hipLaunchKernelGGL((vg::vg_camera_jacobian_kernel<vg::kMEI>), grid, blk, vgl::kLocalLds, st, a); break;
+    default: return vgi::fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
     }
     VG_HIP(hipGetLastError());
     return VG_OK;

@@ -92,9 +92,14 @@ int vg_intrinsic_bounds(int model, int idx, double *lower, double *upper)
         else if (idx == 1) { lo = 0.1; hi = 10.; }
     } else if (model == VG_MODEL_UCM) {    // ucm.h:199-215
         if (idx == 0) { lo = 0.; hi = 3.; }
-    } else {                               // mei.h:287-313
+    } else if (model == VG_MODEL_MEI) {    // mei.h:287-313
         if (idx == 0) { lo = 0.; hi = 3.; }
         else if (idx <= 5) { lo = -10.; hi = 10.; }
+    } else if (model == VG_MODEL_KB) {     // k1..k4: Mei's distortion range
+        if (idx <= 3) { lo = -10.; hi = 10.; }
+    } else {                               // double sphere (num_intrinsics refused everything else): xi, alpha
+        if (idx == 0) { lo = -0.9; hi = 3.; }
+        else if (idx == 1) { lo = 0.; hi = 1.; }
     }
     *lower = lo;
     *upper = hi;

@@ -80,7 +80,10 @@ int vg_rectify_map(int device, void *hip_stream, int model, const double *intrin
     switch (model) {
     case vg::kEUCM: launch_map<vg::kEUCM>(a, vec, st); break;
     case vg::kUCM: launch_map<vg::kUCM>(a, vec, st); break;
-    default: launch_map<vg::kMEI>(a, vec, st); break;
+    case vg::kMEI: launch_map<vg::kMEI>(a, vec, st); break;
+    case vg::kKB: launch_map<vg::kKB>(a, vec, st); break;
+    case vg::kDS: launch_map<vg::kDS>(a, vec, st); break;
+    default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
     }
     VG_HIP(hipGetLastError());
     return VG_OK;

@@ -196,19 +196,23 @@ int vgi::refine_poses_resident(int device, void *hip_stream, int model, const do
     // a persistent grid: as many workgroups as are resident at once (two per CU at two waves per SIMD), never more than the images
     // need; every half-wave starts on the image of its position and takes further ones from the counter
     static int cu_count[64] = {0};   // per device, asked once (hipGetDeviceProperties is a millisecond)
-    static int per_cu_of[64][3] = {{0}};
+    static int per_cu_of[64][5] = {{0}};   // per device and model: EUCM, UCM, Mei, Kannala-Brandt, double sphere
     if (device < 64 && !cu_count[device]) {
         int cus = 0;
         VG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
         cu_count[device] = cus > 0 ? cus : 1;
     }
     const int n_cus = device < 64 ? cu_count[device] : 256;
-    const int mi = model == VG_MODEL_EUCM ? 0 : model == VG_MODEL_UCM ? 1 : 2;
+    // the model was checked at entry (num_intrinsics): one of the five
+    const int mi = model == VG_MODEL_EUCM ? 0 : model == VG_MODEL_UCM ? 1 : model == VG_MODEL_MEI ? 2 : model == VG_MODEL_KB ? 3 : 4;
     int per_cu = device < 64 ? per_cu_of[device][mi] : 0;
     if (per_cu < 1) {
-        const void *fn = model == VG_MODEL_EUCM ? reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kEUCM>)
-                         : model == VG_MODEL_UCM ? reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kUCM>)
-                                                 : reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kMEI>);
+        const void *const fns[5] = {reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kEUCM>),
+                                    reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kUCM>),
+                                    reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kMEI>),
+                                    reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kKB>),
+                                    reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kDS>)};
+        const void *fn = fns[mi];
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, vg::kValuThreads, 0) != hipSuccess || per_cu < 1) {
             (void)hipGetLastError();
             per_cu = 1;
@@ -222,7 +226,10 @@ int vgi::refine_poses_resident(int device, void *hip_stream, int model, const do
     switch (model) {
     case VG_MODEL_EUCM: hipLaunchKernelGGL(vg::vg_pose_lm_kernel<vg::kEUCM>, grid, blk, 0, st, a); break;
     case VG_MODEL_UCM: hipLaunchKernelGGL(vg::vg_pose_lm_kernel<vg::kUCM>, grid, blk, 0, st, a); break;
-    default: hipLaunchKernelGGL(vg::vg_pose_lm_kernel<vg::kMEI>, grid, blk, 0, st, a); break;
+    case VG_MODEL_MEI: hipLaunchKernelGGL(vg::vg_pose_lm_kernel<vg::kMEI>, grid, blk, 0, st, a); break;
+    case VG_MODEL_KB: hipLaunchKernelGGL(vg::vg_pose_lm_kernel<vg::kKB>, grid, blk, 0, st, a); break;
+    case VG_MODEL_DS: hipLaunchKernelGGL(vg::vg_pose_lm_kernel<vg::kDS>, grid, blk, 0, st, a); break;
+    default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
     }
     VG_HIP(hipGetLastError());
     if (kernel_seconds) VG_HIP(hipEventRecord(r.e1, st));

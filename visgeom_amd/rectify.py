@@ -1,5 +1,5 @@
 """Fisheye rectification on the GPU (include/visgeom_amd.h section 7): the pinhole -> camera undistortion maps of a calibrated
-EUCM / UCM / Mei camera (the reference's `rectify` program) and a batched bilinear remap of images through them.  Thin torch
+EUCM / UCM / Mei / Kannala-Brandt / double-sphere camera (the reference's `rectify` program) and a batched bilinear remap of images through them.  Thin torch
 wrappers: both run on torch's current stream of the tensors' device; library errors raise capi.VisgeomError."""
 import ctypes
 

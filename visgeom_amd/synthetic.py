@@ -22,11 +22,17 @@ _alpha = GT_EUCM_CAM1[0]
 GT_UCM = np.array([_alpha / (1 - _alpha), GT_EUCM_CAM1[2] / (1 - _alpha), GT_EUCM_CAM1[3] / (1 - _alpha),
                    GT_EUCM_CAM1[4], GT_EUCM_CAM1[5]])
 GT_MEI = np.concatenate([GT_UCM[:1], [-0.05, 0.01, -0.002, 0.001, -0.0015], GT_UCM[1:]])
-GT = {"eucm": GT_EUCM_CAM1, "ucm": GT_UCM, "mei": GT_MEI}
+# Kannala-Brandt and double sphere are not in the reference: values that see 114-118 degrees of half angle at the corners of the
+# 1280 x 800 image and keep the board poses of make_poses inside it
+GT_KB = np.array([-0.01, 0.003, -0.001, 0.0002, 380.0, 380.0, 642.617, 398.42])
+GT_DS = np.array([-0.2, 0.59, 245.6, 231.6, 642.617, 398.42])
+GT = {"eucm": GT_EUCM_CAM1, "ucm": GT_UCM, "mei": GT_MEI, "kb": GT_KB, "ds": GT_DS}
 # evaluation / initial point (style of data/calib_example.json:17)
 INIT = {"eucm": np.array([0.5, 1.0, 300.0, 300.0, 640.0, 400.0]),
         "ucm": np.array([1.2, 700.0, 700.0, 640.0, 400.0]),
-        "mei": np.array([1.2, 0, 0, 0, 0, 0, 700.0, 700.0, 640.0, 400.0])}
+        "mei": np.array([1.2, 0, 0, 0, 0, 0, 700.0, 700.0, 640.0, 400.0]),
+        "kb": np.array([0, 0, 0, 0, 350.0, 350.0, 640.0, 400.0]),
+        "ds": np.array([0, 0.5, 280.0, 280.0, 640.0, 400.0])}
 
 _GOLDEN = np.uint64(0x9E3779B97F4A7C15)
 _M1 = np.uint64(0xBF58476D1CE4E5B9)
@@ -101,6 +107,27 @@ def project(model, p, X):
         if a > 0.5:
             ok &= (z / ds) >= (a - 1) / (2 * a - 1)
         return np.stack([fu * x / ds + u0, fv * y / ds + v0], -1), ok
+    if model == "kb":
+        k1, k2, k3, k4, fu, fv, u0, v0 = p
+        r = np.sqrt(x * x + y * y)
+        th = np.arctan2(r, z)
+        t2 = th * th
+        d = th * (1 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))))
+        dp = 1 + t2 * (3 * k1 + t2 * (5 * k2 + t2 * (7 * k3 + t2 * 9 * k4)))
+        ok = (dp > 0) & ~((r == 0) & (z <= 0))
+        c = np.where(r > 0, d / np.where(r > 0, r, 1.0), 1.0 / np.where(z != 0, z, 1.0))
+        return np.stack([fu * c * x + u0, fv * c * y + v0], -1), ok
+    if model == "ds":
+        xi, a, fu, fv, u0, v0 = p
+        d1 = np.sqrt(x * x + y * y + z * z)
+        w = xi * d1 + z
+        d2 = np.sqrt(x * x + y * y + w * w)
+        den = a * d2 + (1 - a) * w
+        w1 = a / (1 - a) if a <= 0.5 else (1 - a) / a
+        w2 = (w1 + xi) / np.sqrt(2 * w1 * xi + xi * xi + 1)
+        ok = z > -w2 * d1
+        den = np.where(ok, den, 1.0)
+        return np.stack([fu * x / den + u0, fv * y / den + v0], -1), ok
     xi = p[0]
     rho = np.sqrt(x * x + y * y + z * z)
     den = z + xi * rho
