@@ -127,9 +127,8 @@ inline bool reconstruct_point(int model, const double *p, const double *uv, doub
         X[0] = sc * mx; X[1] = sc * my; X[2] = sc * mz - xi;
         return true;
     }
-    const double xi = p[0];
-    const double fu = model == VG_MODEL_UCM ? p[1] : p[6], fv = model == VG_MODEL_UCM ? p[2] : p[7];
-    const double u0 = model == VG_MODEL_UCM ? p[3] : p[8], v0 = model == VG_MODEL_UCM ? p[4] : p[9];
+    const double xi = p[0], *f = p + (model == VG_MODEL_UCM ? vg::CameraTraits<vg::kUCM>::kFocal : vg::CameraTraits<vg::kMEI>::kFocal);
+    const double fu = f[0], fv = f[1], u0 = f[2], v0 = f[3];
     const double xn = (uv[0] - u0) / fu, yn = (uv[1] - v0) / fv;
     const double u2 = xn * xn + yn * yn;
     const double gamma = std::sqrt(1. + u2 * (1 - xi * xi));

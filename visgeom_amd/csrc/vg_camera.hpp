@@ -9,43 +9,13 @@
 // x^2+y^2+z^2 in the Jacobians, ucm.h:44 vs :125) both forms are kept.
 // Kannala-Brandt and double sphere, further down, are not in the reference: their order of operations is stated here and
 // restated in tests/camera_models_ref.py.
+// The model ids, CameraTraits, num_intrinsics and the list of what adding a camera model has to touch: vg_model_list.hpp.
 #pragma once
 
 #include "vg_geometry.hpp"
+#include "vg_model_list.hpp"
 
 namespace vg {
-
-// Kannala-Brandt and double sphere are not in the reference; value 3 stays unassigned and refused
-enum Model : int { kEUCM = 0, kUCM = 1, kMEI = 2, kKB = 4, kDS = 5 };
-
-template <int MODEL>
-struct CameraTraits;
-template <>
-struct CameraTraits<kEUCM> {
-    static constexpr int K = 6;
-};
-template <>
-struct CameraTraits<kUCM> {
-    static constexpr int K = 5;
-};
-template <>
-struct CameraTraits<kMEI> {
-    static constexpr int K = 10;
-};
-
-template <>
-struct CameraTraits<kKB> {
-    static constexpr int K = 8;
-};
-template <>
-struct CameraTraits<kDS> {
-    static constexpr int K = 6;
-};
-
-VG_HD int num_intrinsics(int model)
-{
-    return model == kEUCM ? 6 : model == kUCM ? 5 : model == kMEI ? 10 : model == kKB ? 8 : model == kDS ? 6 : -1;
-}
 
 // Result of one corner.  P = [du/dX (3) | dv/dX (3)], Ju / Jv = the two intrinsic-Jacobian rows.
 template <int K>

@@ -202,19 +202,10 @@ int launch_emit(hipStream_t stream, const vg::EmitArgs &a, bool want_jac, bool i
 // (vg_emit_models_tu.hip): the two compile side by side and this unit's code object holds what it held before.
 int launch_emit(hipStream_t stream, int model, const vg::EmitArgs &a, bool want_jac, bool inline_chain)
 {
-    switch (model) {
-    case VG_MODEL_EUCM: return launch_emit<vg::kEUCM>(stream, a, want_jac, inline_chain);
-    case VG_MODEL_UCM: return launch_emit<vg::kUCM>(stream, a, want_jac, inline_chain);
-    case VG_MODEL_MEI: return launch_emit<vg::kMEI>(stream, a, want_jac, inline_chain);
-    case VG_MODEL_KB:
-    case VG_MODEL_DS: return vgi::launch_emit_added_model(stream, model, a, want_jac, inline_chain);
-    default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
-    }
+    int rc = VG_OK;
+    const bool here = vg::dispatch_model(model, vg::ReferenceModels{}, [&](auto m) { rc = launch_emit<decltype(m)::value>(stream, a, want_jac, inline_chain); });
+    return here ? rc : vgi::launch_emit_added_model(stream, model, a, want_jac, inline_chain);   // which refuses a model of neither list
 }
-
-// The merged launch (vg_emit_multi_kernel) is built for the reference's three models; a Kannala-Brandt or double-sphere dataset
-// takes the one-dataset launch, the others of the same problem still merge among themselves.
-bool emit_merged_model(int model) { return model == VG_MODEL_EUCM || model == VG_MODEL_UCM || model == VG_MODEL_MEI; }
 
 // The datasets `ids` of the problem in merged launches (vg_emit_multi_kernel) of up to kEmitMultiMax datasets each, in the order
 // given.  The caller checked every one of them: Jacobians wanted, frames fit the LDS, one launch holds its observations; and it

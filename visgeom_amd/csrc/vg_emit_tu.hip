@@ -118,7 +118,8 @@ int vg_problem_evaluate(vg_problem *p, const vg_dataset_outputs *outs)
     const int n_ds = (int)p->dss.size();
     int rc;
     // which datasets can share a launch: every Jacobian-carrying evaluation whose frames fit the LDS and whose
-    // observation count fits one launch; the rest (cost-only calls, huge sets) go through vg_dataset_evaluate
+    // observation count fits one launch; the rest (cost-only calls, huge sets) go through vg_dataset_evaluate.  The merged launch
+    // (vg_emit_multi_kernel) is built for the reference's three models: a Kannala-Brandt or double-sphere dataset goes alone
     std::vector<int> shared, alone;
     for (int i = 0; i < n_ds; i++) {
         Dataset &d = p->dss[i];
@@ -128,7 +129,7 @@ int vg_problem_evaluate(vg_problem *p, const vg_dataset_outputs *outs)
         }
         if (!outs[i].residuals) return fail(VG_ERR_INVALID_ARGUMENT, "residuals is NULL");
         if (wants_jacobian(d, outs[i].jac_intr, outs[i].jac_member) && emit_frames_in_lds(d.N, d.frame_stride) &&
-            d.n_blocks <= max_blocks_per_launch(d) && emit_merged_model(p->cams[d.camera].model))
+            d.n_blocks <= max_blocks_per_launch(d) && vg::model_in(p->cams[d.camera].model, vg::ReferenceModels{}))
             shared.push_back(i);
         else alone.push_back(i);
     }

@@ -112,12 +112,17 @@ int launch_gram_valu_pers(hipStream_t stream, const vg::GramValuArgs &a, unsigne
     return VG_OK;
 }
 
-// corners per pass of Kannala-Brandt's persistent form: the rule of the factored form below (15 columns: two, then the third).
-// An A/B build sets the other value (python -m visgeom_amd._build --variant kbpers3 -DVG_KB_PERS_CORNERS=3).
+// corners per pass over rows of K + 7 columns, in the factored and in the persistent form: three up to 13 columns, beyond that
+// (Mei 17, Kannala-Brandt 15) two and then the third.  For Kannala-Brandt's persistent form three timed 7-10 % faster in an A/B
+// build (python -m visgeom_amd._build --variant kbpers3 -DVG_KB_PERS_CORNERS=3) and wait for their tests (DESIGN.md 5.26,
+// profiles/r25_camera_models.md)
+template <int MODEL>
+constexpr int kGramCorners = vg::CameraTraits<MODEL>::K + 7 <= 13 ? 3 : 2;
 #ifndef VG_KB_PERS_CORNERS
-#define VG_KB_PERS_CORNERS (vg::CameraTraits<vg::kKB>::K + 7 <= 13 ? 3 : 2)
+#define VG_KB_PERS_CORNERS kGramCorners<vg::kKB>
 #endif
-constexpr int kKbPersCorners = VG_KB_PERS_CORNERS;
+template <int MODEL>
+constexpr int kGramPersCorners = MODEL == vg::kKB ? VG_KB_PERS_CORNERS : kGramCorners<MODEL>;
 
 template <int MODEL, int CH>
 int launch_gram_valu_pers_shape(hipStream_t stream, const vg::GramValuArgs &a, int shape, unsigned int *n_wg_out)
@@ -160,7 +165,7 @@ int launch_gram_valu(hipStream_t stream, const vg::GramValuArgs &a, int L, bool 
     if (L == 1) return launch_gram_valu_l<MODEL, 1>(stream, a, inline_chain);
     // two or more members: the factored form -- rows of K + 7 columns whatever L is
     constexpr int K = vg::CameraTraits<MODEL>::K;
-    constexpr int CH = K + 7 <= 13 ? 3 : 2;
+    constexpr int CH = kGramCorners<MODEL>;
     const size_t lds = vg::gram_valu_z_lds_bytes(K, L);
     const bool small_board = a.g.N <= (unsigned)vg::kValuLanesPerImage;
     if (lds > 48 * 1024) {  // chains of four or five members: more than the default dynamic LDS limit
@@ -218,29 +223,17 @@ int vgi::gram_fused_at(vg_problem *p, int dataset_id, const double *d_params, do
         a.partials = d.d_wg_partials;
     }
     const int pers = (inl && d.L == 1) ? gram_pers_shape(a, sum != nullptr) : 0;
+    bool known;
     if (pers) {
         unsigned int n_wg = 0;
-        switch (cam.model) {
-        case VG_MODEL_EUCM: rc = launch_gram_valu_pers_shape<vg::kEUCM, 3>(p->stream, a, pers, &n_wg); break;
-        case VG_MODEL_UCM: rc = launch_gram_valu_pers_shape<vg::kUCM, 3>(p->stream, a, pers, &n_wg); break;
-        case VG_MODEL_MEI: rc = launch_gram_valu_pers_shape<vg::kMEI, 2>(p->stream, a, pers, &n_wg); break;   // 17-wide rows: two corners, then the third
-        // 15-wide rows: two corners by the same K + 7 <= 13 rule as the factored form; three timed 7-10 % faster in an A/B build and
-        // wait for their tests (profiles/r25_camera_models.md)
-        case VG_MODEL_KB: rc = launch_gram_valu_pers_shape<vg::kKB, kKbPersCorners>(p->stream, a, pers, &n_wg); break;
-        case VG_MODEL_DS: rc = launch_gram_valu_pers_shape<vg::kDS, 3>(p->stream, a, pers, &n_wg); break;
-        default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
-        }
+        known = vg::dispatch_model(cam.model, vg::AllModels{}, [&](auto m) {
+            rc = launch_gram_valu_pers_shape<decltype(m)::value, kGramPersCorners<decltype(m)::value>>(p->stream, a, pers, &n_wg);
+        });
         a.n_wg = n_wg;
     } else {
-        switch (cam.model) {
-        case VG_MODEL_EUCM: rc = launch_gram_valu<vg::kEUCM>(p->stream, a, d.L, inl); break;
-        case VG_MODEL_UCM: rc = launch_gram_valu<vg::kUCM>(p->stream, a, d.L, inl); break;
-        case VG_MODEL_MEI: rc = launch_gram_valu<vg::kMEI>(p->stream, a, d.L, inl); break;
-        case VG_MODEL_KB: rc = launch_gram_valu<vg::kKB>(p->stream, a, d.L, inl); break;
-        case VG_MODEL_DS: rc = launch_gram_valu<vg::kDS>(p->stream, a, d.L, inl); break;
-        default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
-        }
+        known = vg::dispatch_model(cam.model, vg::AllModels{}, [&](auto m) { rc = launch_gram_valu<decltype(m)::value>(p->stream, a, d.L, inl); });
     }
+    if (!known) return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
     if (rc != VG_OK || !sum) return rc;
     hipLaunchKernelGGL(vg::vg_gram_partials_sum_kernel, dim3(E), dim3(256), 0, p->stream,
                        (const double *)d.d_wg_partials, a.n_wg, W, sum);
@@ -250,15 +243,13 @@ int vgi::gram_fused_at(vg_problem *p, int dataset_id, const double *d_params, do
 
 // The merged launch (vg_gram_valu_multi_kernel) is built for the reference's three models; a Kannala-Brandt or double-sphere
 // dataset takes the one-dataset launches, the others of the same problem still merge among themselves.
-static bool gram_merged_model(int model) { return model == VG_MODEL_EUCM || model == VG_MODEL_UCM || model == VG_MODEL_MEI; }
-
 bool vgi::gram_merge_covers_all(const vg_problem *p)
 {
     if (vgi::debug_hook(vgi::kHookGramNoMerge)) return false;
     int n = 0;
     for (const Dataset &d : p->dss) {
         if (!d.n_blocks) continue;
-        if (!(d.n_blocks <= 0x7fffffff && d.L >= 1 && d.N > vg::kValuLanesPerImage && gram_merged_model(p->cams[d.camera].model))) return false;
+        if (!(d.n_blocks <= 0x7fffffff && d.L >= 1 && d.N > vg::kValuLanesPerImage && vg::model_in(p->cams[d.camera].model, vg::ReferenceModels{}))) return false;
         n++;
     }
     return n >= 2 && n % vg::kGramMultiMax != 1;  // a lone leftover group would go the ordinary way
@@ -274,7 +265,7 @@ int vgi::gram_fused_merged_at(vg_problem *p, const double *d_params, double *con
     for (int i = 0; i < n_ds && !off; i++) {
         const Dataset &d = p->dss[i];
         if (d.n_blocks > 0 && d.n_blocks <= 0x7fffffff && grams[i] && d.L >= 1 && d.N > vg::kValuLanesPerImage &&
-            gram_merged_model(p->cams[d.camera].model))
+            vg::model_in(p->cams[d.camera].model, vg::ReferenceModels{}))
             ids.push_back(i);
     }
     if (ids.size() < 2) return VG_OK;

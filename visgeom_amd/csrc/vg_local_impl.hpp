@@ -43,9 +43,9 @@ inline size_t io_doubles(const vg_reproject_set *s)
     return 12 + 2 * n + 12 * n + (s->sparse ? 0 : 10 * n);
 }
 
-// the kernels of this section are instantiated for the reference's three models; their switches end in Mei, so Kannala-Brandt
-// and double sphere are refused at the entries, before HIP is touched
-inline bool local_model(int model) { return model == VG_MODEL_EUCM || model == VG_MODEL_UCM || model == VG_MODEL_MEI; }
+// the kernels of this section are instantiated for the reference's three models: Kannala-Brandt and double sphere are refused at
+// the entries, before HIP is touched
+inline bool local_model(int model) { return vg::model_in(model, vg::ReferenceModels{}); }
 
 // std::vector growth inside the set-up may throw; nothing may cross the extern "C" boundary
 inline int create(vg_reproject_set **out, int device, void *hip_stream, int model, const double *intr, const double *xb, bool sparse,
@@ -154,6 +154,7 @@ inline int launch(vg_reproject_set *s, int64_t b0, int64_t nb, const double *xi_
         VG_HIP(hipGetLastError());
     }
     if (!np) return VG_OK;
+    bool known;
     if (s->sparse) {
         vg::SparseArgs a;
         a.frames = s->d_frames;
@@ -171,22 +172,11 @@ inline int launch(vg_reproject_set *s, int64_t b0, int64_t nb, const double *xi_
         a.jac = jac0;
         a.first_point = p0;
         a.n_points = (unsigned)np;
-        if (fused) {
-            const size_t lds = kLocalLds + sizeof(double) * vg::kSparseWgBlocks * vg::kSparseFrame;
-            switch (s->model) {
-            case vg::kEUCM: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kEUCM, true>), grid, blk, lds, s->stream, a); break;
-            case vg::kUCM: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kUCM, true>), grid, blk, lds, s->stream, a); break;
-            case vg::kMEI: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kMEI, true>), grid, blk, lds, s->stream, a); break;
-            default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
-            }
-        } else {
-            switch (s->model) {
-            case vg::kEUCM: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kEUCM, false>), grid, blk, kLocalLds, s->stream, a); break;
-            case vg::kUCM: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kUCM, false>), grid, blk, kLocalLds, s->stream, a); break;
-            case vg::kMEI: hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<vg::kMEI, false>), grid, blk, kLocalLds, s->stream, a); break;
-            default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
-            }
-        }
+        const size_t lds = kLocalLds + sizeof(double) * vg::kSparseWgBlocks * vg::kSparseFrame;   // of the fused form
+        known = vg::dispatch_model(s->model, vg::ReferenceModels{}, [&](auto m) {
+            if (fused) hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<decltype(m)::value, true>), grid, blk, lds, s->stream, a);
+            else hipLaunchKernelGGL((vg::vg_sparse_reproject_kernel<decltype(m)::value, false>), grid, blk, kLocalLds, s->stream, a);
+        });
     } else {
         vg::MonoArgs a;
         const dim3 mgrid((unsigned)((np + vg::kMonoThreads - 1) / vg::kMonoThreads)), mblk(vg::kMonoThreads);
@@ -202,13 +192,11 @@ inline int launch(vg_reproject_set *s, int64_t b0, int64_t nb, const double *xi_
         a.jac_len = jac1;
         a.first_block = b0;
         a.n_points = (unsigned)np;
-        switch (s->model) {
-        case vg::kEUCM: hipLaunchKernelGGL((vg::vg_mono_reproject_kernel<vg::kEUCM>), mgrid, mblk, sizeof(double) * vg::kMonoLdsDoubles, s->stream, a); break;
-        case vg::kUCM: hipLaunchKernelGGL((vg::vg_mono_reproject_kernel<vg::kUCM>), mgrid, mblk, sizeof(double) * vg::kMonoLdsDoubles, s->stream, a); break;
-        case vg::kMEI: hipLaunchKernelGGL((vg::vg_mono_reproject_kernel<vg::kMEI>), mgrid, mblk, sizeof(double) * vg::kMonoLdsDoubles, s->stream, a); break;
-        default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
-        }
+        known = vg::dispatch_model(s->model, vg::ReferenceModels{}, [&](auto m) {
+            hipLaunchKernelGGL((vg::vg_mono_reproject_kernel<decltype(m)::value>), mgrid, mblk, sizeof(double) * vg::kMonoLdsDoubles, s->stream, a);
+        });
     }
+    if (!known) return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
     VG_HIP(hipGetLastError());
     return VG_OK;
 }
@@ -324,12 +312,10 @@ int vg_camera_jacobian_evaluate(int device, void *hip_stream, int model, const d
     a.dfdxi = dfdxi;
     a.n = (unsigned)n;
     const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-    switch (model) {
-    case vg::kEUCM: hipLaunchKernelGGL((vg::vg_camera_jacobian_kernel<vg::kEUCM>), grid, blk, vgl::kLocalLds, st, a); break;
-    case vg::kUCM: hipLaunchKernelGGL((vg::vg_camera_jacobian_kernel<vg::kUCM>), grid, blk, vgl::kLocalLds, st, a); break;
-    case vg::kMEI: hipLaunchKernelGGL((vg::vg_camera_jacobian_kernel<vg::kMEI>), grid, blk, vgl::kLocalLds, st, a); break;
-    default: return vgi::fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
-    }
+    const bool known = vg::dispatch_model(model, vg::ReferenceModels{}, [&](auto m) {
+        hipLaunchKernelGGL((vg::vg_camera_jacobian_kernel<decltype(m)::value>), grid, blk, vgl::kLocalLds, st, a);
+    });
+    if (!known) return vgi::fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
     VG_HIP(hipGetLastError());
     return VG_OK;
 }

@@ -97,9 +97,11 @@ int vg_intrinsic_bounds(int model, int idx, double *lower, double *upper)
         else if (idx <= 5) { lo = -10.; hi = 10.; }
     } else if (model == VG_MODEL_KB) {     // k1..k4: Mei's distortion range
         if (idx <= 3) { lo = -10.; hi = 10.; }
-    } else {                               // double sphere (num_intrinsics refused everything else): xi, alpha
+    } else if (model == VG_MODEL_DS) {     // xi, alpha
         if (idx == 0) { lo = -0.9; hi = 3.; }
         else if (idx == 1) { lo = 0.; hi = 1.; }
+    } else {                               // a model of the list (num_intrinsics knows it) without its ranges here
+        return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
     }
     *lower = lo;
     *upper = hi;

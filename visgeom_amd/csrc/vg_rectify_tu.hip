@@ -77,14 +77,8 @@ int vg_rectify_map(int device, void *hip_stream, int model, const double *intrin
     const bool vec = a.width % vg::kRectPix == 0 && aligned16(map_x) && aligned16(map_y);
     VG_HIP(hipSetDevice(device));
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    switch (model) {
-    case vg::kEUCM: launch_map<vg::kEUCM>(a, vec, st); break;
-    case vg::kUCM: launch_map<vg::kUCM>(a, vec, st); break;
-    case vg::kMEI: launch_map<vg::kMEI>(a, vec, st); break;
-    case vg::kKB: launch_map<vg::kKB>(a, vec, st); break;
-    case vg::kDS: launch_map<vg::kDS>(a, vec, st); break;
-    default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
-    }
+    if (!vg::dispatch_model(model, vg::AllModels{}, [&](auto m) { launch_map<decltype(m)::value>(a, vec, st); }))
+        return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
     VG_HIP(hipGetLastError());
     return VG_OK;
 }

@@ -68,6 +68,31 @@ int refine_scratch_for(int device, size_t bytes, size_t obs_bytes, size_t front_
 
 inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
+// The pose-LM launch of one model on a persistent grid: as many workgroups as are resident at once (two per CU at two waves per
+// SIMD: the occupancy of THIS model's kernel, asked once per device; 1 when the query fails, nothing kept for device >= 64),
+// never more than the images need.
+// e0 (may be NULL) is recorded in front of the kernel.
+template <int MODEL>
+int launch_pose_lm(int device, int n_cus, hipStream_t st, const vg::PoseLmArgs &a, hipEvent_t e0)
+{
+    static int per_cu_of[64] = {0};
+    int per_cu = device < 64 ? per_cu_of[device] : 0;
+    if (per_cu < 1) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<MODEL>), vg::kValuThreads, 0) != hipSuccess || per_cu < 1) {
+            (void)hipGetLastError();
+            per_cu = 1;
+        }
+        if (device < 64) per_cu_of[device] = per_cu;
+    }
+    const int64_t wgs_needed = ((int64_t)a.n_images + vg::kValuImagesPerBlock - 1) / vg::kValuImagesPerBlock;
+    const int64_t wgs_resident = (int64_t)per_cu * n_cus;
+    const dim3 grid((unsigned int)(wgs_needed < wgs_resident ? wgs_needed : wgs_resident)), blk(vg::kValuThreads);
+    if (e0) VG_HIP(hipEventRecord(e0, st));
+    hipLaunchKernelGGL(vg::vg_pose_lm_kernel<MODEL>, grid, blk, 0, st, a);
+    VG_HIP(hipGetLastError());
+    return VG_OK;
+}
+
 }  // namespace
 
 void vgi::refine_release_cached()
@@ -193,45 +218,20 @@ int vgi::refine_poses_resident(int device, void *hip_stream, int model, const do
     a.min_rel_decrease = o.min_relative_decrease;
     a.dmin = o.min_lm_diagonal;
     a.dmax = o.max_lm_diagonal;
-    // a persistent grid: as many workgroups as are resident at once (two per CU at two waves per SIMD), never more than the images
-    // need; every half-wave starts on the image of its position and takes further ones from the counter
+    // a persistent grid (launch_pose_lm): every half-wave starts on the image of its position and takes further ones from the counter
     static int cu_count[64] = {0};   // per device, asked once (hipGetDeviceProperties is a millisecond)
-    static int per_cu_of[64][5] = {{0}};   // per device and model: EUCM, UCM, Mei, Kannala-Brandt, double sphere
     if (device < 64 && !cu_count[device]) {
         int cus = 0;
         VG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
         cu_count[device] = cus > 0 ? cus : 1;
     }
     const int n_cus = device < 64 ? cu_count[device] : 256;
-    // the model was checked at entry (num_intrinsics): one of the five
-    const int mi = model == VG_MODEL_EUCM ? 0 : model == VG_MODEL_UCM ? 1 : model == VG_MODEL_MEI ? 2 : model == VG_MODEL_KB ? 3 : 4;
-    int per_cu = device < 64 ? per_cu_of[device][mi] : 0;
-    if (per_cu < 1) {
-        const void *const fns[5] = {reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kEUCM>),
-                                    reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kUCM>),
-                                    reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kMEI>),
-                                    reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kKB>),
-                                    reinterpret_cast<const void *>(vg::vg_pose_lm_kernel<vg::kDS>)};
-        const void *fn = fns[mi];
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, vg::kValuThreads, 0) != hipSuccess || per_cu < 1) {
-            (void)hipGetLastError();
-            per_cu = 1;
-        }
-        if (device < 64) per_cu_of[device][mi] = per_cu;
-    }
-    const int64_t wgs_needed = (n_images + vg::kValuImagesPerBlock - 1) / vg::kValuImagesPerBlock;
-    const int64_t wgs_resident = (int64_t)per_cu * n_cus;
-    const dim3 grid((unsigned int)(wgs_needed < wgs_resident ? wgs_needed : wgs_resident)), blk(vg::kValuThreads);
-    if (kernel_seconds) VG_HIP(hipEventRecord(r.e0, st));
-    switch (model) {
-    case VG_MODEL_EUCM: hipLaunchKernelGGL(vg::vg_pose_lm_kernel<vg::kEUCM>, grid, blk, 0, st, a); break;
-    case VG_MODEL_UCM: hipLaunchKernelGGL(vg::vg_pose_lm_kernel<vg::kUCM>, grid, blk, 0, st, a); break;
-    case VG_MODEL_MEI: hipLaunchKernelGGL(vg::vg_pose_lm_kernel<vg::kMEI>, grid, blk, 0, st, a); break;
-    case VG_MODEL_KB: hipLaunchKernelGGL(vg::vg_pose_lm_kernel<vg::kKB>, grid, blk, 0, st, a); break;
-    case VG_MODEL_DS: hipLaunchKernelGGL(vg::vg_pose_lm_kernel<vg::kDS>, grid, blk, 0, st, a); break;
-    default: return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
-    }
-    VG_HIP(hipGetLastError());
+    int rc = VG_OK;
+    const bool known = vg::dispatch_model(model, vg::AllModels{}, [&](auto m) {
+        rc = launch_pose_lm<decltype(m)::value>(device, n_cus, st, a, kernel_seconds ? (hipEvent_t)r.e0 : nullptr);
+    });
+    if (!known) return fail(VG_ERR_INVALID_ARGUMENT, "unknown camera model");
+    if (rc != VG_OK) return rc;
     if (kernel_seconds) VG_HIP(hipEventRecord(r.e1, st));
     VG_HIP(hipStreamSynchronize(st));   // the kernel's stores to the mapped block are visible once the stream is idle
     drain.armed = false;

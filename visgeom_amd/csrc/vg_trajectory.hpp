@@ -338,7 +338,7 @@ __device__ __forceinline__ void corner_sums(const Setup &s, const double *cam_po
     for (int k = 0; k < kTri; k++) a[k] = c[k] = 0.;
     double lim = 0.;
     int bad = 0;
-    const double cu = s.cam[MODEL == vg::kEUCM ? 4 : MODEL == vg::kUCM ? 3 : 8], cv = s.cam[MODEL == vg::kEUCM ? 5 : MODEL == vg::kUCM ? 4 : 9];
+    const double cu = s.cam[vg::CameraTraits<MODEL>::kFocal + 2], cv = s.cam[vg::CameraTraits<MODEL>::kFocal + 3];
     const double radius = (cu + cv) / 2.;
     for (int k = lane; k < N; k += kWave) {
         const double bx = s.step * (k % s.nx), by = s.step * (k / s.nx);
