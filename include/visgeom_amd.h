@@ -1505,6 +1505,56 @@ int vg_hough_end_points(int width, int height, const double *eucm6, const double
  * be within +-2^24. */
 int vg_hough_trace(const double *poly6, const double *pt4, int max_steps, int32_t *uv, int *n);
 
+/* =====================================================================================
+ * 20. Conversion between camera models: a camera calibrated in one model (Kannala-Brandt, say) brought to another one (EUCM,
+ *     which the image pipelines take).  Pixels to unit rays for every model; the remap maps from one camera into another, which
+ *     feed vg_remap of section 7 unchanged; and a least-squares fit of a model's intrinsics to a calibrated camera.  The
+ *     unprojection of one pixel is visgeom_amd/csrc/vg_unproject.hpp; its order of operations and the fit's rule are DESIGN.md
+ *     section 5.27, the deviations from the reference's reconstructPoint DESIGN.md section 9.  All five models, in every
+ *     combination; every entry checks its arguments before HIP is touched.
+ * ===================================================================================== */
+/* n pixels uv DEVICE [n][2] of the camera (model, intrinsics HOST) to unit rays DEVICE [n][3] and ok DEVICE u8 [n].  A pixel
+ * outside the model's domain, and a NaN or infinite pixel, gives the ray (0, 0, 0) and ok 0.  Stateless and asynchronous on
+ * hip_stream like section 7: no allocation, no synchronisation.  n in [0, 2^31). */
+int vg_unproject(int device, void *hip_stream, int model, const double *intrinsics, int64_t n, const double *uv, double *rays,
+                 uint8_t *ok);
+/* The maps that resample an image of the SOURCE camera into the DESTINATION camera: pixel (j, i) of the destination is
+ * unprojected by the destination model, turned by R(rotvec3) (HOST, destination -> source frame; NULL = no rotation; the models
+ * are central, so there is no translation) and projected by the source model in FP64; map_x / map_y DEVICE float
+ * [height][width] receive the projection rounded to float, (-1, -1) where the unprojection or the projection fails.  The same
+ * model on both sides turns a camera or changes its intrinsics.  Sides in [1, 16384].  Stateless and asynchronous. */
+int vg_convert_map(int device, void *hip_stream, int dst_model, const double *dst_intrinsics, int src_model, const double *src_intrinsics,
+                   const double *rotvec3, int width, int height, float *map_x, float *map_y);
+/* Host only: the default start of the fit.  With f0 the source's paraxial focal lengths ((fu, fv) for EUCM and Kannala-Brandt,
+ * (fu, fv) / (1 + xi) for UCM, Mei and double sphere) and c its centre: EUCM [0.5, 1, f0, c], UCM [1, 2 f0, c],
+ * Mei [1, 0, 0, 0, 0, 0, 2 f0, c], Kannala-Brandt [0, 0, 0, 0, f0, c], double sphere [0, 0.5, f0, c]. */
+int vg_convert_start(int src_model, const double *src_intrinsics, int dst_model, double *dst_intrinsics);
+typedef struct vg_convert_fit_options {
+    int grid_w, grid_h;           /* 64 x 40 samples; at least 1 each, product at most 2^20 */
+    double max_angle;             /* pi: samples whose ray is further than this (radians) from the optical axis are dropped */
+    int max_iterations;           /* 100 */
+    double function_tolerance;    /* 1e-6   Ceres' defaults */
+    double gradient_tolerance;    /* 1e-10 */
+    double parameter_tolerance;   /* 1e-8 */
+    int use_bounds;               /* 1: candidates are kept on the vg_intrinsic_bounds box */
+} vg_convert_fit_options;
+typedef struct vg_convert_fit_summary {
+    int kept, dropped;            /* samples; kept + dropped = grid_w grid_h */
+    int iterations, termination;  /* enum vg_termination */
+    double initial_cost, final_cost;   /* 1/2 sum of squared pixel residuals over the kept samples */
+    double rms, max_residual;     /* pixels, over the kept samples at the returned point */
+} vg_convert_fit_summary;
+void vg_convert_fit_default_options(vg_convert_fit_options *o);
+/* Fits dst_model's intrinsics to the camera (src_model, src_intrinsics HOST) of a width x height image.  Samples: the pixels
+ * u = (a + 0.5) width / grid_w - 0.5, v = (b + 0.5) height / grid_h - 0.5, unprojected on the device by the source model; one
+ * that fails or lies beyond max_angle is dropped.  Cost: 1/2 sum |project_dst(ray) - (u, v)|^2, minimised by the trust-region rule
+ * of the pose solves (Ceres' acceptance and tolerances) from dst_intrinsics (HOST, in / out; a NaN first value means
+ * vg_convert_start).  The sums of an evaluation are reduced in a fixed order: two calls return the same bits.  Synchronous.
+ * options NULL: the defaults; summary may be NULL.  Fewer than K / 2 kept samples: VG_ERR_INVALID_ARGUMENT; a start that cannot
+ * project every kept sample: VG_ERR_NUMERIC, the text names the first one. */
+int vg_convert_fit(int device, void *hip_stream, int src_model, const double *src_intrinsics, int width, int height, int dst_model,
+                   double *dst_intrinsics, const vg_convert_fit_options *options, vg_convert_fit_summary *summary);
+
 /* ---- measurement / test hooks.  The library reads no environment variable to change what it computes or how; the
  * switches used by tests/ and tools/ are set here (process-wide, not thread safe): "inline_chain_max_bytes", "gram_no_merge",
  * "max_obs_per_launch", "solver_timing", "solver_host_loop", "solver_device_loop", "solver_no_fold_frames",

@@ -34,7 +34,7 @@ def sources():
     vg_depth_tu: depth map warp / merge / noise filter; vg_photometric_tu: photometric pose estimation;
     vg_sparse_odom_tu: sparse visual odometry; vg_render_tu: synthetic scene renderer; vg_mono_odom_tu: monocular visual
     odometry; vg_mapping_tu: photometric mapping; vg_trajectory_tu: calibration trajectory planning; vg_dense_ba_tu: photometric
-    bundle adjustment; vg_hough_tu: fisheye line detection)"""
+    bundle adjustment; vg_hough_tu: fisheye line detection; vg_convert_tu: conversion between camera models)"""
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
 
 

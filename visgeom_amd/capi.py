@@ -333,6 +333,11 @@ SIGNATURES = {
     "vg_hough_polynomial": (ctypes.c_int, [_dp, _dp, _dp]),
     "vg_hough_end_points": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _ip]),
     "vg_hough_trace": (ctypes.c_int, [_dp, _dp, ctypes.c_int, _i32p, _ip]),
+    "vg_unproject": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _dp, ctypes.c_int64, _vp, _vp, _vp]),
+    "vg_convert_map": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "vg_convert_start": (ctypes.c_int, [ctypes.c_int, _dp, ctypes.c_int, _dp]),
+    "vg_convert_fit_default_options": (None, [_vp]),
+    "vg_convert_fit": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _vp, _vp]),
     "vg_debug_set": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_longlong]),
     "vg_calib_stream_write": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_double]),
     "vg_calib_stream_copy": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64]),
@@ -443,6 +448,23 @@ class ReconOutputs(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("indices", "hyp", "points", "sigma_out", "index_map", "item", "valid", "cloud")]
 DENSE_BA_MAX_FRAMES, DENSE_BA_TAIL, DENSE_BA_NONE = 8, 5, -1.
 DENSE_BA_DEFAULTS = {"sigma_grey": 5., "prior_weight": 1., "grad_thresh": 250., "max_iterations": 150, "function_tolerance": 1e-6}
+
+
+class ConvertFitOptions(ctypes.Structure):
+    """struct vg_convert_fit_options"""
+    _fields_ = [("grid_w", ctypes.c_int), ("grid_h", ctypes.c_int), ("max_angle", ctypes.c_double), ("max_iterations", ctypes.c_int),
+                ("function_tolerance", ctypes.c_double), ("gradient_tolerance", ctypes.c_double), ("parameter_tolerance", ctypes.c_double),
+                ("use_bounds", ctypes.c_int)]
+
+
+class ConvertFitSummary(ctypes.Structure):
+    """struct vg_convert_fit_summary"""
+    _fields_ = [("kept", ctypes.c_int), ("dropped", ctypes.c_int), ("iterations", ctypes.c_int), ("termination", ctypes.c_int),
+                ("initial_cost", ctypes.c_double), ("final_cost", ctypes.c_double), ("rms", ctypes.c_double),
+                ("max_residual", ctypes.c_double)]
+
+
+CONVERT_MAX_GRID, CONVERT_MAX_SIDE = 1 << 20, 16384
 
 
 class VisgeomError(RuntimeError):
